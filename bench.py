@@ -3,13 +3,19 @@
 stack at BASELINE.json configs[1] (DG sl2048, 102 neurons, batch 128 per GPU,
 num_units 64, k 24, s 2, layer_norm, n_critic 5), bf16 MFMA / f32 accumulate.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one WGAN_GP.train() = 5 critic updates + 1 generator update on one
 batch (reference gan/algorithms/wgan_gp.py:82-95).  Inputs are resident in HBM
 before the timed region; timing is barrier + synchronize on both sides, MAX
 over ranks; rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up and times the K steps.  --full adds the
+legs that take runs of their own: the per-kernel roofline pass (K more steps
+with every MFMA launch timed) and the CPU baseline (`roofline` and
+`cpu_baseline` are null without it).  --dump-outputs DIR writes what the last
+timed step computed (see dump_outputs).
 """
 import argparse
 import json
@@ -182,6 +188,39 @@ def cpu_baseline(hp, batch, steps):
           hp.signal_shape[0], hp.num_channels, hp.num_units, batch, steps))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, gan, out):
+  """What the last timed train() handed its caller -- gen_loss, dis_loss, the
+  gradient penalty and the signal metrics -- and the weights that step left in
+  both models (get_weights(), Keras order), as float32 .npy files under path.
+  Should the weights of a large custom shape push the total past
+  DUMP_LIMIT_BYTES, every array is cut to the same fraction of its flattened
+  elements, drawn by a fixed seed: two runs with the same arguments write the
+  same elements."""
+  from calciumgan_amd.gan.algorithms import wgan_gp as _w
+  gen_loss, dis_loss, gp, metrics = out
+  arrays = [('gen_loss', gen_loss), ('dis_loss', dis_loss),
+            ('gradient_penalty', gp)]
+  arrays += [(k.replace('/', '_'), metrics[k]) for k in _w._METRIC_KEYS]
+  arrays = [(n, v.detach().float().cpu().numpy()) for n, v in arrays]
+  for model in (gan.generator, gan.discriminator):
+    arrays += [('{}_w{:02d}'.format(model.name, i), w)
+               for i, w in enumerate(model.get_weights())]
+  arrays = [(n, np.asarray(a, dtype=np.float32)) for n, a in arrays]
+  total = sum(a.nbytes for _, a in arrays)
+  # (room for the .npy headers, 128 bytes per file)
+  frac = min(1.0, (DUMP_LIMIT_BYTES - 256 * len(arrays)) / float(total))
+  rng = np.random.RandomState(0)
+  os.makedirs(path, exist_ok=True)
+  for name, a in arrays:
+    if frac < 1.0 and a.size > 1:
+      keep = max(1, int(a.size * frac))
+      a = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+    np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--gpus', type=int, default=1)
@@ -202,7 +241,15 @@ def main():
   ap.add_argument('--backend', default='nccl',
                   help="torch.distributed backend ('nccl' = RCCL; 'gloo' only "
                   'for single-GPU rehearsals of the multi-rank path)')
+  ap.add_argument('--full', action='store_true',
+                  help='also run the per-kernel roofline pass and the CPU '
+                  'baseline (each dropped again by its --no_* option)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help="write the last timed step's outputs and the weights "
+                  'it left as DIR/<name>.npy (float32)')
   args = ap.parse_args()
+  if args.steps < 1:
+    ap.error('--steps must be at least 1')
 
   from calciumgan_amd import nets, parallel
   world = parallel.env_world()
@@ -259,6 +306,8 @@ def main():
   barrier()
   dt = time.perf_counter() - t0
   losses = [float(out[0]), float(out[1]), float(out[2])]
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, gan, out)
 
   # Kernel-duration leg of the roofline: the SAME K steps again with every
   # MFMA-kernel launch timed by the library's launch profiler
@@ -270,7 +319,7 @@ def main():
   # it (rank 0's numbers are reported).
   records = []
   dt_prof = None
-  if not args.no_kernel_timing:
+  if args.full and not args.no_kernel_timing:
     import ctypes
     from calciumgan_amd import _lib
     lib = _lib.load()
@@ -405,7 +454,7 @@ def main():
         'final_losses': losses,
         'roofline': roofline,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       line['cpu_baseline'] = cpu_baseline(hp, args.cpu_batch, args.cpu_steps)
     else:
       line['cpu_baseline'] = None

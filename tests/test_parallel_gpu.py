@@ -144,7 +144,7 @@ def test_bench_two_rank_command_path(tmp_path):
   torch.distributed.run with 2 ranks (gloo, both on this box's one GPU), the
   contract's JSON line from rank 0 only."""
   out = _launch(tmp_path, 'gloo', script=os.path.join(ROOT, 'bench.py'),
-                args=['--gpus', '2', '--backend', 'gloo', '--steps', '3',
+                args=['--gpus', '2', '--backend', 'gloo', '--full', '--steps', '3',
                       '--warmup', '2', '--no_cpu_baseline', '--batch', '32'])
   lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
   assert len(lines) == 1, out.stdout[-2000:]

@@ -16,7 +16,7 @@ export CALCIUMGAN_AUTOTUNE=0
 for r in $(seq 1 $ROUNDS); do
   for arm in "$@"; do
     label=${arm%%:*}; envs=${arm#*:}
-    env $envs python3 bench.py $AB_ARGS --steps ${AB_STEPS:-40} --warmup 3 --no_cpu_baseline 2>/dev/null | python3 -c "
+    env $envs python3 bench.py $AB_ARGS --full --steps ${AB_STEPS:-40} --warmup 3 --no_cpu_baseline 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -4,7 +4,7 @@
 # runs one tile / more than one tile.  bench.py twice per variant.
 set -e
 run() {
-  CALCIUMGAN_HIP_LIB=$2 python bench.py --steps 30 --warmup 3 --no_cpu_baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', round(d['value'],1), round(d['ms_per_step'],3), round(d['roofline']['frac'],4))"
+  CALCIUMGAN_HIP_LIB=$2 python bench.py --full --steps 30 --warmup 3 --no_cpu_baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', round(d['value'],1), round(d['ms_per_step'],3), round(d['roofline']['frac'],4))"
 }
 P4='((bx&1)+2*((bx>>8)&1))'
 A=$(bash tools/build_variant.sh none -DCG_SWP_NO_STAGGER | tail -1)

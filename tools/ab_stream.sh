@@ -15,7 +15,7 @@ if [ -f calciumgan_amd/csrc/_head_swconv_swp.hip ]; then   # (a copy of the prev
   OLD=/tmp/cg_old/libcalciumgan_hip.so
 fi
 run() {
-  CALCIUMGAN_HIP_LIB=$2 python bench.py --steps 30 --warmup 3 --no_cpu_baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', round(d['value'],1), round(d['ms_per_step'],3), round(d['roofline']['frac'],4))"
+  CALCIUMGAN_HIP_LIB=$2 python bench.py --full --steps 30 --warmup 3 --no_cpu_baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', round(d['value'],1), round(d['ms_per_step'],3), round(d['roofline']['frac'],4))"
 }
 for i in 1 2; do
   run product ""

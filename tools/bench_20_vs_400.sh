@@ -5,6 +5,7 @@
 # (0.25 s) sits inside the first second of load; the 400-step one shows what the
 # chip sustains.  -> gpurun_out/bench_20_vs_400.txt
 out=gpurun_out/bench_20_vs_400.txt
+b=$(dirname $out)/_b
 mkdir -p gpurun_out
 export CALCIUMGAN_TILE_CACHE=/tmp/cg_b20_tiles.json
 python3 bench.py --steps 2 --warmup 1 --no_cpu_baseline --no_kernel_timing > /dev/null 2>&1 || exit 1
@@ -19,7 +20,7 @@ sample() {  # $1 = pid to follow, $2 = output file
 {
   echo "tools/bench_20_vs_400.sh (commit $(cat profiles/.head_commit 2>/dev/null)): bench.py --steps N --warmup 5, one box, tiles tuned once; rocm-smi every 0.2 s"
   for steps in 20 400 20 400; do
-    python3 bench.py --steps $steps --warmup 5 --no_cpu_baseline ${EXTRA_BENCH_ARGS} > gpurun_out/_b.json 2> gpurun_out/_b.err &
+    python3 bench.py --full --steps $steps --warmup 5 --no_cpu_baseline ${EXTRA_BENCH_ARGS} > $b.json 2> $b.err &
     pid=$!
     sample $pid gpurun_out/_b.smi
     wait $pid

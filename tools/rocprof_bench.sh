@@ -11,7 +11,7 @@ STEPS=${STEPS:-20}; WARMUP=${WARMUP:-3}; P=gpurun_out/${PREFIX:-}
 python3 bench.py $BENCH_ARGS --steps 2 --warmup 1 --no_cpu_baseline --no_kernel_timing > ${P}rocprof_tune.log 2>&1 || exit 1
 export CALCIUMGAN_AUTOTUNE=0
 rm -rf ${P}prof
-rocprofv3 --kernel-trace --stats --output-format csv -d ${P}prof -- python3 bench.py $BENCH_ARGS --steps $STEPS --warmup $WARMUP --no_cpu_baseline > ${P}rocprof_bench.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d ${P}prof -- python3 bench.py $BENCH_ARGS --full --steps $STEPS --warmup $WARMUP --no_cpu_baseline > ${P}rocprof_bench.log 2>&1 || exit 1
 grep "^{" ${P}rocprof_bench.log > ${P}rocprof_bench_line.json
 # warm-up + timed + the eager instrumented steps
 python3 tools/stats.py ${P}prof $((WARMUP + 2 * STEPS)) > ${P}rocprof_kernel_summary.txt
