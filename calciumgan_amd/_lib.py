@@ -146,6 +146,8 @@ SIGNATURES = {
     'cg_dense1_fwd': [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp],
     'cg_dense1_fwd_bwd': [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i,
                           c_i, c_f, c_vp],
+    'cg_dense1_bce': [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                      c_vp, c_i, c_i, c_i, c_i, c_f, c_vp, c_vp],
     'cg_gp_critic_loss': [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_i, c_f, c_vp],
     'cg_gp_loss_scale': [c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f,
                          c_vp, c_vp, c_ll, c_vp],

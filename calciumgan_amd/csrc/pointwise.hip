@@ -871,6 +871,155 @@ __global__ __launch_bounds__(kThreads) void dense1_wgrad_finish(
 }
 
 // ---------------------------------------------------------------------------
+// BCE head of the vanilla GAN step (reference gan.py:43-56, 72-85)
+// ---------------------------------------------------------------------------
+// One block per sample of [fake | real] (2B samples, the fake segment first).
+// Pass 1 is dense1_fwd_kernel's loop and reduction unchanged (same logits); the
+// block then forms the Keras BCE terms and the seed coefficients from the logit
+// and, in pass 2, writes the seeds of both backward chains:
+//   coef_d[b] = S_d * (s(x_b) - y_b) / B     y = 0 on fake, 1 on real
+//   coef_g[b] = S_g * (s(x_b) - 1) / B       fake segment only
+//   delta_d[b] = coef_d[b] * bf16(w) * lrelu'(h[b]),  delta_g likewise.
+// kRow > 1: the row is kept in LDS between the passes (cfg2: 40 KB); kRow == 1:
+// pass 2 reads h again (it is still in L2 / MALL).  The per-sample terms go to
+// `terms` ([2B] discriminator, [B] generator) for dense1_bce_finish, or, without
+// a workspace, straight onto `loss` with atomics.
+__device__ __forceinline__ float sigmoid_stable(float x) {
+  if (x >= 0.f) return 1.f / (1.f + expf(-x));
+  const float e = expf(x);
+  return e / (1.f + e);
+}
+// tf.nn.sigmoid_cross_entropy_with_logits: max(x, 0) - x z + log1p(exp(-|x|))
+__device__ __forceinline__ float bce_logits(float x, float z) {
+  return fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x)));
+}
+
+template <int NT, int kRow>
+__global__ __launch_bounds__(NT) void dense1_bce_kernel(
+    const uint16_t* __restrict__ h, const float* __restrict__ w,
+    const float* __restrict__ bias, float* __restrict__ out,
+    float* __restrict__ coef_d, float* __restrict__ coef_g,
+    uint16_t* __restrict__ delta_d, uint16_t* __restrict__ delta_g,
+    const float* __restrict__ scale_d, const float* __restrict__ scale_g,
+    float* __restrict__ terms, float* __restrict__ loss, int B, int F, int C,
+    int Cp, float alpha) {
+  constexpr int kThreads = NT;  // (shadows the file's 256 inside this kernel)
+  __shared__ float part[NT / 64];
+  __shared__ float cfs[2];
+  __shared__ uint4 row[kRow];
+  const int b = blockIdx.x;
+  const bool fake = b < B;
+  float s = 0.f;
+  constexpr int kNB = NT >= 1024 ? 2 : 4;  // load pairs in flight per lane
+  for (int i0 = threadIdx.x * 8; i0 < F; i0 += kNB * kThreads * 8) {
+    uint4 raw[kNB];
+    float wv[kNB][8];
+#pragma unroll
+    for (int k = 0; k < kNB; ++k) {
+      const int i = i0 + k * kThreads * 8;
+      const bool ok = i < F;
+      raw[k] = ok ? ldg16(h + (long long)b * F + i) : make_uint4(0u, 0u, 0u, 0u);
+      const int t = ok ? i / Cp : 0;
+      const int c = ok ? i - t * Cp : 0;
+      load8f(w + (long long)t * C + c, ok ? C - c : 0, C, wv[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < kNB; ++k) {
+      float v[8];
+      unpack8(raw[k], v);
+      const int i = i0 + k * kThreads * 8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float wq = act2f(f2act(wv[k][e]));
+        s += v[e] * wq;
+      }
+      if (kRow > 1 && i < F) row[i >> 3] = raw[k];
+    }
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = part[0];
+#pragma unroll
+    for (int k = 1; k < NT / 64; ++k) t += part[k];
+    const float x = t + bias[0];
+    out[b] = x;
+    const float inv_b = 1.f / (float)B;
+    // s(x) - 1 as -s(-x): no cancellation for large positive x
+    const float sd = fake ? sigmoid_stable(x) : -sigmoid_stable(-x);
+    const float cd = sd * inv_b * (scale_d ? scale_d[0] : 1.f);
+    const float cg = -sigmoid_stable(-x) * inv_b * (scale_g ? scale_g[0] : 1.f);
+    const float td = bce_logits(x, fake ? 0.f : 1.f);
+    if (coef_d) coef_d[b] = cd;
+    if (fake && coef_g) coef_g[b] = cg;
+    if (terms) {
+      terms[b] = td;
+      if (fake) terms[2 * B + b] = bce_logits(x, 1.f);
+    } else {
+      atomicAdd(loss + 1, td * inv_b);
+      if (fake) atomicAdd(loss, bce_logits(x, 1.f) * inv_b);
+    }
+    cfs[0] = cd;
+    cfs[1] = cg;
+  }
+  if (!delta_d) return;
+  __syncthreads();
+  const float cd = cfs[0], cg = cfs[1];
+  uint16_t* gout = (fake && delta_g) ? delta_g + (long long)b * F : nullptr;
+  for (int i = threadIdx.x * 8; i < F; i += kThreads * 8) {
+    const uint4 raw = kRow > 1 ? row[i >> 3] : ldg16(h + (long long)b * F + i);
+    const int t = i / Cp;
+    const int ch = i - t * Cp;
+    float v[8], wv[8], od[8], og[8];
+    load8f(w + (long long)t * C + ch, C - ch, C, wv);
+    unpack8(raw, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float g = (ch + e < C) ? act2f(f2act(wv[e])) * (v[e] > 0.f ? 1.f : alpha)
+                                   : 0.f;
+      od[e] = cd * g;
+      og[e] = cg * g;
+    }
+    store8(delta_d + (long long)b * F + i, od);
+    if (gout) store8(gout + i, og);
+  }
+}
+
+// loss[0] = mean_b terms[2B + b] (generator), loss[1] = mean over the real
+// segment + mean over the fake segment (discriminator): one block, fixed order
+__global__ __launch_bounds__(kThreads) void dense1_bce_finish(
+    const float* __restrict__ terms, float* __restrict__ loss, int B) {
+  __shared__ float part[3][kThreads / 64];
+  float sf = 0.f, sr = 0.f, sg = 0.f;
+  for (int b = threadIdx.x; b < B; b += kThreads) {
+    sf += terms[b];
+    sr += terms[B + b];
+    sg += terms[2 * B + b];
+  }
+  sf = wave_sum(sf);
+  sr = wave_sum(sr);
+  sg = wave_sum(sg);
+  if ((threadIdx.x & 63) == 0) {
+    part[0][threadIdx.x >> 6] = sf;
+    part[1][threadIdx.x >> 6] = sr;
+    part[2][threadIdx.x >> 6] = sg;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float f = part[0][0], r = part[1][0], g = part[2][0];
+#pragma unroll
+    for (int k = 1; k < kThreads / 64; ++k) {
+      f += part[0][k];
+      r += part[1][k];
+      g += part[2][k];
+    }
+    loss[0] = g / (float)B;
+    loss[1] = r / (float)B + f / (float)B;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // phase unshuffle + LeakyReLU mask
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void unshuffle_mask_kernel(
@@ -1821,6 +1970,41 @@ extern "C" int cg_dense1_wgrad(const void* x, const float* coef,
     hipLaunchKernelGGL(dense1_wgrad_finish, dim3((F + kThreads - 1) / kThreads),
                        dim3(kThreads), 0, S_(stream), ws, dw, db, gy, F, Fpad, C,
                        Cp, bias_coef ? 1 : 0);
+  CG_LAUNCH_CHECK();
+}
+
+// rows of h up to this many 16-byte groups stay in LDS between the two passes
+// of dense1_bce_kernel (64 KiB; cfg2's 64 x 320 row is 2560 groups, 40 KB)
+constexpr int kBceLdsGroups = 4096;
+
+extern "C" int cg_dense1_bce(const void* h, const float* w, const float* bias,
+                             float* out, float* coef_d, float* coef_g,
+                             void* delta_d, void* delta_g, float* loss,
+                             const float* scale_d, const float* scale_g, int B,
+                             int Lt, int C, int Cp, float alpha, float* ws,
+                             void* stream) {
+  const int F = Lt * Cp;
+  if (Cp % 8 || C > Cp || B < 1 || !h || !w || !bias || !out || !loss)
+    return CG_EINVAL;
+  if (delta_g && !delta_d) return CG_EINVAL;
+  if (ws && 3ll * B > kReduceWsElems) return CG_EINVAL;
+  const dim3 grid(2 * B);
+  const bool lds = delta_d && F / 8 <= kBceLdsGroups;
+#define CG_BCE_LAUNCH(NT, ROW)                                                      \
+  hipLaunchKernelGGL((dense1_bce_kernel<NT, ROW>), grid, dim3(NT), 0, S_(stream),   \
+                     U16(h), w, bias, out, coef_d, coef_g, U16W(delta_d),           \
+                     U16W(delta_g), scale_d, scale_g, ws, loss, B, F, C, Cp, alpha)
+  if (F >= 8192) {
+    if (lds) CG_BCE_LAUNCH(1024, kBceLdsGroups);
+    else CG_BCE_LAUNCH(1024, 1);
+  } else {
+    if (lds) CG_BCE_LAUNCH(256, 1024);  // (F < 8192: at most 1023 groups)
+    else CG_BCE_LAUNCH(256, 1);
+  }
+#undef CG_BCE_LAUNCH
+  if (ws)
+    hipLaunchKernelGGL(dense1_bce_finish, dim3(1), dim3(kThreads), 0, S_(stream),
+                       ws, loss, B);
   CG_LAUNCH_CHECK();
 }
 

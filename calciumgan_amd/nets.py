@@ -1000,10 +1000,12 @@ class _DisPlan(object):
     segments' (the plan's X0 need not hold x^ then)."""
     return self.fwd_l1_pair is not None
 
-  def forward(self, seed_backward=False, mix=None):
-    """act[0] (already filled) -> d_out[:nB].  seed_backward: the head's pass
-    over h5 also writes delta_5 = coef * w_d * lrelu'(h5) (the seed does not
-    depend on the head's output: one launch and one read of h5 instead of two);
+  def forward(self, seed_backward=False, mix=None, head=True):
+    """act[0] (already filled) -> d_out[:nB].  head=False: the convolutions
+    only (the caller runs its own head on act[-1]: cg_dense1_bce).
+    seed_backward: the head's pass over h5 also writes
+    delta_5 = coef * w_d * lrelu'(h5) (the seed does not depend on the head's
+    output: one launch and one read of h5 instead of two);
     backward_chain(seeded=True) then starts from it.  mix (f32 per sample of a
     segment; plans with mixes_layer1): the third segment is x^ = mix * real +
     (1 - mix) * fake -- its layer 1 is cg_lrelu_mix of the first two segments'."""
@@ -1020,6 +1022,8 @@ class _DisPlan(object):
       rest = self.fwd
     for d in rest:
       _run_conv(d, st)
+    if not head:
+      return
     last = net.layers[-1]
     if seed_backward:
       _lib.call('cg_dense1_fwd_bwd', _p(ws.act[-1]), _p(net.dense_w),
@@ -1063,20 +1067,25 @@ class _DisPlan(object):
     for d in self.jvp:
       _run_conv(d, st)
 
-  def weight_grads(self, bias_rows):
+  def weight_grads(self, bias_rows, head_coef=None):
     """Accumulate dW (all nB samples), db (first bias_rows samples; taken
     inside the wgrad kernel from the delta tiles it stages) and the dense head
-    gradients into params.grad (caller zeroed it)."""
+    gradients into params.grad (caller zeroed it).  head_coef (f32 [nB]): the
+    head's seed per SAMPLE, for its weight and bias gradient both (the BCE step)
+    instead of the plan's per-segment coef / bias_coef."""
     st = _stream()
     net, ws = self.ws.net, self.ws
     for i, d in enumerate(self.wgrad):
       d.bias_rows = bias_rows * net.layers[i].lout
     _run_wgrads(self.wgrad, st)
     last = net.layers[-1]
-    _lib.call('cg_dense1_wgrad', _p(ws.act[-1]), _p(self.coef),
-              _p(self.bias_coef), _p(net.params.grad_views[-2]),
+    coef, bias_coef, seg = self.coef, self.bias_coef, self.seg_size
+    if head_coef is not None:
+      coef, bias_coef, seg = head_coef, head_coef, 1
+    _lib.call('cg_dense1_wgrad', _p(ws.act[-1]), _p(coef),
+              _p(bias_coef), _p(net.params.grad_views[-2]),
               _p(net.params.grad_views[-1]), self.nB, last.lout, last.cout,
-              last.coutp, self.seg_size, _p(reduce_ws(net.device)), st)
+              last.coutp, seg, _p(reduce_ws(net.device)), st)
 
 
 # ===========================================================================

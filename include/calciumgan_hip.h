@@ -27,7 +27,7 @@ extern "C" {
 #endif
 
 #define CG_EINVAL 100001
-#define CG_ABI_VERSION 19
+#define CG_ABI_VERSION 20
 
 /* epilogue selectors of cg_swconv */
 #define CG_EPI_NONE 0     /* y = acc (+bias) */
@@ -465,6 +465,28 @@ int cg_dense1_wgrad(const void* x /*bf16 [nB][Lt][Cp]*/, const float* coef,
                     const float* bias_coef /*device [nseg]*/, float* dw,
                     float* db, int nB, int Lt, int C, int Cp, int seg_size,
                     float* ws, void* stream);
+
+/* Head of the vanilla (BCE) GAN step (gan.py:43-56, 72-85; ABI 20).  h holds
+ * 2B samples [fake | real] (fake segment first).  Per sample, x = the logit of
+ * cg_dense1_fwd (same sum order) -> out[b]; with s the sigmoid and y = 0 on the
+ * fake segment, 1 on the real one:
+ *   coef_d[b] = S_d * (s(x_b) - y_b) / B             (NULL: not written)
+ *   coef_g[b] = S_g * (s(x_b) - 1) / B, b < B        (NULL: not written)
+ *   delta_d[b][t][c] = coef_d[b] * bf16(w[t*C+c]) * lrelu'(h[b][t][c])  (2B rows)
+ *   delta_g[b][t][c] = coef_g[b] * bf16(w[t*C+c]) * lrelu'(h[b][t][c])  (B rows)
+ * (delta_d NULL: no seeds; delta_g NULL: no generator seeds).  S_d / S_g are
+ * device scalars (the fp16 loss scales; NULL = 1).  Keras BCE from logits,
+ * max(x,0) - x y + log1p(exp(-|x|)), averaged per segment:
+ *   loss[0] = mean_fake BCE(1, x)                      (generator loss)
+ *   loss[1] = mean_real BCE(1, x) + mean_fake BCE(0, x) (discriminator loss)
+ * With ws (3B floats of it) the means are an ordered reduction and stored;
+ * without, they are added with atomics onto a zeroed loss. */
+int cg_dense1_bce(const void* h /*[2B][Lt][Cp]*/, const float* w,
+                  const float* bias, float* out /*[2B]*/, float* coef_d /*[2B]*/,
+                  float* coef_g /*[B]*/, void* delta_d, void* delta_g,
+                  float* loss /*[2]*/, const float* scale_d,
+                  const float* scale_g, int B, int Lt, int C, int Cp,
+                  float alpha, float* ws, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Backward of LeakyReLU + PhaseShuffle between discriminator layers:
