@@ -36,6 +36,7 @@ c_vp = C.c_void_p
 c_i = C.c_int
 c_ll = C.c_longlong
 c_f = C.c_float
+c_d = C.c_double
 
 
 class ConvDesc(C.Structure):
@@ -180,11 +181,21 @@ SIGNATURES = {
     'cg_signal_metrics': [c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_i, c_f, c_f,
                           c_vp, c_vp],
     'cg_step_outputs': [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp],
+    # spikes.hip: deconvolution and spike statistics during validation
+    'cg_oasis_ws_bytes': [c_ll, c_i],
+    'cg_oasis_ar1_batched': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_f, c_f,
+                             c_d, c_d, c_d, c_vp, c_vp, c_ll, c_ll, c_ll, c_vp,
+                             c_vp, c_vp, c_ll, c_vp],
+    'cg_spike_stats': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_vp, c_vp, c_vp],
+    'cg_spike_stats_error_ws_elems': [c_ll, c_ll],
+    'cg_spike_stats_error': [c_vp, c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_vp,
+                             c_vp],
 }
 _RESTYPES = {'cg_packed_elems': c_ll, 'cg_pack_plan_bytes': c_ll,
              'cg_pack_plan_build': c_ll, 'cg_wgrad_partials_elems': c_ll,
              'cg_dense_wgrad_ws_elems': c_ll, 'cg_rowsumsq_ws_elems': c_ll,
-             'cg_reduce_ws_elems': c_ll, 'cg_wgrad_flex_plan': c_ll}
+             'cg_reduce_ws_elems': c_ll, 'cg_wgrad_flex_plan': c_ll,
+             'cg_oasis_ws_bytes': c_ll, 'cg_spike_stats_error_ws_elems': c_ll}
 
 _libs = {}       # precision -> ctypes handle
 _active = 'bf16'  # precision of the library `call` / `load()` address

@@ -14,9 +14,9 @@ LIB = os.path.join(CSRC, 'libcalciumgan_hip.so')
 # the same sources with fp16 activations (-DCG_ACT_F16=1): mixed_float16 mode
 LIB_F16 = os.path.join(CSRC, 'libcalciumgan_hip_f16.so')
 SOURCES = ['swconv.hip', 'swconv_swp.hip', 'wgrad.hip', 'pointwise.hip',
-           'dense_rows.hip']
-HEADERS = ['cg_common.h', 'swconv_args.h', os.path.join('..', '..', 'include',
-                                       'calciumgan_hip.h')]
+           'dense_rows.hip', 'spikes.hip']
+HEADERS = ['cg_common.h', 'swconv_args.h', 'oasis_flat.h',
+           os.path.join('..', '..', 'include', 'calciumgan_hip.h')]
 
 
 def _hipcc():
@@ -73,6 +73,7 @@ def build(force=False, verbose=True):
 
 HOST_LIB = os.path.join(CSRC, 'libcalciumgan_host.so')
 HOST_SOURCES = ['oasis_ar1.c', 'crc32c.c']
+HOST_HEADERS = ['oasis_flat.h']
 
 
 def build_host(force=False, verbose=True):
@@ -80,8 +81,9 @@ def build_host(force=False, verbose=True):
   post-hoc spike statistics, CRC-32C for TFRecord framing; not part of the GPU
   hot path)."""
   srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES]
+  deps = srcs + [os.path.join(CSRC, h) for h in HOST_HEADERS]
   if (not force and os.path.exists(HOST_LIB) and
-      all(os.path.getmtime(s) <= os.path.getmtime(HOST_LIB) for s in srcs)):
+      all(os.path.getmtime(s) <= os.path.getmtime(HOST_LIB) for s in deps)):
     return HOST_LIB
   cmd = ['gcc', '-O2', '-shared', '-fPIC', '-o', HOST_LIB] + srcs + ['-lm']
   if verbose:

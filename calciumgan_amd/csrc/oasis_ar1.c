@@ -55,6 +55,32 @@ int cg_oasis_ar1(const double* y, int T, double g, double lam, double s_min,
   return 0;
 }
 
+/* out[l] = pow(g, l) for l in [0, n): the powers cg_oasis_ar1 takes, by the same
+ * libm call (the device kernel reads them from this table -- spikes.hip). */
+int cg_oasis_pow_table(double g, int n, double* out) {
+  if (n < 0 || !out) return 1;
+  for (int l = 0; l < n; ++l) out[l] = pow(g, l);
+  return 0;
+}
+
+/* The device kernel's per-lane loop (oasis_flat.h) on the host, one float32
+ * trace: gpow = cg_oasis_pow_table(g, T + 1); c / s may be null.  What the
+ * tests compare with cg_oasis_ar1 where no GPU is at hand. */
+#include "oasis_flat.h"
+int cg_oasis_ar1_flat(const float* x, int T, float scale, float offset,
+                      double g, double s_min, double threshold,
+                      const double* gpow, float* spikes, double* c, double* s) {
+  if (T < 1 || !x || !gpow || !spikes) return 1;
+  double* sv = (double*)malloc((sizeof(double) * 2 + sizeof(int)) * (size_t)T);
+  if (!sv) return 2;
+  double* sw = sv + T;
+  int* sl = (int*)(sw + T);
+  cg_oasis_flat(x, 1, !(scale == 1.0f && offset == 0.0f), scale, offset, T, g,
+                s_min, threshold, gpow, sv, sw, sl, 1, spikes, 1, c, s);
+  free(sv);
+  return 0;
+}
+
 /* rows x T signals -> binarised spike trains (spike_helper.py:23-29: s > thr) */
 int cg_deconvolve(const double* signals, int rows, int T, double g,
                   double s_min, double threshold, float* spikes) {

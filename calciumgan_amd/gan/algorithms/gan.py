@@ -109,6 +109,58 @@ class GAN(object):
         'signals_metrics/std': buf[3],
     }
 
+  # -- spike statistics of a validation batch (csrc/spikes.hip) ----------------
+  def spike_real_statistics(self, real_spikes):
+    """Device (rates (B, C), covariances (B, C (C + 1) / 2)) of the ground-truth
+    trains (B, L, C) of a validation batch, taken as
+    compute_dg_metrics.get_data_statistics takes them from a file with `spikes`
+    (the trains as float32, no deconvolution).  An unshuffled validation set
+    gives the same batches every epoch: the caller may keep the result."""
+    from ..utils import spike_metrics
+    if not torch.is_tensor(real_spikes):
+      import numpy as np
+      real_spikes = torch.from_numpy(
+          np.ascontiguousarray(np.asarray(real_spikes), dtype=np.float32))
+    spikes = real_spikes.to(device=self.device, dtype=torch.float32)
+    return spike_metrics.batch_statistics_device(spikes)
+
+  def spike_statistics(self, fake, real_spikes=None, real_stats=None):
+    """The spike criterion of one validation batch, on the device: `fake`
+    ((B, L, C) f32 as validate() returns it, or the channel-padded generator
+    output: only the first C channels are read) is denormalised with this
+    algorithm's signals_min / max, deconvolved (OASIS AR(1), g 0.95, s_min 0.55,
+    threshold 0.5: spike_helper.deconvolve_signals bit for bit) and reduced to
+    per-trial firing rates and binned covariances; the real side comes from
+    the ground-truth trains `real_spikes` (B, L, C), or from `real_stats` =
+    spike_real_statistics(real_spikes) kept by the caller; sample i is paired
+    with sample i.  Returns 0-d device tensors: the sums of |d| and d^2 of both
+    statistics (compute_dg_metrics.report's MAE / RMSE / MSE are these sums
+    divided by the counts) and the two counts.  No host sync."""
+    from ..utils import spike_helper, spike_metrics
+    C = self.signal_shape[-1]
+    fake = fake[:, :, :C]
+    if real_stats is None:
+      real_stats = self.spike_real_statistics(real_spikes)
+    spikes = spike_helper.deconvolve_signals_device(
+        fake, scale=self._signals_max - self._signals_min,
+        offset=self._signals_min)
+    rates, covs = spike_metrics.batch_statistics_device(spikes)
+    if rates.shape != real_stats[0].shape:
+      raise ValueError('fake batch {} and real trains {} differ in shape'.format(
+          tuple(rates.shape), tuple(real_stats[0].shape)))
+    sums = spike_metrics.error_sums_device(real_stats[0], rates, real_stats[1],
+                                           covs)
+    count = lambda t: torch.tensor(float(t.numel()), dtype=torch.float64,
+                                   device=self.device)
+    return {
+        'firing_rate_abs_sum': sums[0],
+        'firing_rate_sq_sum': sums[1],
+        'covariance_abs_sum': sums[2],
+        'covariance_sq_sum': sums[3],
+        'firing_rate_count': count(rates),
+        'covariance_count': count(covs),
+    }
+
   # -- the BCE step (gan.py:43-90) ---------------------------------------------
   def _bce_get_state(self, B):
     states = self.__dict__.setdefault('_bce_states', {})

@@ -30,6 +30,12 @@ def _load():
                                   ctypes.c_double, ctypes.c_double,
                                   ctypes.c_double,
                                   ctypes.POINTER(ctypes.c_float)]
+    lib.cg_oasis_pow_table.argtypes = [ctypes.c_double, ctypes.c_int, dp]
+    fp = ctypes.POINTER(ctypes.c_float)
+    lib.cg_oasis_ar1_flat.argtypes = [fp, ctypes.c_int, ctypes.c_float,
+                                      ctypes.c_float, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, dp, fp,
+                                      dp, dp]
     _lib = lib
   return _lib
 
@@ -89,3 +95,112 @@ def deconvolve_signals(signals, threshold=0.5):
   if rc:
     raise RuntimeError('cg_deconvolve failed: {}'.format(rc))
   return out
+
+
+# -- on the device (csrc/spikes.hip) -------------------------------------------
+OASIS_G, OASIS_S_MIN = 0.95, 0.55  # spike_helper.py:24
+
+
+def oasis_pow_table(g, n):
+  """float64 (n,): pow(g, l) for l < n by the libm call cg_oasis_ar1 makes (the
+  device kernel reads its powers from this table: device pow is another
+  function, and numpy's vectorised power may be a SIMD variant)."""
+  out = np.empty(n, dtype=np.float64)
+  rc = _load().cg_oasis_pow_table(
+      g, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+  if rc:
+    raise RuntimeError('cg_oasis_pow_table failed: {}'.format(rc))
+  return out
+
+
+def oasis_ar1_flat(x, g, s_min=0.0, threshold=0.5, scale=1.0, offset=0.0):
+  """(c, s, spikes) of one float32 trace by the device kernel's per-lane loop
+  (csrc/oasis_flat.h) compiled for the host: the CPU check of that loop against
+  `oasis_ar1`."""
+  x = np.ascontiguousarray(x, dtype=np.float32)
+  T = len(x)
+  gpow = oasis_pow_table(g, T + 1)
+  c, s = np.empty(T), np.empty(T)
+  spikes = np.empty(T, dtype=np.float32)
+  dp, fp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float)
+  rc = _load().cg_oasis_ar1_flat(x.ctypes.data_as(fp), T, scale, offset, g,
+                                 s_min, threshold, gpow.ctypes.data_as(dp),
+                                 spikes.ctypes.data_as(fp), c.ctypes.data_as(dp),
+                                 s.ctypes.data_as(dp))
+  if rc:
+    raise RuntimeError('cg_oasis_ar1_flat failed: {}'.format(rc))
+  return c, s, spikes
+
+
+_DEVICE_CACHE = {}  # (kind, device, ...) -> tensor
+
+
+def _device_pow_table(device, g, T):
+  """gpow[0 .. T] on `device`, uploaded once per (device, g) and grown on
+  demand -- never from inside a launch."""
+  import torch
+  key = ('gpow', str(device), float(g))
+  t = _DEVICE_CACHE.get(key)
+  if t is None or t.numel() < T + 1:
+    t = _DEVICE_CACHE[key] = torch.from_numpy(oasis_pow_table(g, T + 1)).to(device)
+  return t
+
+
+def _device_workspace(device, nbytes):
+  """The pool-stack workspace, one per device, grown on demand and kept (535 MB
+  for a cfg2 batch).  Calls share it: they must be ordered on one stream."""
+  import torch
+  key = ('ws', str(device))
+  t = _DEVICE_CACHE.get(key)
+  if t is None or t.numel() * 8 < nbytes:
+    t = _DEVICE_CACHE[key] = torch.empty((nbytes + 7) // 8, dtype=torch.float64,
+                                         device=device)
+  return t
+
+
+def deconvolve_signals_device(signals, threshold=0.5, scale=1.0, offset=0.0,
+                              g=OASIS_G, s_min=OASIS_S_MIN, return_cs=False):
+  """`deconvolve_signals` on the GPU, bit for bit: a float32 device tensor of
+  (rows, T) traces, or of (B, L, C) with the traces along axis 1 (any strides:
+  a channel-padded generator output is read in place), -> float32 {0, 1} trains
+  of the same logical shape.  The traces deconvolved are (double)(signals *
+  scale + offset) with float32 product and sum, i.e. utils.denormalize of the
+  float32 array with scale = max - min, offset = min.  return_cs: also the
+  float64 (traces, T) calcium and spike-size arrays (tests)."""
+  import torch
+  from ... import _lib as hip
+  from ... import nets
+  if not (torch.is_tensor(signals) and signals.is_cuda):
+    raise ValueError('deconvolve_signals_device needs a device tensor '
+                     '(deconvolve_signals is the host path)')
+  if signals.dtype != torch.float32 or signals.dim() not in (2, 3):
+    raise ValueError('float32 (rows, T) or (B, L, C) expected')
+  dev = signals.device
+  out = torch.empty(signals.shape, dtype=torch.float32, device=dev)
+  if signals.dim() == 2:
+    rows, T = signals.shape
+    n_outer, n_inner = 1, rows
+    sx = (0, signals.stride(1), signals.stride(0))
+    so = (0, out.stride(1), out.stride(0))
+  else:
+    n_outer, T, n_inner = signals.shape
+    sx = (signals.stride(0), signals.stride(1), signals.stride(2))
+    so = (out.stride(0), out.stride(1), out.stride(2))
+  traces = n_outer * n_inner
+  if traces == 0 or T == 0:
+    raise ValueError('empty input')
+  lib = hip.load()
+  nbytes = lib.cg_oasis_ws_bytes(traces, T)
+  if nbytes < 0:
+    raise ValueError('cg_oasis_ws_bytes: unsupported shape')
+  ws = _device_workspace(dev, nbytes)
+  gpow = _device_pow_table(dev, g, T)
+  c = s = None
+  if return_cs:
+    c = torch.empty(traces, T, dtype=torch.float64, device=dev)
+    s = torch.empty(traces, T, dtype=torch.float64, device=dev)
+  hip.call('cg_oasis_ar1_batched', nets._p(signals), n_outer, n_inner, T, sx[0],
+           sx[1], sx[2], scale, offset, g, s_min, threshold, nets._p(gpow),
+           nets._p(out), so[0], so[1], so[2], nets._p(c), nets._p(s),
+           nets._p(ws), nbytes, nets._stream())
+  return (out, c, s) if return_cs else out

@@ -119,3 +119,89 @@ def victor_purpura_distance(spikes1, spikes2=None, q=1.0):
   if spikes2 is not None:
     result = result[len(spikes1):, :len(spikes2)]
   return result
+
+
+# -- a batch of trials at once: the statistics compute_dg_metrics.py reports ----
+def batch_statistics(spikes):
+  """(rates (B, C), covariances (B, C (C + 1) / 2)) float32 of a batch of binary
+  trains (B, T, C): per trial what compute_dg_metrics.get_data_statistics stores
+  -- `mean_firing_rate` and the upper triangle (np.triu_indices order) of
+  `covariance` of the (C, T) float32 trains."""
+  spikes = np.asarray(spikes)
+  B, _, C = spikes.shape
+  rates = np.zeros((B, C), np.float32)
+  covs = np.zeros((B, C * (C + 1) // 2), np.float32)
+  iu = np.triu_indices(C)
+  for b in range(B):
+    trial = spikes[b].T.astype(np.float32)
+    rates[b] = mean_firing_rate(trial)
+    covs[b] = np.nan_to_num(covariance(trial)[iu])
+  return rates, covs
+
+
+def error_sums(rates_a, rates_b, covs_a, covs_b):
+  """float64 (4,): sum |d| and sum d^2 of the firing rates, then of the
+  covariances -- the sums behind compute_dg_metrics.report (sums, not means: an
+  epoch is formed from its batches)."""
+  dr = np.asarray(rates_a, np.float64) - np.asarray(rates_b, np.float64)
+  dc = np.asarray(covs_a, np.float64) - np.asarray(covs_b, np.float64)
+  return np.array([np.abs(dr).sum(), np.square(dr).sum(), np.abs(dc).sum(),
+                   np.square(dc).sum()])
+
+
+def report_from_sums(sums, n_rates, n_covs):
+  """The four figures main.py --spike_metrics logs, by the definitions of
+  compute_dg_metrics.report over n_rates / n_covs compared values.  (MAPE is
+  a per-trial quantity, not a sum over values: not formed here.)"""
+  s = [float(v) for v in sums]
+  return {
+      'spike_metrics/firing_rate_mae': s[0] / n_rates,
+      'spike_metrics/firing_rate_rmse': float(np.sqrt(s[1] / n_rates)),
+      'spike_metrics/covariance_mae': s[2] / n_covs,
+      'spike_metrics/covariance_mse': s[3] / n_covs,
+  }
+
+
+def batch_statistics_device(spikes):
+  """`batch_statistics` on the GPU (cg_spike_stats): float32 device tensor
+  (B, T, C) of {0, 1}, any strides, -> device (rates (B, C), covariances
+  (B, C (C + 1) / 2)) float32.  Rates equal the host's float32; covariances are
+  the exact integer sums divided once (the host's float64 np.cov rounds more
+  often: equal to ~1e-7 relative)."""
+  import torch
+  from ... import _lib as hip
+  from ... import nets
+  if not (torch.is_tensor(spikes) and spikes.is_cuda and
+          spikes.dtype == torch.float32 and spikes.dim() == 3):
+    raise ValueError('float32 device tensor (B, T, C) expected')
+  B, T, C = spikes.shape
+  rates = torch.empty(B, C, dtype=torch.float32, device=spikes.device)
+  covs = torch.empty(B, C * (C + 1) // 2, dtype=torch.float32,
+                     device=spikes.device)
+  hip.call('cg_spike_stats', nets._p(spikes), B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), nets._p(rates), nets._p(covs),
+           nets._stream())
+  return rates, covs
+
+
+def error_sums_device(rates_a, rates_b, covs_a, covs_b):
+  """`error_sums` on the GPU (cg_spike_stats_error): float32 device (4,), an
+  ordered two-stage reduction -- the same bits every call."""
+  import torch
+  from ... import _lib as hip
+  from ... import nets
+  ts = [rates_a, rates_b, covs_a, covs_b]
+  if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+             for t in ts):
+    raise ValueError('contiguous float32 device tensors expected')
+  if rates_a.shape != rates_b.shape or covs_a.shape != covs_b.shape:
+    raise ValueError('the two sets of statistics differ in shape')
+  n_r, n_c = rates_a.numel(), covs_a.numel()
+  dev = rates_a.device
+  ws = torch.empty(hip.load().cg_spike_stats_error_ws_elems(n_r, n_c),
+                   dtype=torch.float32, device=dev)
+  out = torch.empty(4, dtype=torch.float32, device=dev)
+  hip.call('cg_spike_stats_error', nets._p(rates_a), nets._p(rates_b), n_r,
+           nets._p(covs_a), nets._p(covs_b), n_c, nets._p(out), nets._p(ws),
+           nets._stream())
+  return out

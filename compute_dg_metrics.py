@@ -6,6 +6,12 @@ firing rates and the upper-triangular covariance of 500-ms-binned counts, and
 print MAE / RMSE / MAPE.
 
   python compute_dg_metrics.py --output_dir runs/001 [--num_trials 5]
+      [--device gpu]
+
+--device gpu (not a reference flag) takes the deconvolution and the per-trial
+statistics through the HIP kernels of csrc/spikes.hip -- the spike trains are
+the host's bit for bit, the firing rates equal, the covariances equal to
+float32 rounding -- which makes a --num_trials in the hundreds affordable.
 """
 import argparse
 import os
@@ -32,6 +38,24 @@ def get_data_statistics(hparams, filename):
     cov = spike_metrics.covariance(spikes)
     covariances[:, i] = np.nan_to_num(cov[np.triu_indices(len(cov))])
   return firing_rates, covariances
+
+
+def get_data_statistics_device(hparams, filename):
+  """`get_data_statistics` through the device kernels: all trials in one batch
+  (spike_helper.deconvolve_signals_device, spike_metrics.batch_statistics_device)."""
+  import torch
+  device = torch.device('cuda', torch.cuda.current_device())
+  have_spikes = h5_helper.contains(filename, 'spikes')
+  name = 'spikes' if have_spikes else 'signals'
+  batch = np.stack([np.asarray(h5_helper.get(filename, name, trial=i),
+                               dtype=np.float32)
+                    for i in range(hparams.num_trials)])  # (trials, W, C)
+  batch = torch.from_numpy(batch).to(device)
+  if not have_spikes:
+    batch = spike_helper.deconvolve_signals_device(batch)
+  rates, covs = spike_metrics.batch_statistics_device(batch)
+  return (np.ascontiguousarray(rates.cpu().numpy().T),
+          np.ascontiguousarray(covs.cpu().numpy().T))
 
 
 def percentage_error(y_true, y_pred):
@@ -74,8 +98,10 @@ def main(hparams):
   with open(os.path.join(hparams.generated_dir, 'info.pkl'), 'rb') as f:
     info = pickle.load(f)
   epochs = sorted(info.keys())
-  real_fr, real_cov = get_data_statistics(hparams, hparams.validation_cache)
-  fake_fr, fake_cov = get_data_statistics(hparams, info[epochs[-1]]['filename'])
+  stats = (get_data_statistics_device
+           if getattr(hparams, 'device', 'cpu') == 'gpu' else get_data_statistics)
+  real_fr, real_cov = stats(hparams, hparams.validation_cache)
+  fake_fr, fake_cov = stats(hparams, info[epochs[-1]]['filename'])
   r = report(real_fr, fake_fr, real_cov, fake_cov)
   print('\nmean firing rate\n\tMAE\t{mae:.02f}\n\tRMSE\t{rmse:.02f}\n\tMAPE\t'
         '{mape:.02f}%'.format(**r['firing_rate']))
@@ -93,8 +119,14 @@ def main(hparams):
   return r
 
 
-if __name__ == '__main__':
+def build_parser():
   parser = argparse.ArgumentParser()
   parser.add_argument('--output_dir', default='runs')
   parser.add_argument('--num_trials', default=5, type=int)
-  main(parser.parse_args())
+  parser.add_argument('--device', default='cpu', choices=['cpu', 'gpu'],
+                      help='gpu: deconvolution and statistics on the device')
+  return parser
+
+
+if __name__ == '__main__':
+  main(build_parser().parse_args())

@@ -617,6 +617,64 @@ int cg_step_outputs(const float* gen_loss, const float* loss, const float* gp,
                     const float* metrics, int n, float* out /*[7]*/,
                     void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Spike statistics during validation (spikes.hip; no counterpart on a device in
+ * the reference, which deconvolves on the host: main.py:142-154,
+ * gan/utils/spike_helper.py:23-54, compute_dg_metrics.py:40-58).  Functions
+ * added under ABI 20; the same in both precision builds (nothing here touches
+ * an activation type).
+ * ------------------------------------------------------------------------- */
+/* OASIS AR(1) deconvolution with a minimum spike size (oasisAR1(y, g, s_min),
+ * lam = 0), one trace per lane in float64, then spike = s > threshold: bit for
+ * bit what the host library computes (csrc/oasis_ar1.c: cg_oasis_ar1 /
+ * cg_deconvolve) on the same float64 input.
+ *   trace (o, i), o < n_outer, i < n_inner, frame t:
+ *     y = (double)x[o * sx_outer + t * sx_t + i * sx_inner]
+ *   or, unless scale == 1 and offset == 0, (double)(x * scale + offset) with the
+ *   product and the sum each rounded to float32 (denormalisation of a float32
+ *   array); strides in elements.  Consecutive lanes take consecutive i: a
+ *   (B, L, Cf) batch is read in place with n_inner = C, sx_inner = 1, and a
+ *   (rows, T) array with n_outer = 1, n_inner = rows, sx_inner = T.
+ *   spikes: float32 {0, 1} with strides of its own; c / s: float64 [traces][T]
+ *   (trace = o * n_inner + i) or NULL.
+ *   gpow: DEVICE float64 [T + 1], gpow[l] = pow(g, l) as the HOST's libm gives
+ *   it (cg_oasis_pow_table of libcalciumgan_host.so), uploaded by the caller.
+ *   ws: cg_oasis_ws_bytes(traces, T) bytes, 8-byte aligned: the pool stacks at
+ *   full depth (20 bytes x T per trace, interleaved by trace).  A smaller or
+ *   larger workspace is legal from 64 traces' worth: the call then walks the
+ *   batch in groups of the traces it holds, one launch per group.
+ * T <= 2^24.  Never spins: at most 2 T iterations per trace, NaN included. */
+long long cg_oasis_ws_bytes(long long traces, int T);
+int cg_oasis_ar1_batched(const float* x, int n_outer, int n_inner, int T,
+                         long long sx_outer, long long sx_t, long long sx_inner,
+                         float scale, float offset, double g, double s_min,
+                         double threshold, const double* gpow, float* spikes,
+                         long long so_outer, long long so_t, long long so_inner,
+                         double* c, double* s, void* ws, long long ws_bytes,
+                         void* stream);
+/* Per sample b < B of binary trains spikes[b * s_b + t * s_t + c * s_c] (float32,
+ * 24 frames per second):
+ *   rates[b][c] = sum_t spikes / (T / 24)        (spike_metrics.mean_firing_rate)
+ *   cov[b][p]   = unbiased covariance of the 500-ms bin counts of neurons (i, j),
+ *                 p running over i <= j in np.triu_indices order
+ *                 (spike_metrics.covariance; 12 frames per bin, a trailing
+ *                 partial bin dropped, nb = T / 12 bins)
+ * rates f32 [B][C], cov f32 [B][C (C + 1) / 2].  The sums are exact integers;
+ * only the final quotient rounds.  CG_EINVAL: nb < 2, or 4 C + nb C > 60 KiB
+ * (the counts of one sample are kept in LDS). */
+int cg_spike_stats(const float* spikes, int B, int T, int C, long long s_b,
+                   long long s_t, long long s_c, float* rates, float* cov,
+                   void* stream);
+/* out[0] = sum |fr_a - fr_b|, out[1] = sum (fr_a - fr_b)^2 over n_fr elements,
+ * out[2], out[3] the same for cov over n_cov elements (the sums behind
+ * compute_dg_metrics.report's MAE / RMSE / MSE; sums, so that an epoch is formed
+ * from its batches).  Ordered two-stage reduction through ws
+ * (cg_spike_stats_error_ws_elems floats): the same bits every run. */
+long long cg_spike_stats_error_ws_elems(long long n_fr, long long n_cov);
+int cg_spike_stats_error(const float* fr_a, const float* fr_b, long long n_fr,
+                         const float* cov_a, const float* cov_b, long long n_cov,
+                         float* out /*[4]*/, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,8 +12,9 @@ Differences, all documented: without --mixed_precision activations are bf16
 (f32 accumulation, f32 master weights) where the reference computes in f32;
 with it they are fp16 with the reference's dynamic loss scaling
 (mixed_float16).  Scalars go to TensorBoard event files (written without
-TensorFlow) and JSON lines; trace plots / spike deconvolution in the loop
-(main.py:142-154) are out of scope; under torchrun every rank trains on its
+TensorFlow) and JSON lines; trace plots (main.py:142-154) are out of scope;
+the spike deconvolution the reference does there on the host is --spike_metrics
+here, on the device (csrc/spikes.hip); under torchrun every rank trains on its
 own shard of each batch and rank 0 writes the files.
 """
 import argparse
@@ -74,12 +75,17 @@ def validate(hparams, validation_ds, gan, summary, epoch):
                     (epoch % 10 == 0 or epoch == hparams.epochs - 1)) or (
                         hparams.save_generated == 'last' and
                         epoch == hparams.epochs - 1)
+  spike_metrics_on = getattr(hparams, 'spike_metrics', False)
+  spike_sums = None
   start = time()
-  for signal, _ in validation_ds:
+  for batch_index, (signal, spike) in enumerate(validation_ds):
     signal = _shard(hparams, signal)
     if signal is None:
       continue
     fake, gen_loss, dis_loss, gradient_penalty, metrics = gan.validate(signal)
+    if spike_metrics_on:
+      sums = _spike_sums(validation_ds, gan, batch_index, fake, spike)
+      spike_sums = sums if spike_sums is None else spike_sums + sums
     gen_losses.append(float(gen_loss))
     dis_losses.append(float(dis_loss))
     if gradient_penalty is not None:
@@ -93,6 +99,11 @@ def validate(hparams, validation_ds, gan, summary, epoch):
         utils.save_fake_signals(hparams, epoch, signals=fake)
   gen_loss, dis_loss = float(np.mean(gen_losses)), float(np.mean(dis_losses))
   results = {key: float(np.mean(item)) for key, item in results.items()}
+  if spike_sums is not None:
+    # compute_dg_metrics.report's definitions over every validated sample
+    from calciumgan_amd.gan.utils import spike_metrics
+    sums = spike_sums.tolist()
+    results.update(spike_metrics.report_from_sums(sums[:4], sums[4], sums[5]))
   end = time()
   if summary is not None:
     summary.log(gen_loss, dis_loss,
@@ -100,6 +111,25 @@ def validate(hparams, validation_ds, gan, summary, epoch):
                 None, metrics=results, elapse=end - start, step=epoch,
                 training=False)
   return gen_loss, dis_loss
+
+
+_SPIKE_SUM_KEYS = ('firing_rate_abs_sum', 'firing_rate_sq_sum',
+                   'covariance_abs_sum', 'covariance_sq_sum',
+                   'firing_rate_count', 'covariance_count')
+
+
+def _spike_sums(validation_ds, gan, batch_index, fake, spike):
+  """--spike_metrics: the error sums and counts of one validation batch as a
+  float64 device (6,) (gan.spike_statistics: deconvolution and statistics on
+  the device, no host sync).  The validation set is not shuffled, so batch k
+  holds the same ground-truth trains every epoch: their statistics are
+  computed once and kept on the dataset object."""
+  import torch
+  kept = validation_ds.__dict__.setdefault('_spike_real_stats', {})
+  if batch_index not in kept:
+    kept[batch_index] = gan.spike_real_statistics(np.asarray(spike))
+  s = gan.spike_statistics(fake, real_stats=kept[batch_index])
+  return torch.stack([s[k].double() for k in _SPIKE_SUM_KEYS])
 
 
 def train_and_validate(hparams, train_ds, validation_ds, gan, summary):
@@ -163,6 +193,11 @@ def main(hparams, return_metrics=False):
 
   parallel.init_process_group()
   hparams.rank, hparams.world_size = parallel.rank(), parallel.world_size()
+  if getattr(hparams, 'spike_metrics', False) and hparams.world_size > 1:
+    # (the sums would have to be all-reduced and the ground-truth trains
+    # sharded like the signals; not done: there was no multi-GPU node to test on)
+    raise SystemExit('--spike_metrics is single-process only: run it without '
+                     'torchrun, or drop the flag under data parallelism')
 
   if hparams.rank == 0:
     if hparams.clear_output_dir and os.path.exists(hparams.output_dir):
@@ -201,7 +236,9 @@ def main(hparams, return_metrics=False):
 
 def build_parser():
   """main.py:227-262 -- same flags and defaults (the reference's default
-  --model 'wavegan' is not registered there either; use --model calciumgan)."""
+  --model 'wavegan' is not registered there either; use --model calciumgan).
+  --profile's meaning and --spike_metrics are this project's: the reference has
+  no --spike_metrics flag (it deconvolves on the host inside its loop)."""
   parser = argparse.ArgumentParser()
   parser.add_argument('--input_dir', default='dataset/tfrecords')
   parser.add_argument('--output_dir', default='runs')
@@ -232,6 +269,15 @@ def build_parser():
   parser.add_argument('--profile', action='store_true',
                       help='time every MFMA-kernel launch of batches 2-6 of the '
                       'second epoch -> <output_dir>/profiler/mfma_kernels.json')
+  # (absent from the namespace unless given, so that a run without it carries
+  # exactly the reference's flag set, hparams.json included; read it with
+  # getattr(hparams, 'spike_metrics', False))
+  parser.add_argument('--spike_metrics', action='store_true',
+                      default=argparse.SUPPRESS,
+                      help='validation also deconvolves the generated batch on '
+                      'the GPU and logs spike_metrics/{firing_rate_mae,'
+                      'firing_rate_rmse,covariance_mae,covariance_mse} against '
+                      'the ground-truth spike trains (single process only)')
   parser.add_argument('--dpi', default=120, type=int)
   parser.add_argument('--verbose', default=1, type=int)
   return parser
