@@ -79,19 +79,9 @@ def _ratio_cos(got, ref):
 # ---------------------------------------------------------------------------
 # 1. the head kernel
 # ---------------------------------------------------------------------------
-def _ulp(x, f16):
-  """One ulp of bf16 (8 significant bits) / fp16 (11, subnormals from 2^-14)
-  at |x|, float64."""
-  a = np.abs(x)
-  e = np.floor(np.log2(np.where(a > 0, a, 1.0)))
-  if f16:
-    return np.where(a > 0, 2.0**np.maximum(e - 10, -24), 2.0**-24)
-  return np.where(a > 0, 2.0**(e - 7), 2.0**-133)
-
-
-def _round_act(x, f16):
-  t = torch.tensor(x, dtype=torch.float32)
-  return t.to(torch.float16 if f16 else torch.bfloat16).double().numpy()
+# (one ulp of the activation type at |x|; x rounded to it on the host)
+from pointwise_ref import round_act as _round_act  # noqa: E402
+from pointwise_ref import ulp_act as _ulp  # noqa: E402
 
 
 @pytest.mark.parametrize('precision', ['bf16', 'f16'])
