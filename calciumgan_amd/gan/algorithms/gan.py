@@ -17,8 +17,11 @@ One train() (gan.py:72-85) on a batch `real` of B samples:
      layer 1, from delta_5 of c_g; generator backward
   7. signal metrics of this fake batch; (data parallel) all-reduce of both
      gradients; Adam on D, then on G -- after every read of D's weights
-There is no n_critic loop and no penalty.  The state of the step lives under
-`_bce_` names: WGAN_GP subclasses this class and never touches it.
+There is no n_critic loop and no penalty.
+
+GAN is also the base of every algorithm: train() is a template over the
+per-class pieces (_build_state, _segments, _fill_stage, _adam_steps,
+_graph_under_dp) that replay.py drives, eagerly or as hipGraph replays.
 """
 import os
 
@@ -27,6 +30,7 @@ import torch
 from ... import _lib
 from ... import nets
 from ... import parallel
+from . import replay
 from .optimizer import Optimizer
 from .registry import register
 
@@ -35,19 +39,17 @@ from .registry import register
 _SEED = int(__import__('os').environ.get('CALCIUMGAN_SEED', '1234'))
 _METRIC_KEYS = ('signals_metrics/min', 'signals_metrics/max',
                 'signals_metrics/mean', 'signals_metrics/std')
-# the BCE step replays as one hipGraph after this many eager calls per batch
-# size (single rank; CALCIUMGAN_GRAPH=0 keeps it eager, as for WGAN-GP)
-_BCE_GRAPH_WARMUP_CALLS = 2
-# pinned staging slots of the host-drawn inputs of a replay (phase shifts, Adam
-# step sizes): the host may run this many steps ahead before it waits
-_BCE_STAGING_SLOTS = 4
-# staged words per step: [2B plan shifts int32 (4, 2) | fake-segment plan
+# staged words of a BCE step: [2B plan shifts int32 (4, 2) | fake-segment plan
 # shifts (4, 1) | Adam step sizes f32 (D, G)]
 _BCE_STAGE_WORDS = 14
 
 
 @register('gan')
 class GAN(object):
+  # the BCE step replays as a graph on a single rank only
+  _graph_under_dp = False
+  # train() returns None in the penalty position
+  _has_penalty = False
 
   def __init__(self, hparams, generator, discriminator, summary=None):
     self.generator = generator
@@ -73,6 +75,11 @@ class GAN(object):
     self._sync = parallel.GradSync()
     self._streams = parallel.RandomStreams(_SEED, self.device, hparams.m)
     self._metrics_buf = torch.zeros(4, dtype=torch.float32, device=self.device)
+    # per-batch-size state of the step (workspaces, plans, captured graphs)
+    self._state = {}
+    # CALCIUMGAN_GRAPH=0 keeps every step eager; main.py's --profile window
+    # switches it off and back through the same attribute
+    self._use_graph = os.environ.get('CALCIUMGAN_GRAPH', '1') != '0'
 
   # -- helpers ---------------------------------------------------------------
   def _to_device(self, x):
@@ -162,32 +169,35 @@ class GAN(object):
     }
 
   # -- the BCE step (gan.py:43-90) ---------------------------------------------
-  def _bce_get_state(self, B):
-    states = self.__dict__.setdefault('_bce_states', {})
-    st = states.get(B)
+  def _get_state(self, B):
+    st = self._state.get(B)
     if st is None:
-      dev = self.device
-      dws = self.discriminator.net.workspace(2 * B)
-      stage = torch.zeros(_BCE_STAGE_WORDS, dtype=torch.int32, device=dev)
-      f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-      st = dict(
-          gws=self.generator.net.workspace(B),
-          dws=dws,
-          stage_dev=stage,
-          # D chain over [fake | real]; segment 0 is the fake batch
-          dis=dws.plan(2 * B, B, None, want_norm=False,
-                       shifts=stage[0:8].view(4, 2)),
-          # G chain: the same workspace's first B samples (the fake segment's
-          # activations of the 2B forward), input gradient down to layer 1
-          gen=dws.plan(B, B, 0, want_norm=False, shifts=stage[8:12].view(4, 1)),
-          coef_d=f32(2 * B),
-          coef_g=f32(B),
-          delta_g=torch.zeros_like(dws.delta[-1][:B]),
-          loss=f32(2),  # [gen_loss, dis_loss]
-          zero=f32(1),  # (the penalty slot of cg_step_outputs)
-          out=f32(7))
-      states[B] = st
+      st = self._state[B] = self._build_state(B)
     return st
+
+  def _build_state(self, B):
+    dev = self.device
+    dws = self.discriminator.net.workspace(2 * B)
+    stage = torch.zeros(_BCE_STAGE_WORDS, dtype=torch.int32, device=dev)
+    f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+    return dict(
+        gws=self.generator.net.workspace(B),
+        dws=dws,
+        stage_dev=stage,
+        # D chain over [fake | real]; segment 0 is the fake batch
+        dis=dws.plan(2 * B, B, None, want_norm=False,
+                     shifts=stage[0:8].view(4, 2)),
+        # G chain: the same workspace's first B samples (the fake segment's
+        # activations of the 2B forward), input gradient down to layer 1
+        gen=dws.plan(B, B, 0, want_norm=False, shifts=stage[8:12].view(4, 1)),
+        coef_d=f32(2 * B),
+        coef_g=f32(B),
+        delta_g=torch.zeros_like(dws.delta[-1][:B]),
+        loss=f32(2),  # [gen_loss, dis_loss]
+        zero=f32(1),  # (the penalty slot of cg_step_outputs)
+        # the step's outputs [gen_loss, dis_loss, 0, metrics x 4], written by
+        # the last launches of train(); train() hands out a COPY
+        out=f32(7))
 
   def _bce_shifts(self, r):
     """Host int32 (12,): the (4, 2) [fake | real] shifts of the 2B plan, then the
@@ -240,7 +250,7 @@ class GAN(object):
     (dict(z=, shifts_real=, shifts_fake=)), dict(shifts_dev=True) when the
     shifts are staged on the device (graph replay), or None."""
     B = real.shape[0]
-    st = self._bce_get_state(B)
+    st = self._get_state(B)
     net_g, net_d = self.generator.net, self.discriminator.net
     if r is None or 'shifts_dev' in r:
       z = self.get_noise(B)
@@ -267,7 +277,7 @@ class GAN(object):
   def _bce_step(self, real, r=None, lr_dev=None):
     """One whole train(): compute, metrics, gradient sync, Adam on D then G,
     the outputs buffer.  lr_dev (graph replay): the staged Adam step sizes."""
-    st = self._bce_get_state(real.shape[0])
+    st = self._get_state(real.shape[0])
     self._bce_compute(real, r)
     metrics = self.metrics(real, st['gws'].fake, fake_pitch=self.generator.net.Cf)
     self._sync.all_reduce(self.discriminator.net.params.grad)
@@ -286,118 +296,73 @@ class GAN(object):
               nets._p(st['out']), nets._stream())
     return st['out']
 
-  def _bce_returns(self, o):
-    """(gen_loss, dis_loss, metrics) as views of a fresh copy of the outputs
-    buffer (the next step rewrites it in place); the means over the ranks under
-    data parallelism."""
+  def _outputs(self, o):
+    """(gen_loss, dis_loss, gradient_penalty or None, metrics) as views of a
+    fresh COPY of the step's output buffer: the buffer itself is rewritten by
+    the next train() -- in place, when the step replays as a graph -- so callers
+    may keep the returned tensors across steps without a host sync (main.py
+    averages them at the end of the epoch).  Data parallel: averaged over the
+    ranks, one 7-float all-reduce per step."""
     o = self._sync.mean_scalars(o.clone())
-    return o[0], o[1], {k: o[3 + i] for i, k in enumerate(_METRIC_KEYS)}
+    return (o[0], o[1], o[2] if self._has_penalty else None,
+            {k: o[3 + i] for i, k in enumerate(_METRIC_KEYS)})
 
-  def batch_buffer(self, B):
-    """The device buffer a replay of train() reads its batch of B samples from,
-    (B,) + signal_shape f32: a loader that gathers each batch into it saves the
-    copy in front of every replay (as WGAN_GP.batch_buffer)."""
-    st = self._bce_get_state(B)
-    g = st.get('graph')
-    if g is not None:
-      return g['real']
-    if st.get('batch_buf') is None:
-      st['batch_buf'] = torch.empty((B,) + self.signal_shape,
-                                    dtype=torch.float32, device=self.device)
-    return st['batch_buf']
+  # -- the pieces replay.py drives ---------------------------------------------
+  @property
+  def _adam_steps(self):
+    """Adam steps per train() of (discriminator, generator)."""
+    return 1, 1
 
-  def _bce_capture(self, real, st):
-    """Capture one train() as ONE hipGraph.  The shifts and the Adam step sizes
-    of a replay are copied into the state's stage buffer ahead of it
-    (_bce_stage); z comes from the graph-registered device generator."""
-    g = dict(
-        real=(st['batch_buf'] if st.get('batch_buf') is not None and
-              st['batch_buf'].shape == real.shape else torch.empty_like(real)),
-        stage_host=[torch.zeros(_BCE_STAGE_WORDS, dtype=torch.int32).pin_memory()
-                    for _ in range(_BCE_STAGING_SLOTS)],
-        stage_event=[None] * _BCE_STAGING_SLOTS,
-        stage_next=0)
-    if g['real'].data_ptr() != real.data_ptr():
-      g['real'].copy_(real)
-    lr_dev = st['stage_dev'][12:].view(torch.float32)
-    steps = (self.dis_optimizer.host_steps, self.gen_optimizer.host_steps)
-    torch.cuda.synchronize()
-    try:
-      graph = torch.cuda.CUDAGraph()
-      graph.register_generator_state(self._streams.local)
-      with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-        g['out'] = self._bce_step(g['real'], dict(shifts_dev=True), lr_dev)
-    finally:
-      # capture only records: undo the host step counters it advanced
-      self.dis_optimizer.host_steps, self.gen_optimizer.host_steps = steps
-    g['graph'] = graph
-    return g
+  def _segments(self, real, rand=None, staged=False):
+    """The whole BCE step as one segment.  staged (graph replay): the shifts
+    and the Adam step sizes are read from the state's stage buffer."""
+    lr_dev = None
+    if staged:
+      rand = dict(shifts_dev=True)
+      st = self._get_state(real.shape[0])
+      lr_dev = st['stage_dev'][12:].view(torch.float32)
+    return [(lambda: self._bce_step(real, rand, lr_dev), None, False)]
 
-  def _bce_stage(self, st, g):
-    """Shifts and Adam step sizes of the coming replay -> the stage buffer,
-    through a ring of pinned slots (an event per slot keeps the host from
-    rewriting a slot whose copy has not run yet)."""
-    k = g['stage_next']
-    g['stage_next'] = (k + 1) % _BCE_STAGING_SLOTS
-    if g['stage_event'][k] is not None:
-      g['stage_event'][k].synchronize()
-    host = g['stage_host'][k]
+  def _fill_stage(self, host):
     host[:12] = self._bce_shifts(None)
     lr = host[12:].view(torch.float32)
     lr[0] = self.dis_optimizer.lr_t(self.dis_optimizer.host_steps + 1)
     lr[1] = self.gen_optimizer.lr_t(self.gen_optimizer.host_steps + 1)
-    st['stage_dev'].copy_(host, non_blocking=True)
-    ev = g['stage_event'][k] = torch.cuda.Event()
-    ev.record()
 
-  def _bce_train_graphed(self, real, st):
-    g = st.get('graph')
-    if g is None:
-      try:
-        g = st['graph'] = self._bce_capture(real, st)
-      except Exception as e:  # noqa: BLE001 -- any capture failure
-        import warnings
-        warnings.warn('calciumgan_amd: hipGraph capture of train() failed '
-                      '({}: {}); continuing with eager launches'.format(
-                          type(e).__name__, e))
-        self._use_graph = False
-        torch.cuda.synchronize()
-        return self._bce_step(real)
-    if g['real'].data_ptr() != real.data_ptr():
-      g['real'].copy_(real)
-    # (the draw order of an eager step: z on the device generator inside the
-    # graph, then the shifts here)
-    self._bce_stage(st, g)
-    g['graph'].replay()
-    self.dis_optimizer.host_steps += 1
-    self.gen_optimizer.host_steps += 1
-    return g['out']
+  def batch_buffer(self, B):
+    """The device buffer train() reads a batch of B samples from when it replays
+    its hipGraph: (B,) + signal_shape, f32.  A data loader that gathers every
+    batch INTO it (torch.index_select(..., out=buffer)) saves the copy train()
+    otherwise makes in front of each replay; passing any other tensor stays
+    valid.  One buffer per batch size, alive as long as this object."""
+    return replay.batch_buffer(self._get_state(B), (B,) + self.signal_shape,
+                               self.device)
 
   def train(self, inputs, rand=None):
-    """gan.py:72-85: ONE forward of G and D on [fake | real], both models'
-    gradients from it with D's weights before either update, then Adam on D and
-    on G.  Returns (gen_loss, dis_loss, None, metrics) as 0-d device tensors (no
-    host sync; views of a copy, valid across later steps; the means over the
-    ranks under data parallelism).  rand = dict(z=, shifts_real=, shifts_fake=)
-    injects the draws; otherwise z (per-rank device stream), then one (4, 2)
-    draw [shifts_real | shifts_fake] of the shared stream.  A single rank
-    replays the step as a hipGraph after two eager calls per batch size."""
+    """One step of the algorithm (the class's module docstring; gan.py:72-85
+    here).  Returns (gen_loss, dis_loss, gradient_penalty or None, metrics) as
+    0-d device tensors (no host sync inside; each call returns views of its own
+    small buffer, so they stay valid across later steps; under data parallelism
+    they are the means over all ranks).  `rand` optionally injects the random
+    draws for parity tests (here dict(z=, shifts_real=, shifts_fake=); otherwise
+    z from the per-rank device stream, then one (4, 2) draw [shifts_real |
+    shifts_fake] of the shared stream).  After two eager calls per batch size a
+    graphable step replays as hipGraphs."""
     _lib.use(self.precision)
     real = self._to_device(inputs)
-    st = self._bce_get_state(real.shape[0])
-    # (set on first use, not in __init__: WGAN_GP sets its own.  main.py's
-    # --profile window switches it off and back through the same attribute)
-    use_graph = self.__dict__.setdefault(
-        '_use_graph', os.environ.get('CALCIUMGAN_GRAPH', '1') != '0')
-    if rand is None and use_graph and self._sync.world == 1:
+    st = self._get_state(real.shape[0])
+    if (rand is None and self._use_graph and
+        (self._graph_under_dp or self._sync.world == 1)):
       st['calls'] = st.get('calls', 0) + 1
-      if st['calls'] > _BCE_GRAPH_WARMUP_CALLS:
-        o = self._bce_train_graphed(real, st)
-        gen_loss, dis_loss, metrics = self._bce_returns(o)
-        return gen_loss, dis_loss, None, metrics
-    o = self._bce_step(real, rand)
-    gen_loss, dis_loss, metrics = self._bce_returns(o)
-    return gen_loss, dis_loss, None, metrics
+      if st['calls'] > replay.GRAPH_WARMUP_CALLS:
+        return self._outputs(replay.replay(self, st, real))
+    # an eager step between replays (injected randomness, main.py's --profile
+    # window).  The captured graphs stay valid: they hold pointers to buffers
+    # that live as long as this object, and nothing in them depends on what ran
+    # in between.  (Round 2 dropped them here after "stale graph" penalties of
+    # 1e25; the cause was a hipMemsetAsync NODE inside the captured step --
+    # cg_rownorm's -- not stale memory: DESIGN.md section 8.)
+    return self._outputs(replay.eager(self, st, real, rand))
 
   def validate(self, inputs, rand=None):
     """gan.py:87-90 / :58-70: the same losses with training=False, no update.
@@ -405,7 +370,7 @@ class GAN(object):
     _lib.use(self.precision)
     real = self._to_device(inputs)
     B = real.shape[0]
-    st = self._bce_get_state(B)
+    st = self._get_state(B)
     if rand is None:
       z = self.get_noise(B)
       shifts = self._bce_shifts(None)
@@ -415,10 +380,9 @@ class GAN(object):
     # (the staged shifts of a captured step are rewritten before each replay)
     fake = self._bce_forward(st, real, z, shifts, training=False, seeds=False)
     metrics = self.metrics(real, fake, fake_pitch=self.generator.net.Cf)
-    gen_loss, dis_loss, metrics = self._bce_returns(
-        self._bce_outputs(st, metrics))
     C = self.generator.net.C
-    return fake[:, :, :C].clone(), gen_loss, dis_loss, None, metrics
+    return (fake[:, :, :C].clone(),) + self._outputs(
+        self._bce_outputs(st, metrics))
 
   def generate(self, noise, denorm=False):
     """gan.py:92-97."""

@@ -26,24 +26,20 @@ import torch
 
 from ... import _lib
 from ... import nets
-from .gan import GAN
+from .gan import GAN, _METRIC_KEYS
 from .registry import register
 
 # hipGraph capture of train(): the ~370 launches of one step replay as ONE
 # graph on a single rank, and under data parallelism as 2 * n_critic + 3 graphs
 # cut around the gradient all-reduces (the RCCL calls stay eager between
 # replays and overlap the graphs that do not need their result), removing
-# launch gaps.  CALCIUMGAN_GRAPH=0 disables it.
-_GRAPH_WARMUP_CALLS = 2
+# launch gaps (replay.py).  CALCIUMGAN_GRAPH=0 disables it.
 # development knob: keep the multi-rank segmentation on a single rank
 _FORCE_SPLIT = os.environ.get('CALCIUMGAN_SPLIT_SEGMENTS', '0') == '1'
 # single rank: one generator pass for the fake batches of all critic updates
 # of a step (CALCIUMGAN_BATCH_G=0: one pass per update, as under data
 # parallelism, where each pass hides the previous update's all-reduce)
 _BATCH_G = os.environ.get('CALCIUMGAN_BATCH_G', '1') != '0'
-# data parallel, A/B only: wait for every gradient all-reduce right after it is
-# started instead of overlapping it with the next segment
-_DP_OVERLAP = os.environ.get('CALCIUMGAN_DP_OVERLAP', '1') != '0'
 # the penalty norm's finishing sum, gp / coef / critic loss and v's per-sample
 # scale as ONE launch (cg_gp_loss_scale) instead of three (A/B: =0)
 _FUSE_GP = os.environ.get('CALCIUMGAN_FUSE_GP', '1') != '0'
@@ -52,15 +48,12 @@ _FUSE_GP = os.environ.get('CALCIUMGAN_FUSE_GP', '1') != '0'
 # epilogue (cg_dense_rows_interp), one input buffer per update -- instead of an
 # f32 fake batch that n_critic cg_interp_pack launches read back (A/B: =0)
 _FUSE_INTERP = os.environ.get('CALCIUMGAN_FUSE_INTERP', '1') != '0'
-_METRIC_KEYS = ('signals_metrics/min', 'signals_metrics/max',
-                'signals_metrics/mean', 'signals_metrics/std')
-# pinned staging slots for the host-drawn inputs of a graph replay: the host may
-# run this many steps ahead of the GPU before it waits for a slot's copy
-_STAGING_SLOTS = 4
 
 
 @register('wgan-gp')
 class WGAN_GP(GAN):
+  _has_penalty = True
+  _graph_under_dp = True  # (as segments cut around the all-reduces)
 
   def __init__(self, hparams, generator, discriminator, summary=None):
     super().__init__(hparams, generator, discriminator, summary)
@@ -69,59 +62,54 @@ class WGAN_GP(GAN):
     self.conv2d = getattr(hparams, 'conv2d', False)
     if self.conv2d:
       raise ValueError('calciumgan_amd: conv2d models are out of scope')
-    self._state = {}
-    self._use_graph = os.environ.get('CALCIUMGAN_GRAPH', '1') != '0'
 
   # -- per-batch-size state ---------------------------------------------------
-  def _get_state(self, B):
-    st = self._state.get(B)
-    if st is None:
-      dev = self.device
-      dws = self.discriminator.net.workspace(3 * B)
-      nc = self.n_critic
-      # host-drawn inputs of a step on the device: [shifts int32 x (12 n + 4) |
-      # Adam step sizes f32 x (n + 1)].  The plans read their PhaseShuffle draws
-      # straight from it (update k: 12 ints at 12 k, the generator update's 4
-      # behind them), so a graph replay needs ONE staged copy and no per-update
-      # copies into the plans
-      stage = torch.zeros(nc * 13 + 5, dtype=torch.int32, device=dev)
-      st = dict(
-          gws=self.generator.net.workspace(B),
-          dws=dws,
-          stage_dev=stage,
-          critic=dws.plan(3 * B, B, 2 * B,
-                          shifts=stage[:12].view(4, 3) if nc > 0 else None),
-          gen=dws.plan(B, B, 0, want_norm=False,
-                       shifts=stage[12 * nc:12 * nc + 4].view(4, 1)),
-          norm=torch.zeros(B, dtype=torch.float32, device=dev),
-          coef_gp=torch.zeros(B, dtype=torch.float32, device=dev),
-          gp=torch.zeros(max(self.n_critic, 1), dtype=torch.float32, device=dev),
-          loss=torch.zeros(max(self.n_critic, 1), 2, dtype=torch.float32,
-                           device=dev),
-          gen_loss=torch.zeros(1, dtype=torch.float32, device=dev),
-          # the step's outputs [gen_loss, dis_loss, gp, metrics x 4], written
-          # by the last launches of train(); train() hands out a COPY
-          out=torch.zeros(7, dtype=torch.float32, device=dev))
-      st['critic'].coef.copy_(torch.tensor([-1.0 / B, 1.0 / B, 1.0]))
-      st['critic'].bias_coef.copy_(torch.tensor([-1.0 / B, 1.0 / B, 0.0]))
-      st['critic'].build_jvp(2, st['coef_gp'])
-      st['gen'].coef.copy_(torch.tensor([-1.0 / B]))
-      st['gen'].bias_coef.zero_()
-      if self.dis_optimizer.loss_scale is not None:
-        # mixed_float16: the seeds of the backward chains carry the loss scale
-        # (get_scaled_loss, wgan_gp.py:32,76).  The x^ segment's chain is the
-        # INNER gradient of the penalty (its own tape, wgan_gp.py:45-48): its
-        # seed stays 1, the scale enters its second backward through v
-        st['coef_base'] = dict(
-            critic=(st['critic'].coef.clone(), st['critic'].bias_coef.clone(),
-                    torch.tensor([1.0, 1.0, 0.0], device=dev)),
-            gen=(st['gen'].coef.clone(), st['gen'].bias_coef.clone(),
-                 torch.tensor([1.0], device=dev)))
-      # (fp16: the loss scale multiplies coef on the device afterwards -- three
-      # launches as before)
-      if _FUSE_GP and self.dis_optimizer.loss_scale is None:
-        st['critic'].defer_norm()
-      self._state[B] = st
+  def _build_state(self, B):
+    dev = self.device
+    dws = self.discriminator.net.workspace(3 * B)
+    nc = self.n_critic
+    # host-drawn inputs of a step on the device: [shifts int32 x (12 n + 4) |
+    # Adam step sizes f32 x (n + 1)].  The plans read their PhaseShuffle draws
+    # straight from it (update k: 12 ints at 12 k, the generator update's 4
+    # behind them), so a graph replay needs ONE staged copy and no per-update
+    # copies into the plans
+    stage = torch.zeros(nc * 13 + 5, dtype=torch.int32, device=dev)
+    st = dict(
+        gws=self.generator.net.workspace(B),
+        dws=dws,
+        stage_dev=stage,
+        critic=dws.plan(3 * B, B, 2 * B,
+                        shifts=stage[:12].view(4, 3) if nc > 0 else None),
+        gen=dws.plan(B, B, 0, want_norm=False,
+                     shifts=stage[12 * nc:12 * nc + 4].view(4, 1)),
+        norm=torch.zeros(B, dtype=torch.float32, device=dev),
+        coef_gp=torch.zeros(B, dtype=torch.float32, device=dev),
+        gp=torch.zeros(max(self.n_critic, 1), dtype=torch.float32, device=dev),
+        loss=torch.zeros(max(self.n_critic, 1), 2, dtype=torch.float32,
+                         device=dev),
+        gen_loss=torch.zeros(1, dtype=torch.float32, device=dev),
+        # the step's outputs [gen_loss, dis_loss, gp, metrics x 4], written
+        # by the last launches of train(); train() hands out a COPY
+        out=torch.zeros(7, dtype=torch.float32, device=dev))
+    st['critic'].coef.copy_(torch.tensor([-1.0 / B, 1.0 / B, 1.0]))
+    st['critic'].bias_coef.copy_(torch.tensor([-1.0 / B, 1.0 / B, 0.0]))
+    st['critic'].build_jvp(2, st['coef_gp'])
+    st['gen'].coef.copy_(torch.tensor([-1.0 / B]))
+    st['gen'].bias_coef.zero_()
+    if self.dis_optimizer.loss_scale is not None:
+      # mixed_float16: the seeds of the backward chains carry the loss scale
+      # (get_scaled_loss, wgan_gp.py:32,76).  The x^ segment's chain is the
+      # INNER gradient of the penalty (its own tape, wgan_gp.py:45-48): its
+      # seed stays 1, the scale enters its second backward through v
+      st['coef_base'] = dict(
+          critic=(st['critic'].coef.clone(), st['critic'].bias_coef.clone(),
+                  torch.tensor([1.0, 1.0, 0.0], device=dev)),
+          gen=(st['gen'].coef.clone(), st['gen'].bias_coef.clone(),
+               torch.tensor([1.0], device=dev)))
+    # (fp16: the loss scale multiplies coef on the device afterwards -- three
+    # launches as before)
+    if _FUSE_GP and self.dis_optimizer.loss_scale is None:
+      st['critic'].defer_norm()
     return st
 
   def _critic_plan(self, st, k):
@@ -154,21 +142,6 @@ class WGAN_GP(GAN):
       gws = self.generator.net.workspace(n * B, forward_only=True)
     lay = self.discriminator.net.layers[0]
     return gws.can_interp(n) and lay.cinp == self.generator.net.Cp
-
-  def batch_buffer(self, B):
-    """The device buffer train() reads a batch of B samples from when it replays
-    its hipGraph: (B,) + signal_shape, f32.  A data loader that gathers every
-    batch INTO it (torch.index_select(..., out=buffer)) saves the copy train()
-    otherwise makes in front of each replay; passing any other tensor stays
-    valid.  One buffer per batch size, alive as long as this object."""
-    st = self._get_state(B)
-    g = st.get('graph')
-    if g is not None:
-      return g['real']
-    if st.get('batch_buf') is None:
-      st['batch_buf'] = torch.empty((B,) + self.signal_shape,
-                                    dtype=torch.float32, device=self.device)
-    return st['batch_buf']
 
   def _scale_seeds(self, st, which, optimizer, plan=None):
     """coef = base * (S where the segment's loss term is scaled, else 1), on the
@@ -281,6 +254,13 @@ class WGAN_GP(GAN):
     fake = ws.forward(z, keep=False)
     return [fake[i * B:(i + 1) * B] for i in range(n)]
 
+  def _injected_critic_draws(self, r):
+    """(alpha on the device, host int32 (4, 3) shifts [real | fake | x^]) of the
+    injected draws of one critic update."""
+    return self._to_device(r['alpha']), torch.stack([
+        torch.as_tensor(r[k], dtype=torch.int32)
+        for k in ('shifts_real', 'shifts_fake', 'shifts_inter')], dim=1)
+
   def _critic_compute(self, real, r=None, slot=0, real_cached=False,
                       fake=None, alpha=None, x0_index=None):
     """wgan_gp.py:64-80 up to (not including) the optimizer update: leaves the
@@ -300,12 +280,7 @@ class WGAN_GP(GAN):
       alpha = self._streams.alpha(B) if alpha is None else alpha
       shifts = r['shifts_dev']
     else:
-      alpha = self._to_device(r['alpha'])
-      shifts = torch.stack([
-          torch.as_tensor(r['shifts_real'], dtype=torch.int32),
-          torch.as_tensor(r['shifts_fake'], dtype=torch.int32),
-          torch.as_tensor(r['shifts_inter'], dtype=torch.int32)
-      ], dim=1)
+      alpha, shifts = self._injected_critic_draws(r)
     plan = self._critic_plan(st, x0_index or 0)
     n = lay.lin * lay.cinp
     if plan.jvp_folds:
@@ -393,21 +368,33 @@ class WGAN_GP(GAN):
     metrics = self._gen_apply(real, lr_t_dev)
     return st['gen_loss'][0], metrics
 
-  def _segments(self, real, rand=None, lr_dev=None, out=None):
-    """One train() (wgan_gp.py:82-95) as launch segments cut around the
-    gradient all-reduces.  Returns [(callable, flat_grad_or_None, wait)]:
-    after a segment with a gradient buffer its all-reduce is STARTED; a segment
-    with wait=True needs the pending all-reduce finished first.  Work that
-    does not read the reduced gradients -- the next update's G(z), the signal
-    metrics -- sits in wait=False segments and overlaps the collective:
+  def _segments(self, real, rand=None, staged=False):
+    """One train() (wgan_gp.py:82-95: n_critic critic updates on the SAME
+    batch, then one generator update) as launch segments cut around the
+    gradient all-reduces.  `rand` optionally injects the random draws (same
+    structure as oracle.draw_randomness) for parity tests.  Returns
+    [(callable, flat_grad_or_None, wait)]: after a segment with a gradient
+    buffer its all-reduce is STARTED; a segment with wait=True needs the
+    pending all-reduce finished first.  Work that does not read the reduced
+    gradients -- the next update's G(z), the signal metrics -- sits in
+    wait=False segments and overlaps the collective:
 
       [G(z0) D-step0] ar | [G(z1)] wait [adam0 D-step1] ar | ... |
       [G(zg)] wait [adam D fwd/bwd, G bwd] ar | [metrics] wait [adam_G, outputs]
 
-    The last callable stores the step's outputs in out['value']."""
+    The last callable stores the step's outputs in st['out'].  staged (graph
+    replay): update k reads its shifts from the state's stage buffer (where the
+    plans' own shifts are views of it) and its Adam step size behind them."""
     n = self.n_critic
     st = self._get_state(real.shape[0])
-    out = {} if out is None else out
+    lr_dev = None
+    if staged:
+      sd = st['stage_dev']
+      rand = dict(
+          critic=[dict(shifts_dev=sd[12 * i:12 * i + 12].view(4, 3))
+                  for i in range(n)],
+          gen=dict(shifts_dev=sd[12 * n:12 * n + 4].view(4, 1)))
+      lr_dev = sd[12 * n + 4:].view(torch.float32)
     lr = (lambda i: None) if lr_dev is None else (lambda i: lr_dev[i:])
     rc = (lambda i: None) if rand is None else (lambda i: rand['critic'][i])
     rg = None if rand is None else rand['gen']
@@ -465,12 +452,10 @@ class WGAN_GP(GAN):
 
     def last_seg():
       metrics = self._gen_apply(real, lr(n), metrics=box.pop('metrics'))
-      o = st['out']
       # (metrics are views of one 4-float buffer: GAN.metrics)
       _lib.call('cg_step_outputs', nets._p(st['gen_loss']), nets._p(st['loss']),
                 nets._p(st['gp']), nets._p(metrics[_METRIC_KEYS[0]]), n,
-                nets._p(o), nets._stream())
-      out['value'] = o
+                nets._p(st['out']), nets._stream())
 
     segs = []
     def first_seg():
@@ -522,131 +507,15 @@ class WGAN_GP(GAN):
         for fn in fns:
           fn()
       segs = [(run_all, None, False)]
-    return segs, out
+    return segs
 
-  def _run_segments(self, segs, launch):
-    """Drive (callable, grad, wait) segments; `launch` runs one callable."""
-    pending = None
-    for fn, grad, wait in segs:
-      if wait and pending is not None:
-        pending.wait()
-        pending = None
-      launch(fn)
-      if grad is not None:
-        pending = self._sync.all_reduce_async(grad)
-        if not _DP_OVERLAP and pending is not None:
-          pending.wait()
-          pending = None
-    if pending is not None:
-      pending.wait()
+  @property
+  def _adam_steps(self):
+    return self.n_critic, 1
 
-  def _outputs(self, o):
-    """(gen_loss, dis_loss, gradient_penalty, metrics) as views of a fresh
-    COPY of the step's output buffer: the buffer itself is rewritten by the next
-    train() -- in place, when the step replays as a graph -- so callers may keep
-    the returned tensors across steps without a host sync (main.py averages
-    them at the end of the epoch).  Data parallel: averaged over the ranks, one
-    7-float all-reduce per step."""
-    o = self._sync.mean_scalars(o.clone())
-    return (o[0], o[1], o[2],
-            {k: o[3 + i] for i, k in enumerate(_METRIC_KEYS)})
-
-  def _train_body(self, real, rand=None):
-    segs, out = self._segments(real, rand)
-    self._run_segments(segs, lambda fn: fn())
-    return self._outputs(out['value'])
-
-  def _capture(self, real, st):
-    """Capture one train() as hipGraphs, one per segment (RCCL all-reduces stay
-    eager between replays, overlapped with the wait=False segments).
-    Host-drawn inputs of a replay (phase shifts, Adam step sizes) are copied
-    to fixed device buffers EAGERLY ahead of the replay, from a ring of pinned
-    staging slots (_stage_host_inputs); z / alpha come from the
-    graph-registered device generator."""
-    dev = self.device
+  def _fill_stage(self, host):
+    """[shifts int32 x (12 n + 4) | lr_t f32 x (n + 1)] of the coming step."""
     n = self.n_critic
-    g = dict(
-        # (the caller's own buffer when it gathers its batches into
-        # batch_buffer(): no copy in front of a replay then)
-        real=(st['batch_buf'] if st.get('batch_buf') is not None and
-              st['batch_buf'].shape == real.shape else torch.empty_like(real)),
-        # one staging word array per slot: [shifts int32 x (12 n + 4) |
-        # lr_t f32 x (n + 1)] (the f32 part travels as its bit pattern)
-        stage_host=[torch.zeros(n * 13 + 5, dtype=torch.int32).pin_memory()
-                    for _ in range(_STAGING_SLOTS)],
-        stage_event=[None] * _STAGING_SLOTS,
-        stage_next=0,
-        stage_dev=st['stage_dev'])
-    g['shifts_dev'] = g['stage_dev'][:n * 12 + 4]
-    g['lr_dev'] = g['stage_dev'][n * 12 + 4:].view(torch.float32)
-    if g['real'].data_ptr() != real.data_ptr():
-      g['real'].copy_(real)
-    rand = dict(
-        critic=[dict(shifts_dev=g['shifts_dev'][12 * i:12 * i + 12].view(4, 3))
-                for i in range(n)],
-        gen=dict(shifts_dev=g['shifts_dev'][12 * n:].view(4, 1)))
-    segs, out = self._segments(g['real'], rand, g['lr_dev'])
-    it_d, it_g = (self.dis_optimizer.host_steps, self.gen_optimizer.host_steps)
-    graphs = []
-    pool = None
-    torch.cuda.synchronize()
-    try:
-      for k, (fn, grad, wait) in enumerate(segs):
-        graph = torch.cuda.CUDAGraph()
-        graph.register_generator_state(self._streams.local)
-        # thread_local: the RCCL watchdog thread may touch the HIP runtime
-        # while this thread captures
-        with torch.cuda.graph(graph, pool=pool,
-                              capture_error_mode='thread_local'):
-          fn()
-        pool = graph.pool()
-        graphs.append((graph.replay, grad, wait))
-    finally:
-      # capture only records: undo the host-side step counters it advanced
-      self.dis_optimizer.host_steps, self.gen_optimizer.host_steps = it_d, it_g
-    g['graphs'] = graphs
-    g['out'] = out['value']
-    return g
-
-  def _train_graphed(self, real, st):
-    g = st.get('graph')
-    if g is None:
-      try:
-        g = st['graph'] = self._capture(real, st)
-      except Exception as e:  # noqa: BLE001 -- any capture failure
-        # the step itself is unaffected: keep training with eager launches
-        import warnings
-        warnings.warn('calciumgan_amd: hipGraph capture of train() failed '
-                      '({}: {}); continuing with eager launches'.format(
-                          type(e).__name__, e))
-        self._use_graph = False
-        torch.cuda.synchronize()
-        return self._train_body(real)
-    n = self.n_critic
-    # the graphs read their batch from a fixed buffer.  A caller that gathers
-    # its batches into batch_buffer() wrote it already; any other tensor is
-    # copied (107 MB at cfg2, ~35 us; 4.3 GB at cfg5, 2 ms)
-    if g['real'].data_ptr() != real.data_ptr():
-      g['real'].copy_(real)
-    self._stage_host_inputs(g)
-    self._run_segments(g['graphs'], lambda replay: replay())
-    self.dis_optimizer.host_steps += n
-    self.gen_optimizer.host_steps += 1
-    return self._outputs(g['out'])
-
-  def _stage_host_inputs(self, g):
-    """Phase shifts and Adam step sizes of the coming replay -> device.  The
-    host writes them into the next pinned slot of a ring and enqueues the copy
-    on the launch stream (ordered after the previous replay, which still reads
-    the device buffer); an event per slot keeps the host from rewriting a slot
-    whose copy has not executed yet -- train() never syncs, so the host may
-    run several steps ahead of the GPU."""
-    n = self.n_critic
-    k = g['stage_next']
-    g['stage_next'] = (k + 1) % _STAGING_SLOTS
-    if g['stage_event'][k] is not None:
-      g['stage_event'][k].synchronize()
-    host = g['stage_host'][k]
     for i in range(n):
       host[12 * i:12 * i + 12] = self._streams.shifts(3).reshape(-1)
     host[12 * n:12 * n + 4] = self._streams.shifts(1).reshape(-1)
@@ -654,33 +523,6 @@ class WGAN_GP(GAN):
     for i in range(n):
       lr[i] = self.dis_optimizer.lr_t(self.dis_optimizer.host_steps + i + 1)
     lr[n] = self.gen_optimizer.lr_t(self.gen_optimizer.host_steps + 1)
-    g['stage_dev'].copy_(host, non_blocking=True)
-    ev = g['stage_event'][k] = torch.cuda.Event()
-    ev.record()
-
-  def train(self, inputs, rand=None):
-    """wgan_gp.py:82-95: n_critic critic updates on the SAME batch, then one
-    generator update.  Returns (gen_loss, dis_loss, gradient_penalty, metrics)
-    as 0-d device tensors (no host sync inside; each call returns views of its
-    own small buffer, so they stay valid across later steps; under data
-    parallelism they are the means over all ranks).  `rand` optionally injects
-    the random draws (same structure as oracle.draw_randomness) for parity
-    tests.  After two eager calls per batch size the step replays as
-    hipGraphs."""
-    _lib.use(self.precision)
-    real = self._to_device(inputs)
-    st = self._get_state(real.shape[0])
-    if rand is None and self._use_graph:
-      st['calls'] = st.get('calls', 0) + 1
-      if st['calls'] > _GRAPH_WARMUP_CALLS:
-        return self._train_graphed(real, st)
-    # an eager step between replays (injected randomness, main.py's --profile
-    # window).  The captured graphs stay valid: they hold pointers to buffers
-    # that live as long as this object, and nothing in them depends on what ran
-    # in between.  (Round 2 dropped them here after "stale graph" penalties of
-    # 1e25; the cause was a hipMemsetAsync NODE inside the captured step --
-    # cg_rownorm's -- not stale memory: DESIGN.md section 8.)
-    return self._train_body(real, rand)
 
   def validate(self, inputs, rand=None):
     """gan.py:87-90 / :58-70 with the WGAN-GP loss (inner-gradient penalty, no
@@ -695,17 +537,11 @@ class WGAN_GP(GAN):
       shifts = self._streams.shifts(3)
     else:
       z = self._to_device(rand['z'])
-      alpha = self._to_device(rand['alpha'])
-      shifts = torch.stack([
-          torch.as_tensor(rand['shifts_real'], dtype=torch.int32),
-          torch.as_tensor(rand['shifts_fake'], dtype=torch.int32),
-          torch.as_tensor(rand['shifts_inter'], dtype=torch.int32)
-      ], dim=1)
+      alpha, shifts = self._injected_critic_draws(rand)
     fake = self._critic_forward(st, real, z, alpha, shifts, 0, training=False)
     C = self.generator.net.C
     metrics = self.metrics(real, fake, fake_pitch=self.generator.net.Cf)
     loss = st['loss'][0]
-    gen_loss, dis_loss, gp, metrics = self._outputs(
+    return (fake[:, :, :C].clone(),) + self._outputs(
         torch.stack([loss[1], loss[0], st['gp'][0]] +
                     [metrics[k] for k in _METRIC_KEYS]))
-    return fake[:, :, :C].clone(), gen_loss, dis_loss, gp, metrics

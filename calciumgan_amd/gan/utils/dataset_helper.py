@@ -56,7 +56,7 @@ class ArrayDataset(object):
   """Iterable of (signal, spike) batches; reshuffled every epoch when asked
   (tf.data shuffle(buffer) + batch, dataset_helper.py:170-174).
 
-  With `gather_into` bound (main.py: WGAN_GP.batch_buffer) every batch of that
+  With `gather_into` bound (main.py: GAN.batch_buffer) every batch of that
   size is gathered into ONE device buffer, so the `signal` tensors this iterator
   yields ALIAS each other: a consumer that keeps a reference across steps sees
   the later batch (the training loop reads it within the step; clone to keep)."""
@@ -67,7 +67,7 @@ class ArrayDataset(object):
     self._rng = np.random.RandomState(seed)
     self._dev_signals = None
     # callable(batch_len) -> device tensor to gather the batch into, or None
-    # (main.py binds the training set to WGAN_GP.batch_buffer)
+    # (main.py binds the training set to GAN.batch_buffer)
     self.gather_into = None
 
   def to_device(self, device):

@@ -59,7 +59,7 @@ def det():
     hw.update(net.params.v.cpu().numpy().tobytes())
   print(json.dumps({'weights': hw.hexdigest(), 'outputs': h.hexdigest(),
                     'last': [float(v) for v in vals.cpu()],
-                    'graph': gan._bce_get_state(B).get('graph') is not None}))
+                    'graph': gan._get_state(B).get('graph') is not None}))
 
 
 def dp_inputs(hp):
@@ -85,7 +85,7 @@ def dp():
   gan._sync.all_reduce(gen.net.params.grad)
   d_grad = (dis.net.params.grad * gan._sync.grad_scale).cpu().numpy()
   g_grad = (gen.net.params.grad * gan._sync.grad_scale).cpu().numpy()
-  st = gan._bce_get_state(mine.shape[0])
+  st = gan._get_state(mine.shape[0])
   loss = st['loss'].double().cpu()
   dist.all_reduce(loss)
   # replicas after every step of eager data-parallel training

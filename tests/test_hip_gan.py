@@ -196,7 +196,7 @@ def test_step_matches_bf16_oracle(name):
   emu = BO.step_grads(hp, gw, dw, torch.tensor(real), r, 'bf16')
   gan._bce_compute(gan._to_device(real), r)
   torch.cuda.synchronize()
-  st = gan._bce_get_state(B)
+  st = gan._get_state(B)
   loss = st['loss'].cpu().numpy()
   np.testing.assert_allclose(loss, [float(emu['gen_loss']),
                                     float(emu['dis_loss'])], rtol=1e-2)
@@ -269,9 +269,9 @@ def test_graph_replay_equals_eager(fixed_tiles):
       outs.append(torch.stack([gl, dl] + [m[k] for k in sorted(m)]))
     torch.cuda.synchronize()
     if graphed:
-      assert gan._bce_get_state(B).get('graph') is not None
+      assert gan._get_state(B).get('graph') is not None
     else:
-      assert gan._bce_get_state(B).get('graph') is None
+      assert gan._get_state(B).get('graph') is None
     runs.append((torch.stack(outs).cpu().numpy(),
                  gen.get_weights() + dis.get_weights()))
   (oa, wa), (ob, wb) = runs
@@ -380,7 +380,7 @@ def test_mixed_precision_tracks_f16_oracle_with_loss_scaling():
   for _ in range(5):
     out = gan.train(real)
   torch.cuda.synchronize()
-  assert gan._bce_get_state(B).get('graph') is not None
+  assert gan._get_state(B).get('graph') is not None
   assert np.isfinite([float(out[0]), float(out[1])]).all()
   assert gan.dis_optimizer.iterations == 8 and gan.gen_optimizer.iterations == 8
   assert float(gan.dis_optimizer.loss_scale_state[1]) == 8.0
@@ -442,7 +442,7 @@ def test_two_rank_gan_equals_one_rank_on_global_batch(tmp_path):
   assert rel(recs[0]['d_grad'], dis.net.params.grad.cpu().numpy()) < 2e-3
   assert rel(recs[0]['g_grad'], gen.net.params.grad.cpu().numpy()) < 2e-3
   np.testing.assert_allclose(recs[0]['loss'],
-                             gan._bce_get_state(W.DP['B'])['loss'].cpu().numpy(),
+                             gan._get_state(W.DP['B'])['loss'].cpu().numpy(),
                              rtol=2e-3)
 
 

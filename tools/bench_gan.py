@@ -68,7 +68,7 @@ def main():
     out = gan.train(next_batch(args.warmup + i))
   torch.cuda.synchronize()
   dt = time.perf_counter() - t0
-  st = gan._bce_get_state(B)
+  st = gan._get_state(B)
   print(json.dumps({
       'metric': 'training samples/sec, --algorithm gan (seq_len={})'.format(
           args.seq_len),

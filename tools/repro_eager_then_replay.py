@@ -44,8 +44,9 @@ o = gan.train(batch(0))
 torch.cuda.synchronize()
 print('out', float(o[0]), float(o[1]), float(o[2]))
 print('gp per critic step', st['gp'].cpu().numpy(), 'loss', st['loss'].cpu().numpy().tolist())
-g = st['graph']
-print('lr_dev', g['lr_dev'].cpu().numpy(), 'shifts', g['shifts_dev'].cpu().numpy())
+ns = 12 * gan.n_critic + 4  # staged words: shifts, then the Adam step sizes
+stage = st['stage_dev']
+print('lr_dev', stage[ns:].view(torch.float32).cpu().numpy(), 'shifts', stage[:ns].cpu().numpy())
 print('host steps', gan.dis_optimizer.host_steps, gan.gen_optimizer.host_steps)
 chk('after replay')
 badrun = not np.isfinite([float(o[1])]).all() or abs(float(o[1])) > 1e3

@@ -60,7 +60,7 @@ def persistent_tensors():
   out['gen_coef'] = st['gen'].coef
   g = st.get('graph')
   if g is not None:
-    out['g_real'], out['stage_dev'] = g['real'], g['stage_dev']
+    out['g_real'], out['stage_dev'] = g['real'], st['stage_dev']
   return out
 
 
@@ -147,7 +147,7 @@ pl = st['critic']
 info = dict(
     out=vals, gp=gp.tolist(),
     shifts=pl.shifts.cpu().numpy().reshape(-1).tolist(),
-    stage=st['graph']['stage_dev'].cpu().numpy().tolist()[:16],
+    stage=st['stage_dev'].cpu().numpy().tolist()[:16],
     d_out_absmax=float(st['dws'].d_out.abs().max()),
     gin_absmax=float(pl.gin.float().abs().max()),
     act_absmax=[float(t.float().abs().max()) for t in st['dws'].act],
