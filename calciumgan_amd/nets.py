@@ -6,8 +6,10 @@ parallel.py) the RCCL process group.  Every arithmetic step is a call into the
 gfx950 kernel library through the C ABI (include/calciumgan_hip.h); launch
 descriptors are built once per batch size and replayed.
 """
+import atexit
 import ctypes
 import math
+import os
 
 import numpy as np
 import torch
@@ -16,7 +18,10 @@ from . import _lib
 from . import geometry as geo
 from ._lib import ConvDesc, PackDesc, WgradDesc
 
-BF16 = torch.bfloat16
+
+def _flag(name):
+  """An A/B switch of the environment: on unless CALCIUMGAN_<name>=0."""
+  return os.environ.get('CALCIUMGAN_' + name, '1') != '0'
 
 
 def act_dtype():
@@ -113,9 +118,7 @@ class FlatParams(object):
 # zeroing.  CALCIUMGAN_DETERMINISTIC=0: the atomics (+= onto zeroed buffers).
 # (CALCIUMGAN_WGRAD_PARTIALS=0 brings cg_wgrad's atomics back: they add onto
 # zeroed gradients, so it switches the whole mode off)
-DETERMINISTIC = (
-    __import__('os').environ.get('CALCIUMGAN_DETERMINISTIC', '1') != '0' and
-    __import__('os').environ.get('CALCIUMGAN_WGRAD_PARTIALS', '1') != '0')
+DETERMINISTIC = _flag('DETERMINISTIC') and _flag('WGRAD_PARTIALS')
 _REDUCE_WS = {}
 
 
@@ -136,7 +139,7 @@ def reduce_ws(device):
 
 # CALCIUMGAN_DEFER_FINISH=0: every ordered reduction of the generator backward is
 # finished by its own launch instead of one launch for all of them (A/B)
-_DEFER_FINISH = __import__('os').environ.get('CALCIUMGAN_DEFER_FINISH', '1') != '0'
+_DEFER_FINISH = _flag('DEFER_FINISH')
 _REDUCE_WS_REGIONS = {}
 
 
@@ -155,7 +158,7 @@ def reduce_ws_regions(device, n):
 
 
 # CALCIUMGAN_NARROW_LAST=0: padded channel chunks are walked in full
-_NARROW_LAST = __import__('os').environ.get('CALCIUMGAN_NARROW_LAST', '1') != '0'
+_NARROW_LAST = _flag('NARROW_LAST')
 
 
 def narrow_last_rule(parity_major, CK, Cx, taps, C_real):
@@ -347,30 +350,87 @@ def _conv_desc(x, w, y, nB, Lx, Cx, taps, stride, off, Lu, N, Ly, Cy, CK,
   return d
 
 
+class Stride2Layer(object):
+  """The three MFMA launches of one stride-2 layer.  A weight tensor of logical
+  shape (k, A, B), row-major, and the long side's length L define
+
+    down   (nB, L, Ap) -> (nB, L / 2, Bp)   the stride-2 'same' convolution
+    up     (nB, L / 2, Bp) -> (nB, L, Ap)   its adjoint: two stride-1 phases
+    wgrad  dW (k, A, B) from a long-side x and a short-side g
+
+  A critic layer is (k, cin, cout, lin): forward down, input gradient up.  A
+  generator layer, W (k, 1, cout, cin), is (k, cout, cin, lout): forward up,
+  input gradient down.  The geometry below needs no tensor; a descriptor takes
+  CK, the packing flags and the phase stride from the operand it is given."""
+
+  def __init__(self, k, A, B, L):
+    self.k, self.A, self.B, self.L = k, A, B, L
+    self.Ap, self.Bp = geo.pitch(A), geo.pitch(B)
+    self.pl = geo.same_padding_left(k, 2)
+    self.phases = _transpose_phases(k, self.pl)
+    self.offs = [o for _, o in self.phases]
+    self.ck_down = _ck_for(self.Ap, 2, k, L // 2)
+    self.ck_up = _ck_for(self.Bp, 1, k // 2, L // 2)
+
+  def narrow_last(self, parity_major=True):
+    """Whether the down operand's last channel chunk is packed narrow."""
+    return narrow_last_rule(parity_major, self.ck_down, self.Ap, self.k, self.A)
+
+  def pack_down(self, W, parity_major=True):
+    return PackedOperand(W, [(0, 1, self.A * self.B, self.B, 1)], self.A,
+                         self.B, self.Ap, self.ck_down, self.k,
+                         parity_major=parity_major)
+
+  def pack_up(self, W):
+    return PackedOperand(
+        W, [(t0, -2, self.A * self.B, 1, self.B) for t0, _ in self.phases],
+        self.B, self.A, self.Bp, self.ck_up, self.k // 2)
+
+  def down(self, x, op, y, nB, **kw):
+    """kw: bias, shifts, seg_size, epilogue, mask_src, out_f32, row_scale,
+    alpha (_conv_desc)."""
+    return _conv_desc(x, op.buf, y, nB, self.L, self.Ap, self.k, 2, -self.pl,
+                      self.L // 2, self.B, self.L // 2, self.Bp, op.CK,
+                      w_parity_major=op.parity_major,
+                      w_narrow_last=op.narrow_last, **kw)
+
+  def up(self, x, op, y, nB, **kw):
+    """kw: as down, and rowsumsq, ln, out_shifts."""
+    return _conv_desc(x, op.buf, y, nB, self.L // 2, self.Bp, self.k // 2, 1,
+                      self.offs[0], self.L // 2, self.A, self.L, self.Ap, op.CK,
+                      y_stride=2, y_off=0, nphase=2, w_phase_stride=op.elems,
+                      off_phase_step=self.offs[1] - self.offs[0],
+                      yoff_phase_step=1, **kw)
+
+  def wgrad(self, x, g, dw, nB, **kw):
+    """kw: shifts, seg_size, dbias, bias_rows, slot (_wgrad_desc)."""
+    return _wgrad_desc(x, g, dw, nB, self.L, self.Ap, self.L // 2, self.Bp,
+                       self.k, 2, -self.pl, self.A, self.B, **kw)
+
+
 # CALCIUMGAN_FOLD_SCALE=0: the penalty's v = coef_b * g as its own pass over g
 # (cg_scale_rows into X0) instead of a per-sample scale in the tangent chain's
 # first launch + a pass over the x^ segment of delta_1
-_FOLD_SCALE = __import__('os').environ.get('CALCIUMGAN_FOLD_SCALE', '1') != '0'
+_FOLD_SCALE = _flag('FOLD_SCALE')
 # Critic layer 1 on x^ = a real + (1 - a) fake taken from the layer's outputs on
 # real and fake (the convolution is linear: cg_lrelu_mix) instead of a third of the
 # layer's launch; x^ itself is then never formed.  0: convolve x^ like the other two
 # segments (rounds 1-4).
-_L1_LINEAR = __import__('os').environ.get('CALCIUMGAN_L1_LINEAR', '1') != '0'
+_L1_LINEAR = _flag('L1_LINEAR')
 # ... for segments of at least this many layer-1 output rows (B * L / 2): below,
 # a third of the layer's launch is shorter than the extra launch (cfg2: 131 072)
-_L1_LINEAR_MIN_ROWS = int(__import__('os').environ.get(
-    'CALCIUMGAN_L1_LINEAR_MIN_ROWS', '16384'))
+_L1_LINEAR_MIN_ROWS = int(
+    os.environ.get('CALCIUMGAN_L1_LINEAR_MIN_ROWS', '16384'))
 # Split-K candidates of the tile tuner (CALCIUMGAN_SPLIT_K=0: never): only for
 # launches whose output is at most this many 64x64 tiles
-_SPLIT_K = __import__('os').environ.get('CALCIUMGAN_SPLIT_K', '1') != '0'
+_SPLIT_K = _flag('SPLIT_K')
 _SPLIT_K_MAX_TILES = 2048
 _SPLIT_WS = {}
 # CALCIUMGAN_FUSE_UNSHUFFLE=0: cg_unshuffle_mask as its own pass after every
 # input-gradient launch of the critic
-_FUSE_UNSHUFFLE = __import__('os').environ.get('CALCIUMGAN_FUSE_UNSHUFFLE',
-                                                '1') != '0'
+_FUSE_UNSHUFFLE = _flag('FUSE_UNSHUFFLE')
 # CALCIUMGAN_FUSE_LN=0 keeps LayerNorm a separate pass (A/B, debugging)
-_FUSE_LN = __import__('os').environ.get('CALCIUMGAN_FUSE_LN', '1') != '0'
+_FUSE_LN = _flag('FUSE_LN')
 
 
 def _ln_fusable(lay, CK, taps):
@@ -392,16 +452,16 @@ def _ln_fusable(lay, CK, taps):
 # 12.74 / 12.72 tuned) and makes every run -- bench.py, main.py, the tests --
 # replay bit for bit across processes.
 _TILE_CACHE = {}
-_AUTOTUNE = __import__('os').environ.get('CALCIUMGAN_AUTOTUNE', '0') == '1'
+_AUTOTUNE = os.environ.get('CALCIUMGAN_AUTOTUNE', '0') == '1'
 # CALCIUMGAN_TILE_CACHE=<file.json>: choices are loaded from / saved to this
 # file, so later processes (profiler passes, the other ranks' restarts) launch
 # exactly the tuned configuration without re-timing candidates.
-_TILE_CACHE_FILE = __import__('os').environ.get('CALCIUMGAN_TILE_CACHE')
+_TILE_CACHE_FILE = os.environ.get('CALCIUMGAN_TILE_CACHE')
 # CALCIUMGAN_TUNE_LOG=<file.jsonl>: every tuned geometry with all candidates'
 # times (per-geometry tables under profiles/ come from this)
-_TUNE_LOG = __import__('os').environ.get('CALCIUMGAN_TUNE_LOG')
+_TUNE_LOG = os.environ.get('CALCIUMGAN_TUNE_LOG')
 # CALCIUMGAN_SWP_TILES=0: the software-pipelined tiles are not offered to the tuner
-_SWP_TILES = __import__('os').environ.get('CALCIUMGAN_SWP_TILES', '1') != '0'
+_SWP_TILES = _flag('SWP_TILES')
 
 
 def load_tile_cache(path):
@@ -416,7 +476,6 @@ def load_tile_cache(path):
 
 
 def _load_tile_cache():
-  import os
   if _TILE_CACHE_FILE and os.path.exists(_TILE_CACHE_FILE):
     load_tile_cache(_TILE_CACHE_FILE)
 
@@ -433,7 +492,7 @@ def _save_tile_cache():
 
 
 _load_tile_cache()
-__import__('atexit').register(_save_tile_cache)
+atexit.register(_save_tile_cache)
 
 
 def _autotune_tile(d):
@@ -472,38 +531,31 @@ def _autotune_tile(d):
   if best is None:
     lib = _lib.load()
     st = _stream()
-    cands = []
-    for small, (tm, tn, mf) in _lib.TILES.items():
-      ok = (d.Lu % tm == 0) if d.Lu >= tm else (tm % d.Lu == 0)
+
+    def fits(tm, tn):
+      """A tm x tn tile against the sample length, the fused penalty norm
+      (whole samples per tile) and the output width (LayerNorm: one 128-column
+      tile holds the row)."""
+      if not ((d.Lu % tm == 0) if d.Lu >= tm else (tm % d.Lu == 0)):
+        return False
       if d.rowsumsq and d.Lu < tm:
-        ok = False
-      if mf == 32 and d.CK % 32:
-        ok = False
+        return False
       if d.epilogue == _lib.EPI_LN_LRELU:
-        if tn != 128:
-          ok = False
-      elif tn > 64 and d.N <= 64:
-        ok = False
-      if ok and geo.lds_bytes(d.CK, d.stride, d.taps, d.Lu, tm, tn,
-                              mf) <= geo.LDS_BYTES:
-        cands.append(small)
+        return tn == 128
+      return not (tn > 64 and d.N <= 64)
+
+    cands = [small for small, (tm, tn, mf) in _lib.TILES.items()
+             if fits(tm, tn) and not (mf == 32 and d.CK % 32) and
+             geo.lds_bytes(d.CK, d.stride, d.taps, d.Lu, tm, tn,
+                           mf) <= geo.LDS_BYTES]
     cands = [(small, ks, 0, 1) for small in cands for ks in (2, 4)]
     swp = []
     if (_SWP_TILES and d.CK == 32 and
         d.taps % d.stride == 0 and (d.taps // d.stride) % 2 == 0 and
         d.taps // d.stride >= 6 and (d.stride == 1 or d.w_parity_major)):
       # software-pipelined tiles (two waves per SIMD, swconv_swp.hip)
-      for small, (tm, tn) in _lib.SWP_TILES.items():
-        ok = (d.Lu % tm == 0) if d.Lu >= tm else (tm % d.Lu == 0)
-        if d.rowsumsq and d.Lu < tm:
-          ok = False
-        if d.epilogue == _lib.EPI_LN_LRELU:
-          if tn != 128:
-            ok = False
-        elif tn > 64 and d.N <= 64:
-          ok = False
-        if ok:
-          swp.append((small, 2, 0, 1))
+      swp = [(small, 2, 0, 1) for small, (tm, tn) in _lib.SWP_TILES.items()
+             if fits(tm, tn)]
     if d.stride == 2 and d.w_parity_major:
       # split-parity staging: half the LDS window, twice the staging phases
       cands += [(small, ks, 1, 1) for small, ks, _, _ in list(cands)
@@ -564,7 +616,7 @@ def _autotune_tile(d):
 
 # CALCIUMGAN_STATIC_TILES="a,b,..|c,d,.." (development): the static preference
 # order of the software-pipelined tiles, plain launches | fused-LayerNorm ones
-_STATIC_ORDER = __import__('os').environ.get('CALCIUMGAN_STATIC_TILES')
+_STATIC_ORDER = os.environ.get('CALCIUMGAN_STATIC_TILES')
 
 
 def _static_swp_choice(d):
@@ -620,11 +672,10 @@ def _apply_tile_choice(d, best):
 # f32 atomics (CALCIUMGAN_WGRAD_PARTIALS=0: atomics).  Workspaces are shared by
 # the descriptors of one slot (= position in a batched launch): launches are
 # stream-ordered, so a slot's buffer is free again when the next batch starts.
-_WGRAD_PARTIALS = __import__('os').environ.get('CALCIUMGAN_WGRAD_PARTIALS',
-                                                '1') != '0'
+_WGRAD_PARTIALS = _flag('WGRAD_PARTIALS')
 _PARTIALS_POOL = {}
 # CALCIUMGAN_WGRAD_XCD=0: plain block order instead of the XCD-grouped one
-_WGRAD_XCD = __import__('os').environ.get('CALCIUMGAN_WGRAD_XCD', '1') != '0'
+_WGRAD_XCD = _flag('WGRAD_XCD')
 
 
 def _wgrad_desc(x, g, dw, nB, Lx, Cx, Lu, Cg, taps, stride, off, Cx_real,
@@ -687,7 +738,7 @@ def _run_conv(d, st):
   _timed('cg_swconv', 'swconv', d, st)
 
 
-_BATCH_WGRAD = __import__('os').environ.get('CALCIUMGAN_WGRAD_BATCH', '1') != '0'
+_BATCH_WGRAD = _flag('WGRAD_BATCH')
 
 
 def _run_wgrads(descs, st):
@@ -727,8 +778,10 @@ class DiscriminatorNet(object):
     self.alpha = geo.activation_alpha(hp)  # x -> max(x, alpha x)
     self.device = device
     self.k = hp.kernel_size
-    self.pl = geo.same_padding_left(self.k, hp.strides)
     self.layers = geo.discriminator_layers(hp)
+    # forward = down, input gradient = up
+    self.convs = [Stride2Layer(self.k, lay.cin, lay.cout, lay.lin)
+                  for lay in self.layers]
     shapes = []
     for lay in self.layers:
       shapes += [(self.k, lay.cin, lay.cout), (lay.cout,)]
@@ -746,20 +799,9 @@ class DiscriminatorNet(object):
     init.append(np.zeros(1, np.float32))
     self.params.set_weights(init)
     # packed operands
-    self.w_fwd, self.w_dgrad = [], []
-    phases = _transpose_phases(self.k, self.pl)
-    self.dgrad_offs = [o for _, o in phases]
-    for i, lay in enumerate(self.layers):
-      W = self.params.views[2 * i]
-      ci, co = lay.cin, lay.cout
-      ck = _ck_for(lay.cinp, 2, self.k, lay.lout)
-      self.w_fwd.append(
-          PackedOperand(W, [(0, 1, ci * co, co, 1)], ci, co, lay.cinp, ck,
-                        self.k, parity_major=True))
-      ck = _ck_for(lay.coutp, 1, self.k // 2, lay.lin // 2)
-      self.w_dgrad.append(
-          PackedOperand(W, [(t0, -2, ci * co, 1, co) for t0, _ in phases], co,
-                        ci, lay.coutp, ck, self.k // 2))
+    Ws = self.params.views[0:2 * len(self.layers):2]
+    self.w_fwd = [c.pack_down(W) for c, W in zip(self.convs, Ws)]
+    self.w_dgrad = [c.pack_up(W) for c, W in zip(self.convs, Ws)]
     self._pack_plan = PackPlan(self.w_fwd + self.w_dgrad, device)
     self.repack()
     self._ws = {}
@@ -802,6 +844,7 @@ class _DisWorkspace(object):
     self.delta = [None] + [z(nB, l.lout, l.coutp) for l in net.layers]
     self.d_out = z(nB, dt=torch.float32)
     self._plans = {}
+    self._x0_alt = {}
 
   def x0(self, k):
     """Input buffer X0 of critic update k of a step: update 0 uses act[0]; the
@@ -810,10 +853,9 @@ class _DisWorkspace(object):
     place (WGAN_GP._critic_generate_all).  201 MB each at cfg2."""
     if k == 0:
       return self.act[0]
-    alt = self.__dict__.setdefault('_x0_alt', {})
-    if k not in alt:
-      alt[k] = torch.zeros_like(self.act[0])
-    return alt[k]
+    if k not in self._x0_alt:
+      self._x0_alt[k] = torch.zeros_like(self.act[0])
+    return self._x0_alt[k]
 
   def plan(self, nB, seg_size, input_grad_from, want_norm=True, x0_index=0,
            shifts=None):
@@ -846,7 +888,6 @@ class _DisPlan(object):
     self.x0 = ws.act[0] if x0 is None else x0
     src = lambda i: self.x0 if i == 0 else ws.act[i]
     self.nseg = (nB + seg_size - 1) // seg_size
-    k, pl = net.k, net.pl
     # shifts[l][seg]: PhaseShuffle draw applied after layer l+1 (l = 0..3)
     if shifts is not None:
       assert (tuple(shifts.shape) == (4, self.nseg) and shifts.is_contiguous() and
@@ -856,21 +897,17 @@ class _DisPlan(object):
     self.coef = torch.zeros(self.nseg, dtype=torch.float32, device=dev)
     self.bias_coef = torch.zeros(self.nseg, dtype=torch.float32, device=dev)
     self.fwd, self.dgrad, self.jvp, self.wgrad = [], [], [], []
-    for i, lay in enumerate(net.layers):
+    for i, conv in enumerate(net.convs):
       sh = self.shifts[i - 1] if i > 0 else None
-      bias = net.params.views[2 * i + 1]
-      op = net.w_fwd[i]
       self.fwd.append(
-          _conv_desc(src(i), op.buf, ws.act[i + 1], nB, lay.lin, lay.cinp, k,
-                     2, -pl, lay.lout, lay.cout, lay.lout, lay.coutp, op.CK,
-                     bias=bias, shifts=sh, seg_size=seg_size,
-                     epilogue=_lib.EPI_LRELU, w_parity_major=op.parity_major,
-                     w_narrow_last=op.narrow_last, alpha=net.alpha))
+          conv.down(src(i), net.w_fwd[i], ws.act[i + 1], nB,
+                    bias=net.params.views[2 * i + 1], shifts=sh,
+                    seg_size=seg_size, epilogue=_lib.EPI_LRELU,
+                    alpha=net.alpha))
       self.wgrad.append(
-          _wgrad_desc(src(i), ws.delta[i + 1], net.params.grad_views[2 * i],
-                      nB, lay.lin, lay.cinp, lay.lout, lay.coutp, k, 2, -pl,
-                      lay.cin, lay.cout, shifts=sh, seg_size=seg_size,
-                      dbias=net.params.grad_views[2 * i + 1], slot=i))
+          conv.wgrad(src(i), ws.delta[i + 1], net.params.grad_views[2 * i], nB,
+                     shifts=sh, seg_size=seg_size,
+                     dbias=net.params.grad_views[2 * i + 1], slot=i))
     # input-gradient chain: layer i (1-based l = i+1) maps delta[l] -> e[l-1]
     # PhaseShuffle adjoint + LeakyReLU' mask in the input-gradient launch's
     # epilogue (rows stored at their source positions, masked there) when the
@@ -880,7 +917,6 @@ class _DisPlan(object):
     self.side = {}
     for i in range(len(net.layers) - 1, 0, -1):
       lay = net.layers[i]
-      op = net.w_dgrad[i]
       fused = _FUSE_UNSHUFFLE and 2 * m + 1 <= lay.lin
       extra = {}
       if fused:
@@ -889,34 +925,23 @@ class _DisPlan(object):
         extra = dict(mask_src=ws.act[i], epilogue=_lib.EPI_MASK,
                      out_shifts=(self.shifts[i - 1], seg_size, self.side[i], m),
                      alpha=net.alpha)
-      self.dgrad.append((i,
-                         _conv_desc(ws.delta[i + 1], op.buf,
-                                    ws.delta[i] if fused else ws.e[i], nB,
-                                    lay.lout, lay.coutp, k // 2, 1,
-                                    net.dgrad_offs[0], lay.lin // 2, lay.cin,
-                                    lay.lin, lay.cinp, op.CK, y_stride=2,
-                                    y_off=0, nphase=2,
-                                    w_phase_stride=op.elems,
-                                    off_phase_step=net.dgrad_offs[1] -
-                                    net.dgrad_offs[0], yoff_phase_step=1,
-                                    **extra)))
+      self.dgrad.append(
+          (i, net.convs[i].up(ws.delta[i + 1], net.w_dgrad[i],
+                              ws.delta[i] if fused else ws.e[i], nB, **extra)))
     # layer 1 over [real | fake] only + cg_lrelu_mix for the x^ segment (_L1_LINEAR)
     self.fwd_l1_pair = None
     if (_L1_LINEAR and self.nseg == 3 and nB == 3 * seg_size and
         input_grad_from == 2 * seg_size and 0.0 < net.alpha <= 1.0 and
         seg_size * net.layers[0].lout >= _L1_LINEAR_MIN_ROWS):
-      lay, op = net.layers[0], net.w_fwd[0]
-      self.fwd_l1_pair = _conv_desc(
-          self.x0[:2 * seg_size], op.buf, ws.act[1][:2 * seg_size], 2 * seg_size,
-          lay.lin, lay.cinp, k, 2, -pl, lay.lout, lay.cout, lay.lout, lay.coutp,
-          op.CK, bias=net.params.views[1], seg_size=seg_size,
-          epilogue=_lib.EPI_LRELU, w_parity_major=op.parity_major,
-          w_narrow_last=op.narrow_last, alpha=net.alpha)
+      self.fwd_l1_pair = net.convs[0].down(
+          self.x0[:2 * seg_size], net.w_fwd[0], ws.act[1][:2 * seg_size],
+          2 * seg_size, bias=net.params.views[1], seg_size=seg_size,
+          epilogue=_lib.EPI_LRELU, alpha=net.alpha)
     self.input_grad = None
     self.gin = None
+    self.gin_in_x0 = False
     if input_grad_from is not None:
       lay = net.layers[0]
-      op = net.w_dgrad[0]
       nG = nB - input_grad_from
       self.nG = nG
       # bf16 like every other activation gradient (its f32 sum of squares,
@@ -934,13 +959,9 @@ class _DisPlan(object):
       self.sumsq = None
       if want_norm and lay.lin // 2 >= 256 and (lay.lin // 2) % 256 == 0:
         self.sumsq = torch.zeros(nG, dtype=torch.float32, device=dev)
-      self.input_grad = _conv_desc(
-          ws.delta[1][input_grad_from:], op.buf, self.gin, nG, lay.lout,
-          lay.coutp, k // 2, 1, net.dgrad_offs[0], lay.lin // 2, lay.cin,
-          lay.lin, lay.cinp, op.CK, y_stride=2, y_off=0, nphase=2,
-          w_phase_stride=op.elems,
-          off_phase_step=net.dgrad_offs[1] - net.dgrad_offs[0],
-          yoff_phase_step=1, rowsumsq=self.sumsq)
+      self.input_grad = net.convs[0].up(
+          ws.delta[1][input_grad_from:], net.w_dgrad[0], self.gin, nG,
+          rowsumsq=self.sumsq)
     # (slots tensor, slots per sample) of the ordered penalty norm, or None
     self.ssq = getattr(self.input_grad, '_ssq', None)
     self.norm_deferred = False
@@ -962,27 +983,21 @@ class _DisPlan(object):
     gradient g sitting in X0 (gin_in_x0) the first launch reads g and applies
     coef_b in its epilogue (cg_conv_desc.row_scale)."""
     ws, net = self.ws, self.ws.net
-    fold = coef is not None and getattr(self, 'gin_in_x0', False)
+    fold = coef is not None and self.gin_in_x0
     s0 = seg_index * self.seg_size
     n = min(self.seg_size, self.nB - s0)
-    k, pl = net.k, net.pl
     lib = _lib.load()
 
     def build(fold_first):
       descs = []
-      for i, lay in enumerate(net.layers):
+      for i, conv in enumerate(net.convs):
         sh = self.shifts[i - 1][seg_index:] if i > 0 else None
-        op = net.w_fwd[i]
         seg_act = ws.act[i + 1][s0:s0 + n]
         descs.append(
-            _conv_desc((self.x0 if i == 0 else ws.act[i])[s0:s0 + n], op.buf,
-                       seg_act, n, lay.lin,
-                       lay.cinp, k, 2, -pl, lay.lout, lay.cout, lay.lout,
-                       lay.coutp, op.CK, mask_src=seg_act, shifts=sh,
-                       seg_size=n, epilogue=_lib.EPI_MASK,
-                       w_parity_major=op.parity_major,
-                       w_narrow_last=op.narrow_last, alpha=net.alpha,
-                       row_scale=coef if (fold_first and i == 0) else None))
+            conv.down((self.x0 if i == 0 else ws.act[i])[s0:s0 + n],
+                      net.w_fwd[i], seg_act, n, mask_src=seg_act, shifts=sh,
+                      seg_size=n, epilogue=_lib.EPI_MASK, alpha=net.alpha,
+                      row_scale=coef if (fold_first and i == 0) else None))
       return descs
 
     self.jvp = build(fold)
@@ -1104,9 +1119,11 @@ class GeneratorNet(object):
     self.alpha = geo.activation_alpha(hp)  # x -> max(x, alpha x)
     self.device = device
     self.k = hp.kernel_size
-    self.pl = geo.same_padding_left(self.k, hp.strides)
     self.nd = hp.noise_dim
     self.layers = geo.generator_layers(hp)
+    # W (k, 1, cout, cin): forward = up, input gradient = down
+    self.convs = [Stride2Layer(self.k, lay.cout, lay.cin, lay.lout)
+                  for lay in self.layers]
     self.C = hp.num_channels
     self.Cp = geo.pitch(self.C)
     self.L = hp.signal_shape[0]
@@ -1164,20 +1181,9 @@ class GeneratorNet(object):
     # packed operands
     self.w_in = PackedOperand(V[0], [(0, 1, 0, nflat, 1)], self.nd, nflat,
                               self.nd, self.nd, 1)
-    phases = _transpose_phases(self.k, self.pl)
-    self.fwd_offs = [o for _, o in phases]
-    self.w_fwd, self.w_dgrad = [], []
-    for lay, ic in zip(self.layers, self.idx_conv):
-      W = V[ic]
-      ci, co = lay.cin, lay.cout
-      ck = _ck_for(lay.cinp, 1, self.k // 2, lay.lin)
-      self.w_fwd.append(
-          PackedOperand(W, [(t0, -2, co * ci, 1, ci) for t0, _ in phases], ci,
-                        co, lay.cinp, ck, self.k // 2))
-      ck = _ck_for(lay.coutp, 2, self.k, lay.lin)
-      self.w_dgrad.append(
-          PackedOperand(W, [(0, 1, co * ci, ci, 1)], co, ci, lay.coutp, ck,
-                        self.k, parity_major=True))
+    self.w_fwd = [c.pack_up(V[ic]) for c, ic in zip(self.convs, self.idx_conv)]
+    self.w_dgrad = [c.pack_down(V[ic])
+                    for c, ic in zip(self.convs, self.idx_conv)]
     Wo = V[self.idx_out]
     ck = _ck_for(self.Cp, 1, 1, self.L)
     self.w_out = PackedOperand(Wo, [(0, 1, 0, self.C, 1)], self.C, self.C,
@@ -1255,27 +1261,15 @@ class _GenWorkspace(object):
       fuse = (net.layer_norm and not net.batch_norm and
               _ln_fusable(lay, op.CK, k // 2))
       self.ln_fused.append(fuse)
-      self.f_conv.append(
-          _conv_desc(self.h[i], op.buf, dst, B, lay.lin, lay.cinp, k // 2, 1,
-                     net.fwd_offs[0], lay.lin, lay.cout, lay.lout, lay.coutp,
-                     op.CK, y_stride=2, y_off=0, bias=V[ic + 1],
-                     epilogue=_lib.EPI_NONE
-                     if normed else _lib.EPI_LRELU, nphase=2,
-                     w_phase_stride=op.elems,
-                     off_phase_step=net.fwd_offs[1] - net.fwd_offs[0],
-                     yoff_phase_step=1,
-                     ln=(V[il], V[il + 1], self.h[i + 1], self.mean[i + 1],
-                         self.rstd[i + 1]) if fuse else None, alpha=net.alpha))
-      self.f_conv_fwd_only.append(
-          _conv_desc(self.h[i], op.buf, dst, B, lay.lin, lay.cinp, k // 2, 1,
-                     net.fwd_offs[0], lay.lin, lay.cout, lay.lout, lay.coutp,
-                     op.CK, y_stride=2, y_off=0, bias=V[ic + 1], nphase=2,
-                     w_phase_stride=op.elems,
-                     off_phase_step=net.fwd_offs[1] - net.fwd_offs[0],
-                     yoff_phase_step=1,
-                     ln=(V[il], V[il + 1], self.h[i + 1], None, None),
-                     alpha=net.alpha)
-          if fuse else self.f_conv[-1])
+      # (the fused LayerNorm sets its own epilogue; keep=False: no statistics)
+      conv = lambda stats: net.convs[i].up(
+          self.h[i], op, dst, B, bias=V[ic + 1],
+          epilogue=_lib.EPI_NONE if normed else _lib.EPI_LRELU,
+          ln=(V[il], V[il + 1], self.h[i + 1]) + stats if fuse else None,
+          alpha=net.alpha)
+      self.f_conv.append(conv((self.mean[i + 1], self.rstd[i + 1])))
+      self.f_conv_fwd_only.append(conv((None, None)) if fuse
+                                  else self.f_conv[-1])
     # (fallback for outputs wider than 128 channels; the streaming Dense of
     # forward() otherwise -- self.fake then has the narrower pitch Cf)
     self.f_out = None if net.streaming_out else _conv_desc(
@@ -1299,16 +1293,10 @@ class _GenWorkspace(object):
                          if need > 0 and (DETERMINISTIC or few_tiles) else None)
     self.b_dgrad, self.b_wgrad = [], []
     for i, (lay, ic) in enumerate(zip(net.layers, net.idx_conv)):
-      op = net.w_dgrad[i]
       self.b_dgrad.append(
-          _conv_desc(self.dy[i + 1], op.buf, self.dh[i], B, lay.lout, lay.coutp,
-                     k, 2, -net.pl, lay.lin, lay.cin, lay.lin, lay.cinp, op.CK,
-                     w_parity_major=op.parity_major,
-                     w_narrow_last=op.narrow_last))
+          net.convs[i].down(self.dy[i + 1], net.w_dgrad[i], self.dh[i], B))
       self.b_wgrad.append(
-          _wgrad_desc(self.dy[i + 1], self.h[i], G[ic], B, lay.lout, lay.coutp,
-                      lay.lin, lay.cinp, k, 2, -net.pl, lay.cout, lay.cin,
-                      slot=i))
+          net.convs[i].wgrad(self.dy[i + 1], self.h[i], G[ic], B, slot=i))
     self.b_in_wgrad = _wgrad_desc(self.z, self.dy[0], G[0], B, 1, nd, 1,
                                   w0 * nd, 1, 1, 0, nd, w0 * nd, slot='in')
 

@@ -36,11 +36,17 @@ def int_tensor(rng, shape, lo=-3, hi=3, scale=1.0):
       rng.randint(lo, hi + 1, size=shape).astype(np.float32) * scale)
 
 
-def pack(src_dev, phases, C_real, N_real, Cx, CK, taps, parity_major=False):
-  op = nets.PackedOperand(src_dev, phases, C_real, N_real, Cx, CK, taps,
-                          parity_major=parity_major)
+def packed(op):
+  """A PackedOperand (nets.Stride2Layer.pack_down / pack_up) with its buffer
+  filled: the nets pack all operands of a model in one launch instead."""
   op.repack()
   return op
+
+
+def pack(src_dev, phases, C_real, N_real, Cx, CK, taps, parity_major=False):
+  """Operands outside the stride-2 recipe (the 1-tap Dense launches)."""
+  return packed(nets.PackedOperand(src_dev, phases, C_real, N_real, Cx, CK, taps,
+                                   parity_major=parity_major))
 
 
 def numpy_pack(wl, Cx, CK):
@@ -58,14 +64,6 @@ def numpy_pack(wl, Cx, CK):
       q8, e = divmod(r, 8)
       out[:N, cc, tap * c8 + q8, e] = wl[tap, c, :]
   return out.reshape(Npad, -1)
-
-
-def swconv(x, op, y, *, nB, Lx, Cx, taps, stride, off, Lu, N, Ly, Cy, **kw):
-  d = nets._conv_desc(x, op.buf, y, nB, Lx, Cx, taps, stride, off, Lu, N, Ly,
-                      Cy, op.CK, **kw)
-  small = kw.pop('force_small', None)
-  _lib.call('cg_swconv', ctypes.byref(d), stream())
-  return d
 
 
 def conv_desc(*a, **kw):

@@ -16,7 +16,6 @@ import torch
 
 import oracle as O
 from calciumgan_amd import _lib
-from calciumgan_amd import geometry as geo
 from calciumgan_amd import nets
 
 pytestmark = pytest.mark.gpu
@@ -59,8 +58,8 @@ def test_cfg5_first_layer_contractions_are_adjoint_at_full_batch(nB, L, Ci, Co, 
   assert dt == torch.float16
   gen = torch.Generator(device=H.DEV)
   gen.manual_seed(4321)
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  pl = geo.same_padding_left(k, 2)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop, pl = lay.Ap, lay.Bp, lay.pl
   Lo = L // 2
   xd = _int_pitched(gen, nB, L, Ci, cip, dt)
   gd = _int_pitched(gen, nB, Lo, Co, cop, dt)
@@ -70,30 +69,19 @@ def test_cfg5_first_layer_contractions_are_adjoint_at_full_batch(nB, L, Ci, Co, 
   shifts = np.array([7, -10, 3], np.int32)
   sh = torch.tensor(shifts, device=H.DEV)
 
-  ck = nets._ck_for(cip, 2, k, Lo)
-  op = H.pack(W, [(0, 1, Ci * Co, Co, 1)], Ci, Co, cip, ck, k, parity_major=True)
+  op = H.packed(lay.pack_down(W))
   y = torch.zeros(nB, Lo, cop, dtype=torch.float32, device=H.DEV)
-  d = H.conv_desc(xd, op.buf, y, nB, L, cip, k, 2, -pl, Lo, Co, Lo, cop, ck,
-                  shifts=sh, seg_size=seg, out_f32=True,
-                  w_parity_major=op.parity_major, w_narrow_last=op.narrow_last)
+  d = lay.down(xd, op, y, nB, shifts=sh, seg_size=seg, out_f32=True)
   H.run_conv(d)
 
-  phases = nets._transpose_phases(k, pl)
-  offs = [o for _, o in phases]
-  ckd = nets._ck_for(cop, 1, k // 2, Lo)
-  opd = H.pack(W, [(t0, -2, Ci * Co, 1, Co) for t0, _ in phases], Co, Ci, cop,
-               ckd, k // 2)
+  opd = H.packed(lay.pack_up(W))
   dxs = torch.zeros(nB, L, cip, dtype=torch.float32, device=H.DEV)
   assert dxs.numel() * 4 > 2**33
-  dd = H.conv_desc(gd, opd.buf, dxs, nB, Lo, cop, k // 2, 1, offs[0], Lo, Ci, L,
-                   cip, ckd, y_stride=2, y_off=0, out_f32=True, nphase=2,
-                   w_phase_stride=opd.elems, off_phase_step=offs[1] - offs[0],
-                   yoff_phase_step=1)
+  dd = lay.up(gd, opd, dxs, nB, out_f32=True)
   H.run_conv(dd)
 
   dw = torch.zeros(k, Ci, Co, dtype=torch.float32, device=H.DEV)
-  dwd = nets._wgrad_desc(xd, gd, dw, nB, L, cip, Lo, cop, k, 2, -pl, Ci, Co,
-                         shifts=sh, seg_size=seg, slot=0)
+  dwd = lay.wgrad(xd, gd, dw, nB, shifts=sh, seg_size=seg, slot=0)
   H.run_wgrad(dwd)
   H.sync()
 

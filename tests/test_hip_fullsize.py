@@ -60,37 +60,27 @@ def test_conv_dgrad_wgrad_are_adjoint_at_full_size(nB, L, Ci, Co, k, seg):
   W = _rand_int(gen, (k, Ci, Co), -2, 2, 0.5)
   shifts = np.array([7, -10, 3], np.int32)[:nB // seg]
   sh = torch.tensor(shifts, device=H.DEV)
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  pl = geo.same_padding_left(k, 2)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop = lay.Ap, lay.Bp
   Lo = L // 2
   xd, gd = _pitched(x, cip), _pitched(g, cop)
 
   # y = conv(S x; W), f32
-  ck = nets._ck_for(cip, 2, k, Lo)
-  op = H.pack(W, [(0, 1, Ci * Co, Co, 1)], Ci, Co, cip, ck, k)
+  op = H.packed(lay.pack_down(W, parity_major=False))
   y = torch.zeros(nB, Lo, cop, dtype=torch.float32, device=H.DEV)
-  d = H.conv_desc(xd, op.buf, y, nB, L, cip, k, 2, -pl, Lo, Co, Lo, cop, ck,
-                  shifts=sh, seg_size=seg, out_f32=True)
+  d = lay.down(xd, op, y, nB, shifts=sh, seg_size=seg, out_f32=True)
   H.run_conv(d)
 
   # dxs = dgrad(g; W): gradient w.r.t. the shuffled input, f32
-  phases = nets._transpose_phases(k, pl)
-  offs = [o for _, o in phases]
-  ckd = nets._ck_for(cop, 1, k // 2, Lo)
-  opd = H.pack(W, [(t0, -2, Ci * Co, 1, Co) for t0, _ in phases], Co, Ci, cop,
-               ckd, k // 2)
+  opd = H.packed(lay.pack_up(W))
   dxs = torch.zeros(nB, L, cip, dtype=torch.float32, device=H.DEV)
-  dd = H.conv_desc(gd, opd.buf, dxs, nB, Lo, cop, k // 2, 1, offs[0], Lo, Ci, L,
-                   cip, ckd, y_stride=2, y_off=0, out_f32=True, nphase=2,
-                   w_phase_stride=opd.elems, off_phase_step=offs[1] - offs[0],
-                   yoff_phase_step=1)
+  dd = lay.up(gd, opd, dxs, nB, out_f32=True)
   H.run_conv(dd)
 
   # dW = wgrad(S x, g): K'-split partial sums + reducing launch (the product
   # path's form)
   dw = torch.zeros(k, Ci, Co, dtype=torch.float32, device=H.DEV)
-  dwd = nets._wgrad_desc(xd, gd, dw, nB, L, cip, Lo, cop, k, 2, -pl, Ci, Co,
-                         shifts=sh, seg_size=seg, slot=0)
+  dwd = lay.wgrad(xd, gd, dw, nB, shifts=sh, seg_size=seg, slot=0)
   H.run_wgrad(dwd)
   H.sync()
 
@@ -115,17 +105,15 @@ def test_conv_forward_is_linear_at_full_size(nB, L, Ci, Co, k, seg):
   W = _rand_int(gen, (k, Ci, Co), -2, 2, 0.5)
   b = _rand_int(gen, (Co,), -3, 3)
   shifts = torch.tensor(np.array([-4, 9, 0], np.int32), device=H.DEV)
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  pl = geo.same_padding_left(k, 2)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop = lay.Ap, lay.Bp
   Lo = L // 2
-  ck = nets._ck_for(cip, 2, k, Lo)
-  op = H.pack(W, [(0, 1, Ci * Co, Co, 1)], Ci, Co, cip, ck, k)
+  op = H.packed(lay.pack_down(W, parity_major=False))
   outs = []
   for xin, bias in ((x1, None), (x2, None), (x1 + x2, None), (x1, b)):
     y = torch.zeros(nB, Lo, cop, dtype=torch.float32, device=H.DEV)
-    d = H.conv_desc(_pitched(xin, cip), op.buf, y, nB, L, cip, k, 2, -pl, Lo,
-                    Co, Lo, cop, ck, shifts=shifts, seg_size=seg, bias=bias,
-                    out_f32=True)
+    d = lay.down(_pitched(xin, cip), op, y, nB, shifts=shifts, seg_size=seg,
+                 bias=bias, out_f32=True)
     H.run_conv(d)
     outs.append(y)
   H.sync()
@@ -254,48 +242,35 @@ def test_lean_epilogues_equal_the_classic_tiles_at_full_size(tile, nB, L, Ci, Co
     gen = torch.Generator(device=H.DEV)
     gen.manual_seed(99)
     k = 24
-    cip, cop = geo.pitch(Ci), geo.pitch(Co)
-    pl = geo.same_padding_left(k, 2)
+    lay = nets.Stride2Layer(k, Ci, Co, L)
+    cip, cop = lay.Ap, lay.Bp
     x = _pitched(_rand_int(gen, (nB, L, Ci), -2, 2), cip)
     W = _rand_int(gen, (k, Ci, Co), -1, 1, 0.5)
     bias = _rand_int(gen, (Co,), -2, 2)
-    ck = nets._ck_for(cip, 2, k, L // 2)
-    op = H.pack(W, [(0, 1, Ci * Co, Co, 1)], Ci, Co, cip, ck, k, parity_major=True)
+    op = H.packed(lay.pack_down(W))
     shifts = torch.tensor([3, -7, 10], dtype=torch.int32, device=H.DEV)
     # forward: bias + LeakyReLU (kEpiLrelu), fused input-side PhaseShuffle
     y = torch.empty(nB, L // 2, cop, dtype=BF16, device=H.DEV)
     _swp_vs_classic(
-        lambda: H.conv_desc(x, op.buf, y, nB, L, cip, k, 2, -pl, L // 2, Co,
-                            L // 2, cop, ck, bias=bias, shifts=shifts,
-                            seg_size=128, epilogue=_lib.EPI_LRELU,
-                            w_parity_major=True, w_narrow_last=op.narrow_last),
+        lambda: lay.down(x, op, y, nB, bias=bias, shifts=shifts, seg_size=128,
+                         epilogue=_lib.EPI_LRELU),
         [y], tile)
     # tangent form: LeakyReLU' mask read from another tensor (kEpiMask)
     h = _pitched(_rand_int(gen, (nB, L // 2, Co), -2, 2), cop)
     _swp_vs_classic(
-        lambda: H.conv_desc(x, op.buf, y, nB, L, cip, k, 2, -pl, L // 2, Co,
-                            L // 2, cop, ck, mask_src=h, shifts=shifts,
-                            seg_size=128, epilogue=_lib.EPI_MASK,
-                            w_parity_major=True, w_narrow_last=op.narrow_last),
+        lambda: lay.down(x, op, y, nB, mask_src=h, shifts=shifts, seg_size=128,
+                         epilogue=_lib.EPI_MASK),
         [y], tile)
     # input gradient: two phases, mask + output-side PhaseShuffle adjoint
     # (kEpiMaskShift), reflected rows through the side buffer
-    phases = nets._transpose_phases(k, pl)
-    ckd = nets._ck_for(cop, 1, k // 2, L // 2)
-    opd = H.pack(W, [(t0, -2, Ci * Co, 1, Co) for t0, _ in phases], Co, Ci, cop,
-                 ckd, k // 2)
+    opd = H.packed(lay.pack_up(W))
     g = _pitched(_rand_int(gen, (nB, L // 2, Co), -2, 2), cop)
     hx = _pitched(_rand_int(gen, (nB, L, Ci), -2, 2), cip)
     e = torch.empty(nB, L, cip, dtype=BF16, device=H.DEV)
     side = torch.empty(nB, 10, cip, dtype=BF16, device=H.DEV)
-    offs = [o for _, o in phases]
     _swp_vs_classic(
-        lambda: H.conv_desc(g, opd.buf, e, nB, L // 2, cop, k // 2, 1, offs[0],
-                            L // 2, Ci, L, cip, ckd, y_stride=2, y_off=0, nphase=2,
-                            w_phase_stride=opd.elems,
-                            off_phase_step=offs[1] - offs[0], yoff_phase_step=1,
-                            mask_src=hx, epilogue=_lib.EPI_MASK,
-                            out_shifts=(shifts, 128, side, 10)),
+        lambda: lay.up(g, opd, e, nB, mask_src=hx, epilogue=_lib.EPI_MASK,
+                       out_shifts=(shifts, 128, side, 10)),
         [e, side], tile)
   finally:
     nets._AUTOTUNE = nets_autotune
@@ -327,10 +302,9 @@ def test_flex_weight_gradients_equal_the_split_form_at_full_size():
     for mode in (0, 1):
       dw = torch.full((k, Ci, Co), 7.0, dtype=torch.float32, device=H.DEV)
       db = torch.full((Co,), 7.0, dtype=torch.float32, device=H.DEV)
-      d = nets._wgrad_desc(x, g, dw, nB, L, cip, L // 2, cop, k, 2,
-                           -geo.same_padding_left(k, 2), Ci, Co,
-                           shifts=sh if li else None, seg_size=seg, dbias=db,
-                           bias_rows=2 * seg * (L // 2), slot=(mode, li))
+      d = nets.Stride2Layer(k, Ci, Co, L).wgrad(
+          x, g, dw, nB, shifts=sh if li else None, seg_size=seg, dbias=db,
+          bias_rows=2 * seg * (L // 2), slot=(mode, li))
       assert d.partials and d.store
       descs[mode].append(d)
       outs[mode].append((dw, db))

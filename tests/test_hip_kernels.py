@@ -67,18 +67,16 @@ def test_conv_fwd_bitexact(nB, L, Ci, Co, k, seg, use_shift):
     shifts[:] = 0
   ref = O.leaky_relu(
       O.conv1d_same(_shuffle_batch(x, shifts, seg), W, b, 2)).to(BF16).float()
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop = lay.Ap, lay.Bp
   Lo = L // 2
-  pl = geo.same_padding_left(k, 2)
   Wd, bd = W.to(H.DEV), b.to(H.DEV)
-  ck = nets._ck_for(cip, 2, k, Lo)
-  op = H.pack(Wd, [(0, 1, Ci * Co, Co, 1)], Ci, Co, cip, ck, k)
+  op = H.packed(lay.pack_down(Wd, parity_major=False))
   xd = H.to_pitch(x, cip)
   y = torch.full((nB, Lo, cop), 7.0, dtype=BF16, device=H.DEV)
   sh = torch.tensor(shifts, device=H.DEV)
-  d = H.conv_desc(xd, op.buf, y, nB, L, cip, k, 2, -pl, Lo, Co, Lo, cop, ck,
-                  bias=bd, shifts=sh if use_shift else None, seg_size=seg,
-                  epilogue=_lib.EPI_LRELU)
+  d = lay.down(xd, op, y, nB, bias=bd, shifts=sh if use_shift else None,
+               seg_size=seg, epilogue=_lib.EPI_LRELU)
   H.run_conv(d)
   H.sync()
   got = y.float().cpu()
@@ -121,28 +119,18 @@ def _force_tile(d, tile, ks, sp=0):
   assert _lib.load().cg_swconv(ctypes.byref(d), H.stream()) == 0
 
 
-def _fwd_desc(xd, wbuf, y, nB, L, Ci, Co, k, sp, **kw):
-  """Descriptor of the stride-2 forward tests (device tensors, or _PH at
-  collection time)."""
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  Lo = L // 2
-  ck = nets._ck_for(cip, 2, k, Lo)
-  return H.conv_desc(xd, wbuf, y, nB, L, cip, k, 2, -geo.same_padding_left(k, 2),
-                     Lo, Co, Lo, cop, ck, w_parity_major=bool(sp),
-                     w_narrow_last=nets.narrow_last_rule(bool(sp), ck, cip, k, Ci),
-                     **kw)
+def _fwd_desc(nB, L, Ci, Co, k, sp, **kw):
+  """Collection-time descriptor of the stride-2 forward tests: placeholder
+  tensors (the operand's buffer is host memory that nobody fills)."""
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  return lay.down(_PH, lay.pack_down(_PH, parity_major=bool(sp)), _PH, nB, **kw)
 
 
-def _dgrad_desc(dyd, wbuf, y, nB, L, Ci, Co, k, **kw):
-  """Two-phase transposed convolution (input gradient of a stride-2 conv)."""
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  offs = [o for _, o in nets._transpose_phases(k, geo.same_padding_left(k, 2))]
-  ck = nets._ck_for(cop, 1, k // 2, L // 2)
-  elems = _lib.load().cg_packed_elems(Ci, k // 2, cop, ck)
-  return H.conv_desc(dyd, wbuf, y, nB, L // 2, cop, k // 2, 1, offs[0], L // 2,
-                     Ci, L, cip, ck, y_stride=2, y_off=0, nphase=2,
-                     w_phase_stride=elems, off_phase_step=offs[1] - offs[0],
-                     yoff_phase_step=1, **kw)
+def _dgrad_desc(nB, L, Ci, Co, k, **kw):
+  """... of the two-phase transposed convolution (input gradient of a stride-2
+  conv)."""
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  return lay.up(_PH, lay.pack_up(_PH), _PH, nB, **kw)
 
 
 def _tile_cases(shapes, admit, sps=(0,), tiles=None):
@@ -170,8 +158,8 @@ FWD_SHAPES = [(2, 1024, 64, 192, 24, 1), (6, 128, 96, 102, 24, 2),
 
 
 def _fwd_admits(tile, ks, sp, nB, L, Ci, Co, k, seg):
-  d = _fwd_desc(_PH, _PH, _PH, nB, L, Ci, Co, k, sp, bias=_PH, shifts=_PH,
-                seg_size=seg, epilogue=_lib.EPI_LRELU)
+  d = _fwd_desc(nB, L, Ci, Co, k, sp, bias=_PH, shifts=_PH, seg_size=seg,
+                epilogue=_lib.EPI_LRELU)
   return _admits(d, tile, ks, sp)
 
 
@@ -191,12 +179,10 @@ def test_conv_fwd_every_tile(tile, ks, nB, L, Ci, Co, k, seg, sp, epi_mode):
   shifts = rng.randint(-2, 3, size=nseg).astype(np.int32)
   ref = O.leaky_relu(
       O.conv1d_same(_shuffle_batch(x, shifts, seg), W, b, 2)).to(BF16).float()
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop = lay.Ap, lay.Bp
   Lo = L // 2
-  pl = geo.same_padding_left(k, 2)
-  ck = nets._ck_for(cip, 2, k, Lo)
-  op = H.pack(W.to(H.DEV), [(0, 1, Ci * Co, Co, 1)], Ci, Co, cip, ck, k,
-              parity_major=bool(sp))
+  op = H.packed(lay.pack_down(W.to(H.DEV), parity_major=bool(sp)))
   xd = H.to_pitch(x, cip)
   y = torch.full((nB, Lo, cop), 7.0, dtype=BF16, device=H.DEV)
   sh = torch.tensor(shifts, device=H.DEV)
@@ -204,9 +190,9 @@ def test_conv_fwd_every_tile(tile, ks, nB, L, Ci, Co, k, seg, sp, epi_mode):
   # Ci = 102 / 70 with parity-major weights: the last 32-channel chunk holds
   # 6 real channels and is packed / walked narrow (cg_pack_desc.narrow_last)
   assert op.narrow_last == (bool(sp) and Ci in (102, 70))
-  d = H.conv_desc(xd, op.buf, y, nB, L, cip, k, 2, -pl, Lo, Co, Lo, cop, ck,
-                  bias=bd, shifts=sh, seg_size=seg, epilogue=_lib.EPI_LRELU,
-                  w_parity_major=bool(sp), w_narrow_last=op.narrow_last)
+  assert op.narrow_last == lay.narrow_last(bool(sp))
+  d = lay.down(xd, op, y, nB, bias=bd, shifts=sh, seg_size=seg,
+               epilogue=_lib.EPI_LRELU)
   _force_tile(d, tile, ks, sp)
   H.sync()
   got = y.float().cpu()
@@ -223,7 +209,7 @@ def test_conv_fwd_every_tile(tile, ks, nB, L, Ci, Co, k, seg, sp, epi_mode):
 
 
 def _row_scale_admits(tile, ks, sp, nB, L, Ci, Co, k, epi):
-  d = _fwd_desc(_PH, _PH, _PH, nB, L, Ci, Co, k, 1, bias=_PH, epilogue=epi,
+  d = _fwd_desc(nB, L, Ci, Co, k, 1, bias=_PH, epilogue=epi,
                 mask_src=_PH if epi == _lib.EPI_MASK else None, row_scale=_PH)
   return _admits(d, tile, ks, 0)
 
@@ -247,12 +233,10 @@ def test_conv_fwd_row_scale(tile, ks, nB, L, Ci, Co, k, epi, sp, epi_mode):
   scale = torch.tensor(2.0 ** rng.randint(-3, 3, size=nB), dtype=torch.float32)
   scale[1] = -scale[1]
   lin = O.conv1d_same(x, W, b, 2) * scale[:, None, None]
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop = lay.Ap, lay.Bp
   Lo = L // 2
-  pl = geo.same_padding_left(k, 2)
-  ck = nets._ck_for(cip, 2, k, Lo)
-  op = H.pack(W.to(H.DEV), [(0, 1, Ci * Co, Co, 1)], Ci, Co, cip, ck, k,
-              parity_major=True)
+  op = H.packed(lay.pack_down(W.to(H.DEV)))
   xd = H.to_pitch(x, cip)
   y = torch.full((nB, Lo, cop), 7.0, dtype=BF16, device=H.DEV)
   mask = None
@@ -262,10 +246,8 @@ def test_conv_fwd_row_scale(tile, ks, nB, L, Ci, Co, k, epi, sp, epi_mode):
     mask = H.to_pitch(m, cop)
     ref = lin * torch.where(m > 0, 1.0, nets.LEAKY_ALPHA)
   sd = scale.to(H.DEV)
-  d = H.conv_desc(xd, op.buf, y, nB, L, cip, k, 2, -pl, Lo, Co, Lo, cop, ck,
-                  bias=b.to(H.DEV), epilogue=epi, mask_src=mask,
-                  w_parity_major=True, w_narrow_last=op.narrow_last,
-                  row_scale=sd)
+  d = lay.down(xd, op, y, nB, bias=b.to(H.DEV), epilogue=epi, mask_src=mask,
+               row_scale=sd)
   _force_tile(d, tile, 2, 0)
   H.sync()
   got = y.float().cpu()
@@ -283,15 +265,14 @@ def _split_k_cases():
   out = []
   for nB, L, Ci, Co, k, epi in [(3, 256, 128, 192, 24, 1), (2, 128, 102, 64, 24, 2),
                                 (4, 64, 256, 320, 24, 0), (2, 512, 256, 128, 24, 2)]:
-    cip = geo.pitch(Ci)
-    ck = nets._ck_for(cip, 2, k, L // 2)
+    lay = nets.Stride2Layer(k, Ci, Co, L)
     for tile in [0, 1, 2, 4, 8, 9, 10, 11, 12, 13, 14, 15]:
       for ksplit in (2, 4):
-        if (cip // ck) % ksplit:
+        if (lay.Ap // lay.ck_down) % ksplit:
           continue
-        d = _fwd_desc(_PH, _PH, _PH, nB, L, Ci, Co, k, 1,
-                      bias=_PH if epi == 1 else None, shifts=_PH, seg_size=1,
-                      epilogue=epi, mask_src=_PH if epi == 2 else None)
+        d = _fwd_desc(nB, L, Ci, Co, k, 1, bias=_PH if epi == 1 else None,
+                      shifts=_PH, seg_size=1, epilogue=epi,
+                      mask_src=_PH if epi == 2 else None)
         d.ksplit, d.split_ws, d.split_ws_elems = ksplit, _PH.data_ptr(), 1 << 40
         if _admits(d, tile, 2, 0):
           out.append((tile, ksplit, nB, L, Ci, Co, k, epi))
@@ -313,12 +294,10 @@ def test_conv_fwd_split_k(tile, ksplit, nB, L, Ci, Co, k, epi):
   shifts = rng.randint(-2, 3, size=nB).astype(np.int32)
   pre = O.conv1d_same(_shuffle_batch(x, shifts, 1), W, b if epi == 1 else None,
                       2)
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop = lay.Ap, lay.Bp
   Lo = L // 2
-  pl = geo.same_padding_left(k, 2)
-  ck = nets._ck_for(cip, 2, k, Lo)
-  op = H.pack(W.to(H.DEV), [(0, 1, Ci * Co, Co, 1)], Ci, Co, cip, ck, k,
-              parity_major=True)
+  op = H.packed(lay.pack_down(W.to(H.DEV)))
   y = torch.full((nB, Lo, cop), 7.0, dtype=BF16, device=H.DEV)
   hmask = None
   if epi == 2:  # in place: y holds the activations whose sign masks the result
@@ -331,11 +310,10 @@ def test_conv_fwd_split_k(tile, ksplit, nB, L, Ci, Co, k, epi):
   else:
     ref = pre.to(BF16).float()
   ws = torch.full((ksplit * nB * Lo * cop,), float('nan'), device=H.DEV)
-  d = H.conv_desc(H.to_pitch(x, cip), op.buf, y, nB, L, cip, k, 2, -pl, Lo, Co,
-                  Lo, cop, ck, bias=b.to(H.DEV) if epi == 1 else None,
-                  shifts=torch.tensor(shifts, device=H.DEV), seg_size=1,
-                  epilogue=epi, mask_src=y if epi == 2 else None,
-                  w_parity_major=True, w_narrow_last=op.narrow_last)
+  d = lay.down(H.to_pitch(x, cip), op, y, nB,
+               bias=b.to(H.DEV) if epi == 1 else None,
+               shifts=torch.tensor(shifts, device=H.DEV), seg_size=1,
+               epilogue=epi, mask_src=y if epi == 2 else None)
   d.ksplit, d.split_ws, d.split_ws_elems = ksplit, ws.data_ptr(), ws.numel()
   _force_tile(d, tile, 2, 0)
   H.sync()
@@ -346,7 +324,7 @@ def test_conv_fwd_split_k(tile, ksplit, nB, L, Ci, Co, k, epi):
 
 
 def _dgrad_admits(tile, ks, sp, nB, L, Ci, Co, k):
-  d = _dgrad_desc(_PH, _PH, _PH, nB, L, Ci, Co, k, out_f32=True)
+  d = _dgrad_desc(nB, L, Ci, Co, k, out_f32=True)
   if L // 2 >= _lib.tile_shape(tile)[0]:
     d.rowsumsq = _PH.data_ptr()
   return _admits(d, tile, ks, 0)
@@ -365,19 +343,12 @@ def test_conv_dgrad_every_tile(tile, ks, nB, L, Ci, Co, k, sp, epi_mode):
   x = torch.zeros(nB, L, Ci, requires_grad=True)
   (O.conv1d_same(x, W, None, 2) * dy).sum().backward()
   ref = x.grad
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  pl = geo.same_padding_left(k, 2)
-  phases = nets._transpose_phases(k, pl)
-  ck = nets._ck_for(cop, 1, k // 2, L // 2)
-  op = H.pack(W.to(H.DEV), [(t0, -2, Ci * Co, 1, Co) for t0, _ in phases], Co,
-              Ci, cop, ck, k // 2)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop = lay.Ap, lay.Bp
+  op = H.packed(lay.pack_up(W.to(H.DEV)))
   y = torch.full((nB, L, cip), 3.0, dtype=torch.float32, device=H.DEV)
-  offs = [o for _, o in phases]
   dyd = H.to_pitch(dy, cop)
-  d = H.conv_desc(dyd, op.buf, y, nB, L // 2, cop, k // 2, 1, offs[0], L // 2,
-                  Ci, L, cip, ck, y_stride=2, y_off=0, out_f32=True, nphase=2,
-                  w_phase_stride=op.elems, off_phase_step=offs[1] - offs[0],
-                  yoff_phase_step=1)
+  d = lay.up(dyd, op, y, nB, out_f32=True)
   rows, _ = _lib.tile_shape(tile)
   ssq = None
   if L // 2 >= rows:  # one sample per tile: the sum of squares can be fused
@@ -427,18 +398,11 @@ def test_conv_dgrad_bitexact(nB, L, Ci, Co, k):
   x = torch.zeros(nB, L, Ci, requires_grad=True)
   (O.conv1d_same(x, W, None, 2) * dy).sum().backward()
   ref = x.grad
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  pl = geo.same_padding_left(k, 2)
-  phases = nets._transpose_phases(k, pl)
-  ck = nets._ck_for(cop, 1, k // 2, L // 2)
-  op = H.pack(W.to(H.DEV), [(t0, -2, Ci * Co, 1, Co) for t0, _ in phases], Co,
-              Ci, cop, ck, k // 2)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop = lay.Ap, lay.Bp
+  op = H.packed(lay.pack_up(W.to(H.DEV)))
   y = torch.full((nB, L, cip), 3.0, dtype=torch.float32, device=H.DEV)
-  offs = [o for _, o in phases]
-  d = H.conv_desc(H.to_pitch(dy, cop), op.buf, y, nB, L // 2, cop, k // 2, 1,
-                  offs[0], L // 2, Ci, L, cip, ck, y_stride=2, y_off=0,
-                  out_f32=True, nphase=2, w_phase_stride=op.elems,
-                  off_phase_step=offs[1] - offs[0], yoff_phase_step=1)
+  d = lay.up(H.to_pitch(dy, cop), op, y, nB, out_f32=True)
   H.run_conv(d)
   H.sync()
   got = y.cpu()
@@ -457,32 +421,21 @@ def test_conv_transpose_fwd_bitexact(B, L, Ci, Co, k):
   Wt = H.int_tensor(rng, (k, 1, Co, Ci), -2, 2, 0.5)
   b = H.int_tensor(rng, (Co,), -4, 4)
   ref = O.conv1d_transpose_same(x, Wt, b, 2)
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  pl = geo.same_padding_left(k, 2)
-  phases = nets._transpose_phases(k, pl)
-  offs = [o for _, o in phases]
-  ck = nets._ck_for(cip, 1, k // 2, L)
-  op = H.pack(Wt.to(H.DEV), [(t0, -2, Co * Ci, 1, Ci) for t0, _ in phases], Ci,
-              Co, cip, ck, k // 2)
+  lay = nets.Stride2Layer(k, Co, Ci, 2 * L)  # a generator layer: forward = up
+  cip, cop = lay.Bp, lay.Ap
+  op = H.packed(lay.pack_up(Wt.to(H.DEV)))
   y = torch.zeros(B, 2 * L, cop, dtype=torch.float32, device=H.DEV)
-  d = H.conv_desc(H.to_pitch(x, cip), op.buf, y, B, L, cip, k // 2, 1, offs[0],
-                  L, Co, 2 * L, cop, ck, y_stride=2, bias=b.to(H.DEV),
-                  out_f32=True, nphase=2, w_phase_stride=op.elems,
-                  off_phase_step=offs[1] - offs[0], yoff_phase_step=1)
+  d = lay.up(H.to_pitch(x, cip), op, y, B, bias=b.to(H.DEV), out_f32=True)
   H.run_conv(d)
   H.sync()
   np.testing.assert_array_equal(y.cpu()[:, :, :Co].numpy(), ref.numpy())
 
 
-def _ln_desc(xd, wbuf, y, B, L, Ci, Co, k, **kw):
-  """Conv1DTranspose forward (two 12-tap phases) of the fused-LayerNorm test."""
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  offs = [o for _, o in nets._transpose_phases(k, geo.same_padding_left(k, 2))]
-  ck = nets._ck_for(cip, 1, k // 2, L)
-  elems = _lib.load().cg_packed_elems(Co, k // 2, cip, ck)
-  return H.conv_desc(xd, wbuf, y, B, L, cip, k // 2, 1, offs[0], L, Co, 2 * L,
-                     cop, ck, y_stride=2, nphase=2, w_phase_stride=elems,
-                     off_phase_step=offs[1] - offs[0], yoff_phase_step=1, **kw)
+def _ln_desc(B, L, Ci, Co, k, **kw):
+  """... of the Conv1DTranspose forward (two 12-tap phases) of the
+  fused-LayerNorm test."""
+  lay = nets.Stride2Layer(k, Co, Ci, 2 * L)
+  return lay.up(_PH, lay.pack_up(_PH), _PH, B, **kw)
 
 
 def _ln_cases():
@@ -494,8 +447,7 @@ def _ln_cases():
       tm = _lib.tile_shape(tile)[0]
       if not ((L % tm == 0) if L >= tm else (tm % L == 0)):
         continue
-      d = _ln_desc(_PH, _PH, _PH, B, L, Ci, Co, k, bias=_PH,
-                   ln=(_PH, _PH, _PH, _PH, _PH))
+      d = _ln_desc(B, L, Ci, Co, k, bias=_PH, ln=(_PH, _PH, _PH, _PH, _PH))
       if _admits(d, tile, ks):
         out.append((tile, ks, B, L, Ci, Co, k))
   return out
@@ -513,13 +465,9 @@ def test_conv_transpose_layernorm_fused(tile, ks, B, L, Ci, Co, k):
   b = torch.tensor(rng.randn(Co).astype(np.float32) * 0.2)
   gam = torch.tensor(rng.rand(Co).astype(np.float32) + 0.5).to(H.DEV)
   bet = torch.tensor(rng.randn(Co).astype(np.float32) * 0.1).to(H.DEV)
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  pl = geo.same_padding_left(k, 2)
-  phases = nets._transpose_phases(k, pl)
-  offs = [o for _, o in phases]
-  ck = nets._ck_for(cip, 1, k // 2, L)
-  op = H.pack(Wt.to(H.DEV), [(t0, -2, Co * Ci, 1, Ci) for t0, _ in phases], Ci,
-              Co, cip, ck, k // 2)
+  lay = nets.Stride2Layer(k, Co, Ci, 2 * L)
+  cip, cop = lay.Bp, lay.Ap
+  op = H.packed(lay.pack_up(Wt.to(H.DEV)))
   rows = B * 2 * L
   xd = H.to_pitch(x, cip)
   z = lambda *s, dt=BF16: torch.zeros(*s, dtype=dt, device=H.DEV)
@@ -527,23 +475,19 @@ def test_conv_transpose_layernorm_fused(tile, ks, B, L, Ci, Co, k):
   m0, r0 = z(rows, dt=torch.float32), z(rows, dt=torch.float32)
   y1, h1 = z(B, 2 * L, cop), z(B, 2 * L, cop)
   m1, r1 = z(rows, dt=torch.float32), z(rows, dt=torch.float32)
-  common = dict(y_stride=2, bias=b.to(H.DEV), nphase=2, w_phase_stride=op.elems,
-                off_phase_step=offs[1] - offs[0], yoff_phase_step=1)
-  d0 = H.conv_desc(xd, op.buf, y0, B, L, cip, k // 2, 1, offs[0], L, Co, 2 * L,
-                   cop, ck, **common)
+  bd = b.to(H.DEV)
+  d0 = lay.up(xd, op, y0, B, bias=bd)
   H.run_conv(d0)
   _lib.call('cg_ln_lrelu_fwd', H.p(y0), H.p(gam), H.p(bet), H.p(h0), H.p(m0),
             H.p(r0), rows, Co, cop, 1e-3, ALPHA, H.stream())
-  d1 = H.conv_desc(xd, op.buf, y1, B, L, cip, k // 2, 1, offs[0], L, Co, 2 * L,
-                   cop, ck, ln=(gam, bet, h1, m1, r1), **common)
+  d1 = lay.up(xd, op, y1, B, bias=bd, ln=(gam, bet, h1, m1, r1))
   d1.tile, d1.stage_ksteps = tile, ks
   assert _lib.load().cg_swconv_check(ctypes.byref(d1)) == 0
   H.run_conv(d1)
   # forward-only form (no statistics buffers): same activation, y not written
   y2 = torch.full((B, 2 * L, cop), 5.0, dtype=BF16, device=H.DEV)
   h2 = z(B, 2 * L, cop)
-  d2 = H.conv_desc(xd, op.buf, y2, B, L, cip, k // 2, 1, offs[0], L, Co, 2 * L,
-                   cop, ck, ln=(gam, bet, h2, None, None), **common)
+  d2 = lay.up(xd, op, y2, B, bias=bd, ln=(gam, bet, h2, None, None))
   d2.tile, d2.stage_ksteps = tile, ks
   H.run_conv(d2)
   H.sync()
@@ -581,12 +525,11 @@ def test_conv_transpose_dgrad_bitexact(B, L, Ci, Co, k):
   dy = H.int_tensor(rng, (B, 2 * L, Co))
   x = torch.zeros(B, L, Ci, requires_grad=True)
   (O.conv1d_transpose_same(x, Wt, None, 2) * dy).sum().backward()
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  ck = nets._ck_for(cop, 2, k, L)
-  op = H.pack(Wt.to(H.DEV), [(0, 1, Co * Ci, Ci, 1)], Co, Ci, cop, ck, k)
+  lay = nets.Stride2Layer(k, Co, Ci, 2 * L)  # generator: input gradient = down
+  cip, cop = lay.Bp, lay.Ap
+  op = H.packed(lay.pack_down(Wt.to(H.DEV), parity_major=False))
   y = torch.zeros(B, L, cip, dtype=torch.float32, device=H.DEV)
-  d = H.conv_desc(H.to_pitch(dy, cop), op.buf, y, B, 2 * L, cop, k, 2, -11, L,
-                  Ci, L, cip, ck, out_f32=True)
+  d = lay.down(H.to_pitch(dy, cop), op, y, B, out_f32=True)
   H.run_conv(d)
   H.sync()
   np.testing.assert_array_equal(y.cpu()[:, :, :Ci].numpy(), x.grad.numpy())
@@ -801,11 +744,6 @@ WGRAD_CASES = [
 ]
 
 
-def _wgrad_test_desc(x, g, dw, nB, L, Ci, Co, k, **kw):
-  return nets._wgrad_desc(x, g, dw, nB, L, geo.pitch(Ci), L // 2, geo.pitch(Co), k,
-                          2, -geo.same_padding_left(k, 2), Ci, Co, **kw)
-
-
 def _wgrad_cases():
   """(case, partials, classic); the partial-sum form only where three K' splits
   exist at the shape."""
@@ -815,7 +753,8 @@ def _wgrad_cases():
     for partials in (False, 'add', 'store'):
       for classic in (0, 1):
         if partials:
-          d = _wgrad_test_desc(_PH, _PH, _PH, nB, L, Ci, Co, k, seg_size=seg)
+          d = nets.Stride2Layer(k, Ci, Co, L).wgrad(_PH, _PH, _PH, nB,
+                                                    seg_size=seg)
           d.classic_staging, d.nsplit = classic, 3
           if _lib.load().cg_wgrad_partials_elems(ctypes.byref(d)) <= 0:
             continue
@@ -849,11 +788,10 @@ def test_conv_wgrad_bitexact(nB, L, Ci, Co, k, seg, use_shift, partials, classic
   sh = torch.tensor(shifts, device=H.DEV)
   dbias = torch.zeros(Co, dtype=torch.float32, device=H.DEV)
   nb_bias = max(1, (2 * nB) // 3)  # bias gradient over the first samples only
-  d = nets._wgrad_desc(H.to_pitch(x, cip), H.to_pitch(dy, cop), dw, nB, L, cip,
-                       L // 2, cop, k, 2, -geo.same_padding_left(k, 2), Ci, Co,
-                       shifts=sh if use_shift else None, seg_size=seg,
-                       dbias=dbias, bias_rows=nb_bias * (L // 2),
-                       slot=0 if partials else None)
+  d = nets.Stride2Layer(k, Ci, Co, L).wgrad(
+      H.to_pitch(x, cip), H.to_pitch(dy, cop), dw, nB,
+      shifts=sh if use_shift else None, seg_size=seg, dbias=dbias,
+      bias_rows=nb_bias * (L // 2), slot=0 if partials else None)
   d.classic_staging = classic
   if partials:
     d.nsplit = 3  # several K' splits whatever the shape
@@ -881,8 +819,8 @@ def test_conv_transpose_wgrad_bitexact():
   (O.conv1d_transpose_same(x, Wt, None, 2) * dy).sum().backward()
   cip, cop = geo.pitch(Ci), geo.pitch(Co)
   dw = torch.zeros(k, 1, Co, Ci, dtype=torch.float32, device=H.DEV)
-  d = nets._wgrad_desc(H.to_pitch(dy, cop), H.to_pitch(x, cip), dw, B, 2 * L,
-                       cop, L, cip, k, 2, -11, Co, Ci)
+  d = nets.Stride2Layer(k, Co, Ci, 2 * L).wgrad(
+      H.to_pitch(dy, cop), H.to_pitch(x, cip), dw, B)
   H.run_wgrad(d)
   H.sync()
   np.testing.assert_array_equal(dw.cpu().numpy(), Wt.grad.numpy())
@@ -985,30 +923,22 @@ def test_dgrad_with_fused_unshuffle(nB, L, Ci, Co, k, seg, m, epi_mode):
   shifts = rng.randint(-m, m + 1, size=nseg).astype(np.int32)
   if m:
     shifts[0], shifts[-1] = m, -m
-  cip, cop = geo.pitch(Ci), geo.pitch(Co)
-  pl = geo.same_padding_left(k, 2)
-  phases = nets._transpose_phases(k, pl)
-  offs = [o for _, o in phases]
-  ck = nets._ck_for(cop, 1, k // 2, L // 2)
-  op = H.pack(W.to(H.DEV), [(t0, -2, Ci * Co, 1, Co) for t0, _ in phases], Co,
-              Ci, cop, ck, k // 2)
+  lay = nets.Stride2Layer(k, Ci, Co, L)
+  cip, cop = lay.Ap, lay.Bp
+  op = H.packed(lay.pack_up(W.to(H.DEV)))
   dyd, hd = H.to_pitch(dy, cop), H.to_pitch(h, cip)
   sh = torch.tensor(shifts, device=H.DEV)
-  common = dict(y_stride=2, y_off=0, nphase=2, w_phase_stride=op.elems,
-                off_phase_step=offs[1] - offs[0], yoff_phase_step=1)
   z = lambda *s_: torch.zeros(*s_, dtype=BF16, device=H.DEV)
   e, d0 = z(nB, L, cip), z(nB, L, cip)
-  da = H.conv_desc(dyd, op.buf, e, nB, L // 2, cop, k // 2, 1, offs[0], L // 2,
-                   Ci, L, cip, ck, **common)
+  da = lay.up(dyd, op, e, nB)
   H.run_conv(da)
   _lib.call('cg_unshuffle_mask', H.p(e), H.p(hd), H.p(d0), H.p(sh), nB, L, cip,
             seg, ALPHA, H.stream())
   sr = max(1, m)
   side = z(nB, sr, cip)
   d1 = torch.full((nB, L, cip), 9.0, dtype=BF16, device=H.DEV)
-  db = H.conv_desc(dyd, op.buf, d1, nB, L // 2, cop, k // 2, 1, offs[0], L // 2,
-                   Ci, L, cip, ck, mask_src=hd, epilogue=_lib.EPI_MASK,
-                   out_shifts=(sh, seg, side, sr), **common)
+  db = lay.up(dyd, op, d1, nB, mask_src=hd, epilogue=_lib.EPI_MASK,
+              out_shifts=(sh, seg, side, sr))
   H.run_conv(db)
   _lib.call('cg_unshuffle_fixup', H.p(side), H.p(hd), H.p(d1), H.p(sh), nB, L,
             cip, seg, sr, ALPHA, H.stream())
@@ -1347,11 +1277,9 @@ def test_wgrad_batched_equals_individual_launches(wgrad_form):
     for descs, outs in ((descs_a, outs_a), (descs_b, outs_b)):
       dw = torch.zeros(k, Ci, Co, dtype=torch.float32, device=H.DEV)
       db = torch.zeros(Co, dtype=torch.float32, device=H.DEV)
-      d = nets._wgrad_desc(x, g, dw, nB, L, geo.pitch(Ci), L // 2,
-                           geo.pitch(Co), k, 2, -geo.same_padding_left(k, 2),
-                           Ci, Co, shifts=sh, seg_size=2, dbias=db,
-                           bias_rows=3 * (L // 2),
-                           slot=len(descs) if descs is descs_b else None)
+      d = nets.Stride2Layer(k, Ci, Co, L).wgrad(
+          x, g, dw, nB, shifts=sh, seg_size=2, dbias=db, bias_rows=3 * (L // 2),
+          slot=len(descs) if descs is descs_b else None)
       descs.append(d)
       outs.append((dw, db))
   for d in descs_a:
