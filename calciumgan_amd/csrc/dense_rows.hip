@@ -102,7 +102,9 @@ __global__ __launch_bounds__(kDrThreads, 2) void dense_rows_kernel(
       for (int e = 0; e < 4; ++e) {
         const float t = v[e] + bv[e];
         const float sg = 1.f / (1.f + __expf(-t));
-        v[e] = (sig ? sg : t) * keep[e];  // channel padding stays zero
+        // (a select, not a product with 0: a row of inf / NaN must leave the
+        // channel padding +0 as well)
+        v[e] = keep[e] != 0.f ? (sig ? sg : t) : 0.f;
       }
       if (m < a.rows && tcol < a.Cy)
         *reinterpret_cast<f32x4*>(a.y + m * a.Cy + tcol) = v;
@@ -242,7 +244,7 @@ __global__ __launch_bounds__(kDrThreads, 2) void dense_rows_interp_kernel(
       for (int e = 0; e < 4; ++e) {
         const float t = f[e] + bv[e];
         const float sg = 1.f / (1.f + __expf(-t));
-        f[e] = (sig ? sg : t) * keep[e];
+        f[e] = keep[e] != 0.f ? (sig ? sg : t) : 0.f;
         xh[e] = al * rr[pass][e] + (1.f - al) * f[e];
       }
       if (tcol < a.Cp) {

@@ -223,7 +223,8 @@ int cg_swconv_check(const cg_conv_desc* d);
 /* Streaming form of the 1-tap case with f32 output (the generator's last
  * layers.Dense + sigmoid, calciumgan.py:96-101; HBM-bound):
  *   y[r, n] = epi(bias[n] + sum_c x[r, c] * W[c][n]),  y[r, n >= N] = 0
- * x bf16 [rows][Cx], y f32 [rows][Cy]; `w` is the cg_pack_weights operand for
+ * x bf16 / fp16 (the build's activation type) [rows][Cx], y f32 [rows][Cy]; `w`
+ * is the cg_pack_weights operand for
  * (taps 1, Cx, CK 32).  Epilogue CG_EPI_NONE or CG_EPI_SIGMOID.  Two forms:
  * Cx in {32, 64, 96, 128} and N <= Cy <= 128 (Cy % 4 == 0): every wave holds W
  * in registers; otherwise Cx in {128, 256, 384, 512}, any N <= Cy (Cy % 8 == 0):
@@ -233,13 +234,13 @@ int cg_dense_rows(const void* x, const void* w, const float* bias, float* y,
                   long long rows, int Cx, int N, int Cy, int epilogue,
                   void* stream);
 /* cg_dense_rows for the fake batches of ALL n critic updates of one train() -- x
- * bf16 [n * B * L][Cx], the generator's last hidden layer over n * B samples --
+ * bf16 / fp16 [n * B * L][Cx], the generator's last hidden layer over n * B samples --
  * fused with cg_interp_pack.  Register form: Cx in {32, 64, 96, 128}, N <= 128, Cp =
  * 128.  LDS-panel form (ABI 19; BASELINE configs[4]): Cx in {128, 256, 384, 512}
  * with Cx > 128 or N > 128, Cp >= N a multiple of 8, B * L % 32 == 0; without x^
  * (alpha == NULL) the Dense only stores its fake segments and a second launch
  * reads `real` once for the n real segments.
- * x0[k] (bf16 [3 B][L][Cp]) receives [real | fake_k | x^_k], x^ =
+ * x0[k] (bf16 / fp16 [3 B][L][Cp]) receives [real | fake_k | x^_k], x^ =
  * alpha[k * B + b] * real + (1 - alpha) * fake (wgan_gp.py:38-41, interpolation
  * in f32 on the f32 Dense output as the reference does).  The f32 fake batch
  * never reaches HBM and `real` (f32 [B][L][Cr]) is read once.  L % 16 == 0,

@@ -667,7 +667,10 @@ def test_dense_rows_wide(rows, Ci, Co, epi):
   configs[4]'s 512 -> 512 per-timestep Dense) and its activation-typed twin
   cg_dense_rows_act (the input gradient dh = dz W^T): exact on integer data,
   f32 tolerance through the sigmoid, padding columns zero, ragged row counts,
-  several 128-column panels, row blocks that wrap the grid."""
+  several 128-column panels.  (No case here has enough rows for a wave to take a
+  second block -- 8192 rows at 512 -> 512, 10240 at 512 -> 300, 65536 at K = 128:
+  the row blocks that wrap the grid are WIDE_WRAP / ACT_ONLY of
+  tests/test_hip_dense_rows.py.)"""
   rng = np.random.RandomState(22)
   cip, cop = geo.pitch(Ci), geo.pitch(Co)
   x = H.int_tensor(rng, (1, rows, Ci), -3, 3)
