@@ -918,9 +918,12 @@ extern "C" long long cg_packed_elems(int N, int taps, int Cx, int CK) {
 }
 
 static bool narrow_ok(const cg_pack_desc* d) {
+  // (taps >= 6: the chunk's ceil16(4 taps) positions must hold the 32 narrow ones --
+  // with 2 or 4 taps the odd taps' 16 slots lay past the chunk and were dropped)
   return !d->narrow_last ||
-         (d->parity_major && d->CK == 32 && d->taps <= 32 && !(d->taps & 1) &&
-          d->Cx >= 64 && d->C_real > d->Cx - 32 && d->C_real <= d->Cx - 24);
+         (d->parity_major && d->CK == 32 && d->taps >= 6 && d->taps <= 32 &&
+          !(d->taps & 1) && d->Cx >= 64 && d->C_real > d->Cx - 32 &&
+          d->C_real <= d->Cx - 24);
 }
 
 static int fill_pack_args(const cg_pack_desc* d, PackArgs& a) {
@@ -1229,7 +1232,8 @@ static int swconv_run(const cg_conv_desc* d, void* stream) {
   }
   a.narrow = 0;
   if (d->w_narrow_last) {
-    if (R != 2 || !a.pmajor || d->CK != 32 || d->Cx / d->CK < 2 || d->taps > 32)
+    if (R != 2 || !a.pmajor || d->CK != 32 || d->Cx / d->CK < 2 || d->taps > 32 ||
+        d->taps < 6)
       return CG_EINVAL;
     a.narrow = 1;
   }

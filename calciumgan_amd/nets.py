@@ -165,7 +165,7 @@ def narrow_last_rule(parity_major, CK, Cx, taps, C_real):
   """Whether a packed operand's last 32-channel chunk is laid out narrow (one
   8-channel group per tap): a 102-of-128 kind of pitch, parity-major weights."""
   return bool(_NARROW_LAST and parity_major and CK == 32 and Cx >= 64 and
-              taps <= 32 and Cx - 32 < C_real <= Cx - 24)
+              6 <= taps <= 32 and Cx - 32 < C_real <= Cx - 24)
 
 
 class PackedOperand(object):

@@ -292,8 +292,8 @@ typedef struct cg_pack_desc {
                        then the odd ones -- the order in which a stride-2 launch
                        with w_parity_major walks them (one source-row parity
                        at a time) */
-  int narrow_last;  /* 1 (needs parity_major, CK == 32, taps <= 32, and
-                       Cx - 32 < C_real <= Cx - 24: the last channel chunk
+  int narrow_last;  /* 1 (needs parity_major, CK == 32, 6 <= taps <= 32, Cx >= 64
+                       and Cx - 32 < C_real <= Cx - 24: the last channel chunk
                        holds at most 8 real channels): that chunk is packed as
                        one 8-channel group per tap -- 16 slots per tap parity,
                        K = 32 groups instead of taps*4 -- for launches with
