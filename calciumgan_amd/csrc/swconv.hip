@@ -556,9 +556,12 @@ swconv_kernel(ConvArgs a) {
             float hv[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
+              const int n = (e < 4 ? nA : nB - 4) + e;  // (as in the statistics)
               const float t = (v[e] - mean) * rstd * (e < 4 ? g0[e] : g1[e - 4]) +
                               (e < 4 ? b0[e] : b1[e - 4]);
-              hv[e] = fmaxf(t, a.alpha * t);
+              // (channel padding stays +0 whatever the row holds: with NaN / inf
+              // statistics the zero gamma / beta of a padding column give NaN)
+              hv[e] = n < a.N ? fmaxf(t, a.alpha * t) : 0.f;
             }
             // (forward-only callers -- G(z) of a critic update -- pass no
             // statistics buffers: the pre-activation is then not stored either)
@@ -1164,8 +1167,11 @@ static int swconv_run(const cg_conv_desc* d, void* stream) {
        d->side_rows < 1 || d->epilogue == CG_EPI_LN_LRELU ||
        d->epilogue == CG_EPI_SIGMOID || d->epilogue == CG_EPI_LRELU))
     return CG_EINVAL;
+  // (stride 1 only: the stride-2 dispatch has no LayerNorm instantiation, and
+  // its split-parity branch would otherwise run the launch without the epilogue)
   if (d->epilogue == CG_EPI_LN_LRELU &&
-      (tc.wgn != 2 || d->N > 128 || d->out_f32 || d->rowsumsq || !d->ln_gamma ||
+      (d->stride != 1 || tc.wgn != 2 || d->N > 128 || d->out_f32 || d->rowsumsq ||
+       !d->ln_gamma ||
        !d->ln_beta || !d->ln_h || (!d->ln_mean != !d->ln_rstd)))
     return CG_EINVAL;
   const int TM = tc.swp_wm ? tc.swp_wm * tc.mt * 16 : (4 / tc.wgn) * tc.mt * tc.mf;

@@ -848,7 +848,9 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
                 const float t =
                     (v[p][e] - mean) * rstd * (e < 4 ? g0[e] : g1[e - 4]) +
                     (e < 4 ? b0v[e] : b1v[e - 4]);
-                hv[e] = fmaxf(t, a.alpha * t);
+                // (channel padding stays +0 whatever the row holds: with NaN / inf
+                // statistics the zero gamma / beta of a padding column give NaN)
+                hv[e] = n + e < a.N ? fmaxf(t, a.alpha * t) : 0.f;
               }
               // (forward-only callers pass no statistics buffers: the
               // pre-activation is then not stored either)

@@ -52,9 +52,11 @@ extern "C" {
 /* Software-pipelined tiles (swconv_swp.hip): two waves per SIMD (one 8-wave
  * workgroup or two 4-wave workgroups per CU), fragments double-buffered in
  * registers at K-step granularity, the source window and the weight ring both
- * filled by LDS-DMA.  v_mfma_f32_16x16x32, CK == 32, at least six taps per
- * source-row parity; split-K over whole channel chunks; the LayerNorm epilogue
- * on the 128-column tiles.
+ * filled by LDS-DMA.  v_mfma_f32_16x16x32, CK == 32, exactly twelve taps per
+ * source-row parity (24 taps at stride 2 with a parity-major operand, 12 per
+ * phase at stride 1), at least 16 rows of a sample per wave subtile and at most
+ * eight samples per row tile; split-K over whole channel chunks; the LayerNorm
+ * epilogue on the 128-column tiles.
  * Same results as the tiles above. */
 #define CG_TILE_SWP_512x64 9
 #define CG_TILE_SWP_256x64 10
@@ -151,7 +153,9 @@ typedef struct cg_conv_desc {
   int tile;             /* CG_TILE_* */
   int stage_ksteps;     /* 0: choose; 2 or 4: MFMA K-steps per weight stage */
   float* rowsumsq;      /* optional f32 [nB]: += sum over (row, n) of y^2 per
-                           sample (penalty norm, wgan_gp.py:49); needs Lu >= tile */
+                           sample (penalty norm, wgan_gp.py:49); needs Lu >= tile.
+                           The value squared is the f32 epilogue result, BEFORE
+                           it is rounded to a bf16 / fp16 y */
   int w_parity_major;   /* stride 2: `w` was packed with parity_major = 1 */
   int split_parity;     /* stride 2 + w_parity_major: stage one source-row
                            parity at a time (half the LDS window, twice the
@@ -160,7 +164,7 @@ typedef struct cg_conv_desc {
    * Conv1DTranspose, calciumgan.py:68-70 fused into the producing launch):
    * y receives the bf16 pre-activation, ln_h = lrelu(LN(y)), ln_mean / ln_rstd
    * the per-row statistics (indexed like rows of y) cg_ln_lrelu_bwd consumes.
-   * Needs N <= 128, bf16 output and a 128-column tile (cg_tile_shape).
+   * Needs stride 1, N <= 128, bf16 output and a 128-column tile (cg_tile_shape).
    * ln_mean = ln_rstd = NULL: forward only -- neither the statistics nor the
    * pre-activation y are stored (y may then be any non-NULL pointer). */
   const float* ln_gamma; /* f32 [N] */
