@@ -190,6 +190,10 @@ SIGNATURES = {
     'cg_spike_stats_error_ws_elems': [c_ll, c_ll],
     'cg_spike_stats_error': [c_vp, c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_vp,
                              c_vp],
+    # van_rossum.hip / spikes.hip: per-trial statistics of compute_metrics.py
+    'cg_van_rossum': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_d, c_vp, c_vp,
+                      c_vp],
+    'cg_spike_corrcoef': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_vp, c_vp],
 }
 _RESTYPES = {'cg_packed_elems': c_ll, 'cg_pack_plan_bytes': c_ll,
              'cg_pack_plan_build': c_ll, 'cg_wgrad_partials_elems': c_ll,

@@ -6,6 +6,8 @@
 //   cg_spike_stats        per sample: firing rate per neuron and the upper
 //                         triangle of the covariance of the 500-ms bin counts
 //   cg_spike_stats_error  sums of |d| and d^2 between two such sets, ordered
+//   cg_spike_corrcoef     per sample: Pearson correlation of the same bin counts,
+//                         float64 (compute_metrics.py --device gpu)
 // None of these is a throughput kernel: the deconvolution is a chain of
 // dependent float64 divisions per trace (13 056 traces = 204 waves at B = 128),
 // the statistics are integer sums over a few MB.
@@ -70,6 +72,20 @@ constexpr int kStatsThreads = 256;
 constexpr int kBinFrames = 12;  // 500 ms at 24 Hz
 constexpr int kStatsMaxLds = 60 * 1024;
 
+// the sample's 500-ms bin counts, cnt[bin][c] (the caller synchronises)
+__device__ __forceinline__ void stage_bin_counts(const float* sp, long long s_t,
+                                                 long long s_c, int C, int nb,
+                                                 unsigned char* cnt) {
+  for (int idx = threadIdx.x; idx < nb * C; idx += kStatsThreads) {
+    const int bin = idx / C, c = idx - bin * C;
+    const float* p = sp + (long long)bin * kBinFrames * s_t + (long long)c * s_c;
+    int n = 0;
+#pragma unroll
+    for (int f = 0; f < kBinFrames; ++f) n += p[f * s_t] != 0.f ? 1 : 0;
+    cnt[idx] = (unsigned char)n;
+  }
+}
+
 __global__ __launch_bounds__(kStatsThreads) void spike_stats_kernel(
     const float* __restrict__ spikes, long long s_b, long long s_t, long long s_c,
     int T, int C, int nb, float duration, float* __restrict__ rates,
@@ -79,14 +95,7 @@ __global__ __launch_bounds__(kStatsThreads) void spike_stats_kernel(
   unsigned char* cnt = lds + (size_t)C * 4;      // [nb][C]
   const int b = blockIdx.x;
   const float* sp = spikes + (long long)b * s_b;
-  for (int idx = threadIdx.x; idx < nb * C; idx += kStatsThreads) {
-    const int bin = idx / C, c = idx - bin * C;
-    const float* p = sp + (long long)bin * kBinFrames * s_t + (long long)c * s_c;
-    int n = 0;
-#pragma unroll
-    for (int f = 0; f < kBinFrames; ++f) n += p[f * s_t] != 0.f ? 1 : 0;
-    cnt[idx] = (unsigned char)n;
-  }
+  stage_bin_counts(sp, s_t, s_c, C, nb, cnt);
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += kStatsThreads) {
     int n = 0;
@@ -114,6 +123,50 @@ __global__ __launch_bounds__(kStatsThreads) void spike_stats_kernel(
       sij += (int)cnt[bin * C + i] * (int)cnt[bin * C + j];
     const long long num = (long long)nb * sij - (long long)sums[i] * sums[j];
     cov[(long long)b * P + p] = (float)((double)num / denom);
+  }
+}
+
+// Pearson correlation of the same bin counts (spike_metrics.
+// correlation_coefficients_exact): num = nb S_ij - S_i S_j and v_i = nb S_ii -
+// S_i^2 are exact 64-bit integers, converted to float64 exactly (< 2^53), then
+//   r_ij = num / sqrt(v_i v_j)
+// -- NaN (0 / 0) where a train's counts do not vary, as np.corrcoef gives.  The
+// full matrix is written; (j, i) is the value of (i, j).
+__global__ __launch_bounds__(kStatsThreads) void spike_corrcoef_kernel(
+    const float* __restrict__ spikes, long long s_b, long long s_t, long long s_c,
+    int C, int nb, double* __restrict__ corr) {
+  extern __shared__ unsigned char lds[];
+  int* sums = reinterpret_cast<int*>(lds);       // [C]
+  unsigned char* cnt = lds + (size_t)C * 4;      // [nb][C]
+  const int b = blockIdx.x;
+  stage_bin_counts(spikes + (long long)b * s_b, s_t, s_c, C, nb, cnt);
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += kStatsThreads) {
+    int n = 0;
+    for (int bin = 0; bin < nb; ++bin) n += cnt[bin * C + c];
+    sums[c] = n;
+  }
+  __syncthreads();
+  const int P = C * (C + 1) / 2;
+  double* out = corr + (long long)b * C * C;
+  for (int p = blockIdx.y * kStatsThreads + threadIdx.x; p < P;
+       p += gridDim.y * kStatsThreads) {
+    int i = 0, rem = p;
+    while (rem >= C - i) { rem -= C - i; ++i; }
+    const int j = i + rem;
+    int sij = 0, sii = 0, sjj = 0;
+    for (int bin = 0; bin < nb; ++bin) {
+      const int ni = cnt[bin * C + i], nj = cnt[bin * C + j];
+      sij += ni * nj;
+      sii += ni * ni;
+      sjj += nj * nj;
+    }
+    const long long num = (long long)nb * sij - (long long)sums[i] * sums[j];
+    const long long vi = (long long)nb * sii - (long long)sums[i] * sums[i];
+    const long long vj = (long long)nb * sjj - (long long)sums[j] * sums[j];
+    const double r = (double)num / sqrt((double)vi * (double)vj);
+    out[(long long)i * C + j] = r;
+    out[(long long)j * C + i] = r;
   }
 }
 
@@ -253,6 +306,23 @@ extern "C" int cg_spike_stats(const float* spikes, int B, int T, int C,
   hipLaunchKernelGGL(spike_stats_kernel, dim3(B, split), dim3(kStatsThreads),
                      (size_t)lds, S_(stream), spikes, s_b, s_t, s_c, T, C, nb,
                      duration, rates, cov);
+  CG_LAUNCH_CHECK();
+}
+
+extern "C" int cg_spike_corrcoef(const float* spikes, int B, int T, int C,
+                                 long long s_b, long long s_t, long long s_c,
+                                 double* corr, void* stream) {
+  if (!spikes || !corr || B < 1 || C < 1 || T < 1) return CG_EINVAL;
+  const int nb = T / kBinFrames;
+  if (nb < 2) return CG_EINVAL;
+  const long long lds = (long long)C * 4 + (long long)nb * C;
+  if (lds > kStatsMaxLds || C > 4096) return CG_EINVAL;
+  const int P = C * (C + 1) / 2;
+  int split = (P + kStatsThreads * 4 - 1) / (kStatsThreads * 4);
+  if (split < 1) split = 1;
+  if (split > 8) split = 8;
+  hipLaunchKernelGGL(spike_corrcoef_kernel, dim3(B, split), dim3(kStatsThreads),
+                     (size_t)lds, S_(stream), spikes, s_b, s_t, s_c, C, nb, corr);
   CG_LAUNCH_CHECK();
 }
 

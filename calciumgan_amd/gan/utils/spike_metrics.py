@@ -3,6 +3,8 @@ installed; they are un-pinned upstream -- PARITY UNPINNED, definitions below
 follow Elephant's documented statistics on binary trains at 24 Hz).
 
 spikes: (neurons, T) arrays of {0,1} at FRAME_RATE frames per second."""
+import math
+
 import numpy as np
 
 from .spike_helper import FRAME_RATE
@@ -93,6 +95,81 @@ def van_rossum_distance(spikes1, spikes2=None, tau=1.0):
   if spikes2 is not None:
     result = result[len(spikes1):, :len(spikes2)]
   return result
+
+
+def van_rossum_gram_frames(spikes, decay):
+  """The summed kernel matrix of `van_rossum_distance` on the frame grid, without
+  the kernel between all pairs of spikes: float64 (n, n)
+    S_ij = sum_{k in i, l in j} decay^|f_k - f_l| = G_ij + G_ji,  G = M' Sp^T
+  with Sp the (n, T) trains and M' the half-weighted causal filter -- per train
+  and frame h = s[t] / 2, m' = fl(fl(decay m) + h), M'[t] = m', m = fl(m' + h),
+  m = 0 before frame 0, every operation rounded to float64 on its own.  The half
+  weights count equal-frame pairs once; the diagonal is S_ii = n_i + 2 sum_{k<l}
+  decay^(f_l - f_k).  O(T n^2) and no memory beyond the trial; the statement
+  cg_van_rossum (csrc/van_rossum.hip) is tested against: its M' are these bits,
+  only the order of the sum over frames differs.  decay 1, 0 and (T <= 40) 0.5
+  make every sum exact."""
+  s = (np.asarray(spikes) != 0).astype(np.float64)
+  assert s.ndim == 2
+  n, T = s.shape
+  a = np.float64(decay)
+  filt = np.empty((n, T), np.float64)
+  m = np.zeros(n, np.float64)
+  for t in range(T):
+    h = 0.5 * s[:, t]
+    mp = a * m
+    mp = mp + h
+    filt[:, t] = mp
+    m = mp + h
+  G = filt @ s.T
+  return G + G.T
+
+
+def van_rossum_decay(tau=1.0):
+  """exp(-1 / (24 tau)): the kernel's decay over one frame, as the host forms it
+  for `van_rossum_distance_frames` and for the device call alike."""
+  return math.exp(-1.0 / (FRAME_RATE * tau))
+
+
+def _distance_from_gram(S):
+  d = np.diag(S)
+  d2 = (d[:, None] + d[None, :]) - 2.0 * S
+  return np.sqrt(np.maximum(d2, 0.0))
+
+
+def van_rossum_distance_frames(spikes1, spikes2=None, tau=1.0):
+  """`van_rossum_distance` from `van_rossum_gram_frames`: D_ij =
+  sqrt(max(fl(fl(S_ii + S_jj) - 2 S_ij), 0)), the same normalisation (one spike
+  against an empty train is at distance 1), the full matrix or the (spikes2 x
+  spikes1) cross block sliced exactly as `van_rossum_distance` slices it."""
+  spikes = np.asarray(spikes1) if spikes2 is None else np.concatenate(
+      [np.asarray(spikes1), np.asarray(spikes2)], 0)
+  result = _distance_from_gram(
+      van_rossum_gram_frames(spikes, van_rossum_decay(tau)))
+  if spikes2 is not None:
+    result = result[len(spikes1):, :len(spikes2)]
+  return result
+
+
+def correlation_coefficients_exact(spikes1, spikes2=None, binsize_ms=500.0):
+  """`correlation_coefficients` from exact integer sums (what cg_spike_corrcoef
+  computes): with the bin counts n_i, S_i = sum n_i, S_ij = sum n_i n_j and nb
+  bins, num = nb S_ij - S_i S_j and v_i = nb S_ii - S_i^2 are 64-bit integers,
+  converted to float64 exactly BEFORE the product v_i v_j (which does not fit in
+  64 bits at large T), and r_ij = num / sqrt(v_i v_j).  NaN where a train's
+  counts do not vary, like np.corrcoef; the diagonal is exactly 1 elsewhere."""
+  spikes = np.asarray(spikes1) if spikes2 is None else np.concatenate(
+      [np.asarray(spikes1), np.asarray(spikes2)], 0)
+  counts = np.atleast_2d(bin_counts(spikes != 0, binsize_ms)).astype(np.int64)
+  nb = counts.shape[-1]
+  sums = counts.sum(-1)
+  num = nb * (counts @ counts.T) - sums[:, None] * sums[None, :]
+  v = np.diag(num).astype(np.float64)
+  with np.errstate(invalid='ignore', divide='ignore'):
+    r = num.astype(np.float64) / np.sqrt(v[:, None] * v[None, :])
+  if spikes2 is not None:
+    r = r[len(spikes1):, :len(spikes2)]
+  return r
 
 
 def victor_purpura_distance(spikes1, spikes2=None, q=1.0):
@@ -205,3 +282,49 @@ def error_sums_device(rates_a, rates_b, covs_a, covs_b):
            nets._p(covs_a), nets._p(covs_b), n_c, nets._p(out), nets._p(ws),
            nets._stream())
   return out
+
+
+# frames per LDS chunk of cg_van_rossum (csrc/van_rossum.hip: kVrChunk) -- the
+# tests put spikes on both sides of every chunk boundary
+VAN_ROSSUM_CHUNK = 16
+
+
+def _trial_batch(spikes):
+  import torch
+  if not (torch.is_tensor(spikes) and spikes.is_cuda and
+          spikes.dtype == torch.float32 and spikes.dim() == 3):
+    raise ValueError('float32 device tensor (B, T, C) expected')
+  return spikes.shape
+
+
+def van_rossum_distance_device(spikes, tau=1.0, return_gram=False):
+  """`van_rossum_distance_frames` of every trial of a batch on the GPU
+  (cg_van_rossum): float32 device tensor (B, T, C) of {0, 1}, any strides, ->
+  float64 device (B, C, C) distances between the trial's neurons; return_gram:
+  (distances, summed kernel matrices S).  The decay exp(-1 / (24 tau)) is formed
+  here on the host.  Symmetric bit for bit, diagonal exactly 0, the same bits
+  every call."""
+  import torch
+  from ... import _lib as hip
+  from ... import nets
+  B, T, C = _trial_batch(spikes)
+  dist = torch.empty(B, C, C, dtype=torch.float64, device=spikes.device)
+  gram = torch.empty_like(dist) if return_gram else None
+  hip.call('cg_van_rossum', nets._p(spikes), B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), van_rossum_decay(tau),
+           nets._p(gram), nets._p(dist), nets._stream())
+  return (dist, gram) if return_gram else dist
+
+
+def correlation_coefficients_device(spikes):
+  """`correlation_coefficients_exact` of every trial of a batch on the GPU
+  (cg_spike_corrcoef): float32 device tensor (B, T, C) of {0, 1}, any strides,
+  -> float64 device (B, C, C); NaN where a train's bin counts do not vary."""
+  import torch
+  from ... import _lib as hip
+  from ... import nets
+  B, T, C = _trial_batch(spikes)
+  corr = torch.empty(B, C, C, dtype=torch.float64, device=spikes.device)
+  hip.call('cg_spike_corrcoef', nets._p(spikes), B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), nets._p(corr), nets._stream())
+  return corr

@@ -13,6 +13,16 @@ the reference's compute_metrics.py (BASELINE configs[3]: recorded-data pipeline
   here)
 
   python compute_metrics.py --output_dir runs/001 [--all_epochs]
+      [--device gpu [--batch_trials 128]]
+
+--device gpu (not a reference flag) takes the deconvolution, the firing rates,
+the per-trial correlations and the van Rossum matrices through the HIP kernels
+(csrc/spikes.hip, csrc/van_rossum.hip) in batches of --batch_trials trials: the
+spike trains written back are the host's byte for byte, the firing rates equal,
+correlations and distances equal to float64 rounding (a value within that of a
+histogram edge may change bins in the KL).  The KL and the heatmap ordering stay
+on the host.  No process pool is created on that path (--num_processors is
+ignored): a pool forked after the GPU is open is not safe.
 
 The KL is the reference's: both samples cut into 30 equal-width bins over their
 pooled range by pandas.cut, empty bins replaced by 1e-10 (:80-111) -- pandas is
@@ -200,6 +210,122 @@ def compute_epoch_spike_metrics(hparams, filename, epoch):
   return out
 
 
+# -- --device gpu ---------------------------------------------------------------
+def _device():
+  import torch
+  return torch.device('cuda', torch.cuda.current_device())
+
+
+def _batches(hparams, array):
+  """float32 device tensors of `batch_trials` trials of an NWC host array."""
+  import torch
+  step = max(int(getattr(hparams, 'batch_trials', 128)), 1)
+  for i in range(0, len(array), step):
+    yield torch.from_numpy(
+        np.ascontiguousarray(array[i:i + step], dtype=np.float32)).to(_device())
+
+
+def deconvolve_from_file_device(hparams, filename):
+  """`deconvolve_from_file` through cg_oasis_ar1_batched, a batch of trials per
+  launch, scale 1 and offset 0: the float32 signals of the file widened to
+  float64 as the host does, so the int8 trains are the host's byte for byte."""
+  if hparams.verbose:
+    print('\tDeconvolve {}'.format(filename))
+  signals = np.asarray(h5_helper.get(filename, name='signals'))
+  if signals.dtype != np.float32:
+    raise ValueError('--device gpu deconvolves float32 signals; {} holds {}'
+                     .format(filename, signals.dtype))
+  signals = utils.set_array_format(signals, 'NWC', hparams)
+  spikes = np.concatenate([
+      spike_helper.deconvolve_signals_device(batch, threshold=0.5).cpu().numpy()
+      for batch in _batches(hparams, signals)]).astype(np.int8)
+  h5_helper.write(filename, {'spikes': spikes})
+  return spikes
+
+
+def trial_statistics_device(hparams, filename):
+  """Of the first num_samples trials of `filename`, on the device: firing rates
+  (n, C) float32 (cg_spike_stats), correlation coefficients and van Rossum
+  distances between the trial's neurons (n, C, C) float64 (cg_spike_corrcoef,
+  cg_van_rossum), brought to the host."""
+  spikes = utils.set_array_format(
+      np.asarray(h5_helper.get(filename, name='spikes')), 'NWC', hparams)
+  rates, corr, dist = [], [], []
+  for batch in _batches(hparams, spikes[:hparams.num_samples]):
+    rates.append(spike_metrics.batch_statistics_device(batch)[0].cpu().numpy())
+    corr.append(spike_metrics.correlation_coefficients_device(batch).cpu().numpy())
+    dist.append(spike_metrics.van_rossum_distance_device(batch).cpu().numpy())
+  return dict(rates=np.concatenate(rates), correlation=np.concatenate(corr),
+              van_rossum=np.concatenate(dist))
+
+
+def neuron_van_rossum_blocks_device(hparams, filename, neurons, num_trials=45):
+  """The recorded x synthetic blocks of `neuron_van_rossum` before sorting, one
+  launch for all chosen neurons: their first trials from both files side by side
+  as the trains of a (len(neurons), T, 2 num_trials) batch, the cross block
+  sliced as the host slices it."""
+  import torch
+  sides = []
+  for f in (hparams.validation_cache, filename):
+    spikes = utils.set_array_format(
+        np.asarray(h5_helper.get(f, name='spikes')), 'NWC', hparams)
+    # (trials, T, neurons) -> (neurons, T, trials)
+    sides.append(spikes[:num_trials][:, :, list(neurons)].transpose(2, 1, 0))
+  n_real, n_fake = sides[0].shape[2], sides[1].shape[2]
+  batch = torch.from_numpy(np.ascontiguousarray(
+      np.concatenate(sides, axis=2), dtype=np.float32)).to(_device())
+  dist = spike_metrics.van_rossum_distance_device(batch).cpu().numpy()
+  return dist[:, n_real:, :n_fake]
+
+
+def device_pairs(hparams, filename):
+  """The (recorded, synthetic) samples behind the three KL figures, from the
+  device statistics: per neuron the firing rates over the trials, per trial the
+  upper triangles of the correlation and van Rossum matrices."""
+  real = getattr(hparams, '_recorded_statistics', None)
+  if real is None:  # the validation set is the same for every epoch
+    real = hparams._recorded_statistics = trial_statistics_device(
+        hparams, hparams.validation_cache)
+  fake = trial_statistics_device(hparams, filename)
+  n = hparams.num_neurons
+  iu = np.triu_indices(n, k=1)
+  trials = range(min(len(real['rates']), len(fake['rates'])))
+  return dict(
+      firing_rate=[(real['rates'][:, c], fake['rates'][:, c]) for c in range(n)],
+      correlation=[(_upper(real['correlation'][i], n),
+                    _upper(fake['correlation'][i], n)) for i in trials],
+      van_rossum=[(real['van_rossum'][i][iu], fake['van_rossum'][i][iu])
+                  for i in trials])
+
+
+def compute_epoch_spike_metrics_device(hparams, filename, epoch):
+  """`compute_epoch_spike_metrics` with the statistics from the device; the KL
+  and `sort_heatmap` on the host as there."""
+  if not h5_helper.contains(filename, 'spikes'):
+    deconvolve_from_file_device(hparams, filename)
+  pairs = device_pairs(hparams, filename)
+  out = {}
+  kl = pairs_kl_divergence(pairs['firing_rate'])
+  out['firing_rate_kl'] = dict(
+      mean=float(np.mean(kl)),
+      neurons={int(n): float(kl[n]) for n in hparams.neurons})
+  if hparams.verbose:
+    print('\tfiring rate        KL mean: {:.04f}'.format(np.mean(kl)))
+  kl = pairs_kl_divergence(pairs['correlation'])
+  out['correlation_kl'] = dict(mean=float(np.mean(kl)))
+  if hparams.verbose:
+    print('\tcorrelation        KL mean: {:.04f}'.format(np.mean(kl)))
+  blocks = neuron_van_rossum_blocks_device(hparams, filename, hparams.neurons, 45)
+  out['van_rossum_heatmap_min'] = {
+      int(n): float(np.nanmin(sort_heatmap(b)[0]))
+      for n, b in zip(hparams.neurons, blocks)}
+  kl = pairs_kl_divergence(pairs['van_rossum'])
+  out['van_rossum_kl'] = dict(mean=float(np.mean(kl)))
+  if hparams.verbose:
+    print('\tvan Rossum         KL mean: {:.04f}'.format(np.mean(kl)))
+  return out
+
+
 def main(hparams):
   """compute_metrics.py:500-542."""
   if not os.path.exists(hparams.output_dir):
@@ -228,8 +354,11 @@ def main(hparams):
     start = time()
     if hparams.verbose:
       print('\nCompute metrics for {}'.format(info[epoch]['filename']))
-    report[int(epoch)] = compute_epoch_spike_metrics(
-        hparams, filename=info[epoch]['filename'], epoch=epoch)
+    compute = (compute_epoch_spike_metrics_device
+               if getattr(hparams, 'device', 'cpu') == 'gpu' else
+               compute_epoch_spike_metrics)
+    report[int(epoch)] = compute(hparams, filename=info[epoch]['filename'],
+                                 epoch=epoch)
     report[int(epoch)]['elapse'] = time() - start
     with open(os.path.join(hparams.output_dir, 'scalars.jsonl'), 'a') as f:
       f.write(json.dumps({'tag': 'elapse/spike_metrics',
@@ -252,6 +381,10 @@ def build_parser():
   parser.add_argument('--format', default='pdf', choices=['pdf', 'png'])
   parser.add_argument('--verbose', default=1, type=int)
   parser.add_argument('--seed', default=12, type=int)
+  parser.add_argument('--device', default='cpu', choices=['cpu', 'gpu'],
+                      help='gpu: deconvolution and statistics on the device')
+  parser.add_argument('--batch_trials', default=128, type=int,
+                      help='--device gpu: trials per launch')
   return parser
 
 

@@ -680,6 +680,46 @@ int cg_spike_stats_error(const float* fr_a, const float* fr_b, long long n_fr,
                          const float* cov_a, const float* cov_b, long long n_cov,
                          float* out /*[4]*/, float* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Per-trial correlations and van Rossum distances of the recorded-data report
+ * (compute_metrics.py:306-480 of the reference, which takes them from Elephant
+ * on the host; here compute_metrics.py --device gpu).  Functions added under
+ * ABI 20; the same in both precision builds (nothing here touches an
+ * activation type).  Strides in elements, as for cg_spike_stats: a (B, T, C)
+ * batch inside a pitch-128 buffer and a (rows, T) array are read in place;
+ * a frame counts as a spike when it is != 0.
+ * ------------------------------------------------------------------------- */
+/* Summed kernel matrix and van Rossum distances between the C trains of every
+ * sample, on the 24-Hz frame grid (van_rossum.hip; the numpy statement is
+ * spike_metrics.van_rossum_gram_frames / van_rossum_distance_frames):
+ *   gram[b][i][j] = S_ij = sum_{k in i, l in j} decay^|f_k - f_l|
+ *                 = G_ij + G_ji, G = M' Sp^T, M' the half-weighted causal filter
+ *                   h = s[t] / 2; m' = fl(fl(decay m) + h); M'[t] = m'; m = fl(m' + h)
+ *                   (each operation rounded to float64 on its own, m = 0 first)
+ *   dist[b][i][j] = sqrt(max(fl(fl(S_ii + S_jj) - 2 S_ij), 0))
+ * with decay = exp(-1 / (24 tau)) formed by the caller.  The products run on
+ * v_mfma_f64_16x16x4_f64: M' is the statement's bit for bit, only the order of
+ * the sum over frames belongs to the matrix pipe (decay 1, 0 and, while T <= 40,
+ * 0.5 make every sum exact).  Both outputs are symmetric bit for bit, the
+ * diagonal of dist is exactly 0, and the same input gives the same bits every
+ * call (no atomics, no scratch memory, nothing zeroed beforehand).
+ * gram / dist: float64 [B][C][C]; either may be NULL, not both.
+ * CG_EINVAL (nothing launched): a NULL spikes, both outputs NULL, B, T or C < 1,
+ * T > 2^24, C > 4096, decay outside [0, 1] (NaN included). */
+int cg_van_rossum(const float* spikes, int B, int T, int C, long long s_b,
+                  long long s_t, long long s_c, double decay, double* gram,
+                  double* dist, void* stream);
+/* Pearson correlation of the 500-ms bin counts (12 frames per bin, a trailing
+ * partial bin dropped, nb = T / 12) between the C trains of every sample
+ * (spike_metrics.correlation_coefficients_exact): with the exact integer sums
+ * S_i = sum n_i, S_ij = sum n_i n_j kept in 64 bits,
+ *   num = nb S_ij - S_i S_j, v_i = nb S_ii - S_i^2, r_ij = num / sqrt(v_i v_j)
+ * (num, v_i, v_j converted to float64 before the product).  NaN where a train's
+ * counts do not vary, as np.corrcoef gives.  corr: float64 [B][C][C], symmetric
+ * bit for bit.  CG_EINVAL as cg_spike_stats: nb < 2, or 4 C + nb C > 60 KiB. */
+int cg_spike_corrcoef(const float* spikes, int B, int T, int C, long long s_b,
+                      long long s_t, long long s_c, double* corr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
