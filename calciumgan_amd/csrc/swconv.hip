@@ -1162,8 +1162,11 @@ static int swconv_run(const cg_conv_desc* d, void* stream) {
   const int R = d->stride;
   if (d->tile < 0 || d->tile >= CG_NUM_TILES) return CG_EINVAL;
   const TileCfg tc = kTileCfgs[d->tile];
+  // (side == NULL: the folded fix-up of the 32-row software-pipelined tiles;
+  // swconv_swp_launch holds its conditions)
   if (d->out_shifts &&
-      (d->out_f32 || d->rowsumsq || d->out_seg_size < 1 || !d->side ||
+      (d->out_f32 || d->rowsumsq || d->out_seg_size < 1 ||
+       (!d->side && !tc.swp_wm) ||
        d->side_rows < 1 || d->epilogue == CG_EPI_LN_LRELU ||
        d->epilogue == CG_EPI_SIGMOID || d->epilogue == CG_EPI_LRELU))
     return CG_EINVAL;

@@ -1175,6 +1175,120 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
             masked8(v, mk[mt][p], true);
             store_rows(finish8(v, nl0 + p * 32), ry, vo[p], mt);
           }
+      } else if (a.side == nullptr) {
+        // Folded form (cg_conv_desc.side == NULL; two phases, rows t = 2 u + phase,
+        // Lu a multiple of the wave's 16 MT rows and side_rows < 16 MT: checked on
+        // the host).  A reflected row t' and the direct row t whose target it is
+        // folded onto are mirrors: t + t' = 2 (Ly - 1 - s) for s > 0, 2 |s| for
+        // s < 0 -- the same parity, so the same phase, tile and column, and both
+        // among the last (first) |s| + 1 rows of the sample in that phase: the
+        // same WAVE.  The lane of the direct row fetches the side value from its
+        // partner lane and stores what cg_unshuffle_fixup would have left:
+        //   round(float(round(round(v + bias) mf)) + float(side) mf).
+        // No side buffer, no second launch, no other workgroup involved.
+        static_assert(MT == 2 || EPI != kEpiMaskShift,
+                      "the partner's subtile is one of two");
+        const __amdgpu_buffer_rsrc_t ry =
+            rsrc_at(a.y, ((long long)bw * a.Ly * a.Cy) * 2);
+        const __amdgpu_buffer_rsrc_t rm =
+            rsrc_at(a.mask, ((long long)bw * a.Ly * a.Cy) * 2);
+        // wave rows i = mt 16 + rM hold t = t0 + 2 i: partners have i + i' = kmir
+        const int kmir = (oshift > 0 ? a.Ly - 1 - oshift : -oshift) - t0;
+        // (one block pair at a time, its bias re-read from LDS and a scheduling
+        // barrier behind it: with both pairs' masks, biases and side values live
+        // at once this path, not the K loop, set the kernel's register count)
+        int padr[MT];
+        bool fold[MT], phi[MT], direct[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          const int i = mt * 16 + rM;
+          const int t = t0 + 2 * i;
+          const int ip = kmir - i;
+          const int tp = t0 + 2 * ip;
+          const bool to_side = oshift > 0 ? t >= a.Ly - oshift : t < -oshift;
+          const bool p_side = oshift > 0 ? tp >= a.Ly - oshift : tp < -oshift;
+          direct[mt] = !to_side;
+          fold[mt] = !to_side && ip >= 0 && ip < 16 * MT && p_side;
+          phi[mt] = (ip & 16) != 0;
+          padr[mt] = ((lane & 48) | (ip & 15)) * 4;  // same g, row ip & 15
+        }
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const int n = nl0 + p * 32;
+          const bool ok = !(cols_open && n >= a.Cy);
+          int vy[MT];
+          u32x4 mk[MT];
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            const int r = t0 + 2 * (mt * 16 + rM) + oshift;  // the direct row's target
+            vy[mt] = (ok && direct[mt]) ? r * rowB + n * 2 : kOff;
+            mk[mt] = __builtin_amdgcn_raw_buffer_load_b128(rm, vy[mt], 0, 0);
+          }
+          float bp[8];
+          {
+            const f32x4 b0v = *reinterpret_cast<const f32x4*>(bias_lds + n);
+            const f32x4 b1v = *reinterpret_cast<const f32x4*>(bias_lds + n + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              bp[e] = b0v[e];
+              bp[4 + e] = b1v[e];
+            }
+          }
+          // the side values of both subtiles, as the side buffer would hold them
+          u32x4 sd[MT];
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            float v[8];
+            pair8(mt, p, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += bp[e];
+            sd[mt] = finish8(v, n);
+          }
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            float v[8];
+            pair8(mt, p, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += bp[e];
+            masked8(v, mk[mt], true);
+            const u32x4 d = finish8(v, n);
+            const u32x4 h4 = mk[mt];
+            u32x4 o4;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              // (the partner's subtile is not compile-time: fetch both, select)
+              const uint32_t s0 = (uint32_t)__builtin_amdgcn_ds_bpermute(
+                  padr[mt], (int)sd[0][q]);
+              const uint32_t s1 = (uint32_t)__builtin_amdgcn_ds_bpermute(
+                  padr[mt], (int)sd[1][q]);
+              const uint32_t sw = phi[mt] ? s1 : s0;
+              const float mlo = act_lo(h4[q]) > 0.f ? 1.f : a.alpha;
+              const float mhi = act_hi(h4[q]) > 0.f ? 1.f : a.alpha;
+              // (one fused multiply-add, as cg_unshuffle_fixup's dv += sv * mf)
+              const uint32_t f = pack2act(__builtin_fmaf(act_lo(sw), mlo, act_lo(d[q])),
+                                          __builtin_fmaf(act_hi(sw), mhi, act_hi(d[q])));
+              o4[q] = fold[mt] ? f : d[q];
+            }
+            __builtin_amdgcn_raw_buffer_store_b128(o4, ry, vy[mt], 0, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        // the |s| rows nothing maps to -- [0, s) for s > 0, [Ly - |s|, Ly) for
+        // s < 0 -- from the same edge waves.  |s| = 1 has an edge wave in ONE phase
+        // only (phase 1 for s > 0, phase 0 for s < 0), so phase 1 takes the even
+        // rows of [0, s) and phase 0 the odd rows of [Ly - |s|, Ly)
+        {
+          const int ph = t0 & 1;
+          const int rz = oshift > 0 ? 2 * rM + 1 - ph : a.Ly - 1 - ph - 2 * rM;
+          const bool zr = oshift > 0 ? rz < oshift : rz >= a.Ly + oshift;
+#pragma unroll
+          for (int p = 0; p < 2; ++p) {
+            const bool ok = !(cols_open && nl0 + p * 32 >= a.Cy);
+            __builtin_amdgcn_raw_buffer_store_b128(
+                u32x4{0u, 0u, 0u, 0u}, ry,
+                (ok && zr) ? rz * rowB + (nl0 + p * 32) * 2 : kOff, 0, 0);
+          }
+        }
       } else {
         // the one or two waves per sample whose rows reach the reflected end:
         // per-lane targets, one store instruction per destination buffer
@@ -1490,7 +1604,18 @@ int swconv_swp_launch(const ConvArgs& a, int stride, int wm, int wn, int mt,
   // lean epilogue forms: the 32-row wave tiles (what the tuner picks for nearly
   // every cfg2 geometry), bf16 rows, no split-K / f32 output / penalty norm
   int epi = kEpiGeneric;
-  if (mt == 2 && !a.out_f32 && ksplit <= 1 && g_swp_lean_epi) {
+  // out_shifts without a side buffer: the folded PhaseShuffle fix-up, which only
+  // kEpiMaskShift carries (whatever the development switch says) and only where
+  // a reflected row and its target meet in one wave: two phases interleaved
+  // (rows 2 u + phase), whole 32-row waves per sample and phase, |shift| < 32
+  const bool folded = a.out_shifts && !a.side;
+  if (folded &&
+      (mt != 2 || stride != 1 || a.out_f32 || ksplit > 1 || a.rowsumsq ||
+       a.row_scale || a.epilogue != CG_EPI_MASK || a.gp != 2 || a.y_stride != 2 ||
+       a.y_off != 0 || a.yoff_phase_step != 1 || a.Ly != 2 * a.Lu ||
+       a.Lu % (16 * mt) || a.side_rows < 1 || a.side_rows + 1 > 16 * mt))
+    return CG_EINVAL;
+  if (mt == 2 && !a.out_f32 && ksplit <= 1 && (g_swp_lean_epi || folded)) {
     if ((a.epilogue == CG_EPI_NONE || a.epilogue == CG_EPI_LRELU) &&
         !a.out_shifts && !a.row_scale) {
       epi = a.rowsumsq ? kEpiLreluSsq : kEpiLrelu;
@@ -1506,6 +1631,7 @@ int swconv_swp_launch(const ConvArgs& a, int stride, int wm, int wn, int mt,
     // (stride 1 carries the two forms its launches use, stride 2 likewise)
     if (stride == 1 && epi == kEpiMask) epi = kEpiGeneric;
   }
+  if (folded && epi != kEpiMaskShift) return CG_EINVAL;
 #define CG_SWP_E(RR, WM, WN, MM, NN, EE)                                     \
   if (stride == RR && wm == WM && wn == WN && mt == MM && narrow == NN &&    \
       epi == EE)                                                             \

@@ -429,6 +429,10 @@ _SPLIT_WS = {}
 # CALCIUMGAN_FUSE_UNSHUFFLE=0: cg_unshuffle_mask as its own pass after every
 # input-gradient launch of the critic
 _FUSE_UNSHUFFLE = _flag('FUSE_UNSHUFFLE')
+# CALCIUMGAN_FOLD_FIXUP=0: the reflected rows of that epilogue through a side
+# buffer and cg_unshuffle_fixup (one more launch per layer) instead of folded in
+# by the input-gradient launch itself (cg_conv_desc.side == NULL)
+_FOLD_FIXUP = _flag('FOLD_FIXUP')
 # CALCIUMGAN_FUSE_LN=0 keeps LayerNorm a separate pass (A/B, debugging)
 _FUSE_LN = _flag('FUSE_LN')
 
@@ -912,9 +916,12 @@ class _DisPlan(object):
     # PhaseShuffle adjoint + LeakyReLU' mask in the input-gradient launch's
     # epilogue (rows stored at their source positions, masked there) when the
     # reflected and the empty rows of a sample cannot coincide; the at most m
-    # reflected rows per sample go through `side` and cg_unshuffle_fixup
+    # reflected rows per sample are folded in by the launch itself where the
+    # library admits that form (side == NULL), else they go through `side` and
+    # cg_unshuffle_fixup
     m = max(1, int(net.hp.m))
     self.side = {}
+    self.folded = set()  # layers whose launch needs nothing behind it
     for i in range(len(net.layers) - 1, 0, -1):
       lay = net.layers[i]
       fused = _FUSE_UNSHUFFLE and 2 * m + 1 <= lay.lin
@@ -925,9 +932,18 @@ class _DisPlan(object):
         extra = dict(mask_src=ws.act[i], epilogue=_lib.EPI_MASK,
                      out_shifts=(self.shifts[i - 1], seg_size, self.side[i], m),
                      alpha=net.alpha)
-      self.dgrad.append(
-          (i, net.convs[i].up(ws.delta[i + 1], net.w_dgrad[i],
-                              ws.delta[i] if fused else ws.e[i], nB, **extra)))
+      d = net.convs[i].up(ws.delta[i + 1], net.w_dgrad[i],
+                          ws.delta[i] if fused else ws.e[i], nB, **extra)
+      if fused and _FOLD_FIXUP and ws.delta[i].is_cuda:
+        # the same launch (tile included) without the side buffer, if admitted
+        side_ptr, d.side = d.side, None
+        if _lib.load().cg_swconv_check(ctypes.byref(d)) == 0:
+          side_t = self.side.pop(i)  # no side tensor, no cg_unshuffle_fixup
+          self.folded.add(i)
+          d._keep = tuple(t for t in d._keep if t is not side_t)
+        else:
+          d.side = side_ptr
+      self.dgrad.append((i, d))
     # layer 1 over [real | fake] only + cg_lrelu_mix for the x^ segment (_L1_LINEAR)
     self.fwd_l1_pair = None
     if (_L1_LINEAR and self.nseg == 3 and nB == 3 * seg_size and
@@ -1063,6 +1079,8 @@ class _DisPlan(object):
     for i, d in self.dgrad:
       _run_conv(d, st)
       lay = net.layers[i - 1]
+      if i in self.folded:
+        continue
       if i in self.side:
         side = self.side[i]
         _lib.call('cg_unshuffle_fixup', _p(side), _p(ws.act[i]),

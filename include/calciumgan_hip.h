@@ -180,12 +180,23 @@ typedef struct cg_conv_desc {
    * on the reflected branch (at most |shift| per sample) go unmasked to
    * side[b][j] and are folded in by cg_unshuffle_fixup, which also zeroes the
    * |shift| rows nothing maps to.  NULL: rows are stored where they are
-   * computed.  bf16 output only. */
+   * computed.  bf16 output only.
+   * side == NULL with out_shifts: the folded form -- the launch itself adds each
+   * reflected row onto its target and zeroes the empty rows, y ends up bit for
+   * bit what the launch with `side` followed by cg_unshuffle_fixup leaves, and
+   * there is no side buffer and no second launch.  A reflected row and the
+   * direct row of its target are mirrors of equal parity among the first / last
+   * |shift| + 1 rows of their phase, i.e. registers of one wave; so it is
+   * admitted only where that holds: CG_EPI_MASK on the software-pipelined tiles
+   * with 32-row waves (CG_TILE_SWP_128x64, _256x64_W8, _128x128_W8), stride 1,
+   * two interleaved phases (y_stride 2, y_off 0, yoff_phase_step 1, Ly = 2 Lu),
+   * Lu % 32 == 0, side_rows (still the bound on |shift|) <= 31, no row_scale.
+   * CG_EINVAL everywhere else. */
   int w_narrow_last;    /* `w` was packed with narrow_last = 1 (stride 2,
                            w_parity_major, CK == 32) */
   const int* out_shifts;
   int out_seg_size;
-  void* side;           /* bf16 [nB][side_rows][Cy] */
+  void* side;           /* bf16 [nB][side_rows][Cy]; NULL: the folded form */
   int side_rows;        /* >= max |shift| */
   /* Split-K for launches with few output tiles (the penalty's tangent chain:
    * one 128-sample segment): ksplit > 1 workgroups share an output tile, each
