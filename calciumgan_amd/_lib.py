@@ -194,12 +194,17 @@ SIGNATURES = {
     'cg_van_rossum': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_d, c_vp, c_vp,
                       c_vp],
     'cg_spike_corrcoef': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_vp, c_vp],
+    # victor_purpura.hip: the edit distances between the trains of a trial
+    'cg_victor_purpura_ws_bytes': [c_i, c_i, c_i],
+    'cg_victor_purpura': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_d, c_vp, c_vp,
+                          c_ll, c_vp],
 }
 _RESTYPES = {'cg_packed_elems': c_ll, 'cg_pack_plan_bytes': c_ll,
              'cg_pack_plan_build': c_ll, 'cg_wgrad_partials_elems': c_ll,
              'cg_dense_wgrad_ws_elems': c_ll, 'cg_rowsumsq_ws_elems': c_ll,
              'cg_reduce_ws_elems': c_ll, 'cg_wgrad_flex_plan': c_ll,
-             'cg_oasis_ws_bytes': c_ll, 'cg_spike_stats_error_ws_elems': c_ll}
+             'cg_oasis_ws_bytes': c_ll, 'cg_spike_stats_error_ws_elems': c_ll,
+             'cg_victor_purpura_ws_bytes': c_ll}
 
 _libs = {}       # precision -> ctypes handle
 _active = 'bf16'  # precision of the library `call` / `load()` address

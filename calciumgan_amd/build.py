@@ -14,7 +14,8 @@ LIB = os.path.join(CSRC, 'libcalciumgan_hip.so')
 # the same sources with fp16 activations (-DCG_ACT_F16=1): mixed_float16 mode
 LIB_F16 = os.path.join(CSRC, 'libcalciumgan_hip_f16.so')
 SOURCES = ['swconv.hip', 'swconv_swp.hip', 'wgrad.hip', 'pointwise.hip',
-           'dense_rows.hip', 'spikes.hip', 'van_rossum.hip']
+           'dense_rows.hip', 'spikes.hip', 'van_rossum.hip',
+           'victor_purpura.hip']
 HEADERS = ['cg_common.h', 'swconv_args.h', 'oasis_flat.h',
            os.path.join('..', '..', 'include', 'calciumgan_hip.h')]
 

@@ -198,6 +198,78 @@ def victor_purpura_distance(spikes1, spikes2=None, q=1.0):
   return result
 
 
+
+def victor_purpura_cost(q=1.0):
+  """q / 24: the cost of shifting a spike by one frame, as the host forms it for
+  `victor_purpura_distance_frames` and for the device call alike."""
+  return float(q) / FRAME_RATE
+
+
+def victor_purpura_distance_frames(spikes1, spikes2=None, q=1.0):
+  """`victor_purpura_distance` on the frame grid, in float64, every operation
+  rounded on its own: with f_i the ascending frame indices of the non-zero
+  entries of train i, n_i their number and qf = victor_purpura_cost(q),
+    G[k][0] = k, G[0][l] = l,
+    G[k][l] = min(G[k-1][l] + 1, G[k][l-1] + 1,
+                  G[k-1][l-1] + fl(qf |f_a[k-1] - f_b[l-1]|)),   D_ab = G[n_a][n_b]
+  (the frame difference an exact integer).  `victor_purpura_distance` forms
+  q |t_k - t_l| from times in seconds instead: the two agree to rounding.  The
+  statement cg_victor_purpura (csrc/victor_purpura.hip) is tested against bit
+  for bit -- the programme only adds and takes minima of non-NaN values, so the
+  order in which the cells are visited does not matter.  Here all pairs of the
+  trial go through one sweep over the anti-diagonals k + l = d, padded to the
+  longest train (the padding never feeds a cell that counts) and sorted so that
+  the pairs still short of their last diagonal n_a + n_b are a prefix.  The full
+  matrix (symmetric, diagonal 0), or the (spikes2 x spikes1) cross block sliced
+  exactly as `victor_purpura_distance` slices it."""
+  spikes = np.asarray(spikes1) if spikes2 is None else np.concatenate(
+      [np.asarray(spikes1), np.asarray(spikes2)], 0)
+  s = spikes != 0
+  assert s.ndim == 2
+  n = len(s)
+  qf = victor_purpura_cost(q)
+  counts = s.sum(1).astype(np.int64)
+  N = int(counts.max()) if n else 0
+  result = np.zeros((n, n), np.float64)
+  I, J = np.triu_indices(n, k=1)
+  if len(I):
+    order = np.argsort(-(counts[I] + counts[J]), kind='stable')
+    I, J = I[order], J[order]
+    na, total = counts[I], counts[I] + counts[J]
+    frames = np.zeros((n, max(N, 1)), np.int64)
+    for i, train in enumerate(s):
+      frames[i, :counts[i]] = np.nonzero(train)[0]
+    A = frames[I]                  # A[p, k - 1] = f_a[k - 1]
+    Brev = frames[J][:, ::-1]      # Brev[p, N - l] = f_b[l - 1]
+    # pairs with n_a + n_b >= d: the first m_ge[d]
+    m_ge = np.bincount(total, minlength=2 * N + 2)[::-1].cumsum()[::-1]
+    out = np.zeros(len(I), np.float64)
+    # g[p, k] = G[k][d - k] of pair p on the diagonal d; d = 0: G[0][0] = 0
+    g1 = np.zeros((len(I), N + 1), np.float64)
+    g2 = None
+    for d in range(1, int(total[0]) + 1):
+      m = int(m_ge[d])
+      g = np.empty((m, N + 1), np.float64)
+      if d <= N:
+        g[:, 0] = d
+        g[:, d] = d
+      k0, k1 = max(1, d - N), min(N, d - 1)
+      if k0 <= k1:
+        up = g1[:m, k0 - 1:k1] + 1.0
+        left = g1[:m, k0:k1 + 1] + 1.0
+        df = np.abs(A[:m, k0 - 1:k1] - Brev[:m, N - d + k0:N - d + k1 + 1])
+        shift = g2[:m, k0 - 1:k1] + qf * df.astype(np.float64)
+        g[:, k0:k1 + 1] = np.minimum(np.minimum(up, left), shift)
+      last = int(m_ge[d + 1])      # pairs [last, m) end on this diagonal
+      out[last:m] = g[np.arange(last, m), na[last:m]]
+      g2, g1 = g1, g
+    result[I, J] = out
+    result[J, I] = out
+  if spikes2 is not None:
+    result = result[len(spikes1):, :len(spikes2)]
+  return result
+
+
 # -- a batch of trials at once: the statistics compute_dg_metrics.py reports ----
 def batch_statistics(spikes):
   """(rates (B, C), covariances (B, C (C + 1) / 2)) float32 of a batch of binary
@@ -328,3 +400,25 @@ def correlation_coefficients_device(spikes):
   hip.call('cg_spike_corrcoef', nets._p(spikes), B, T, C, spikes.stride(0),
            spikes.stride(1), spikes.stride(2), nets._p(corr), nets._stream())
   return corr
+
+
+def victor_purpura_distance_device(spikes, q=1.0):
+  """`victor_purpura_distance_frames` of every trial of a batch on the GPU
+  (cg_victor_purpura): float32 device tensor (B, T, C), non-zero a spike, any
+  strides, -> float64 device (B, C, C), the statement's bits.  The cost q / 24
+  of a frame is formed here on the host; the workspace (frame indices, counts
+  and boundary columns) is allocated per call and needs no initialisation.  No
+  host synchronisation."""
+  import torch
+  from ... import _lib as hip
+  from ... import nets
+  B, T, C = _trial_batch(spikes)
+  nbytes = hip.load().cg_victor_purpura_ws_bytes(B, T, C)
+  if nbytes < 0:
+    raise ValueError('cg_victor_purpura: unsupported shape {}'.format((B, T, C)))
+  ws = torch.empty(nbytes, dtype=torch.uint8, device=spikes.device)
+  dist = torch.empty(B, C, C, dtype=torch.float64, device=spikes.device)
+  hip.call('cg_victor_purpura', nets._p(spikes), B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), victor_purpura_cost(q),
+           nets._p(dist), nets._p(ws), nbytes, nets._stream())
+  return dist

@@ -13,7 +13,7 @@ the reference's compute_metrics.py (BASELINE configs[3]: recorded-data pipeline
   here)
 
   python compute_metrics.py --output_dir runs/001 [--all_epochs]
-      [--device gpu [--batch_trials 128]]
+      [--device gpu [--batch_trials 128]] [--victor_purpura [--vp_q 1.0]]
 
 --device gpu (not a reference flag) takes the deconvolution, the firing rates,
 the per-trial correlations and the van Rossum matrices through the HIP kernels
@@ -23,6 +23,14 @@ correlations and distances equal to float64 rounding (a value within that of a
 histogram edge may change bins in the KL).  The KL and the heatmap ordering stay
 on the host.  No process pool is created on that path (--num_processors is
 ignored): a pool forked after the GPU is open is not safe.
+
+--victor_purpura (not a reference flag either; absent from the namespace unless
+given) adds `victor_purpura_kl`, built exactly as `van_rossum_kl` from the
+Victor-Purpura distances (cost --vp_q per second of shift) between the neurons
+of a trial: spike_metrics.victor_purpura_distance_frames on the host,
+cg_victor_purpura (csrc/victor_purpura.hip) on the device.  The two hold the
+same bits, so both devices report the same figure.  Without the flag nothing is
+computed or written beyond what was before.
 
 The KL is the reference's: both samples cut into 30 equal-width bins over their
 pooled range by pandas.cut, empty bins replaced by 1e-10 (:80-111) -- pandas is
@@ -145,6 +153,17 @@ def trial_van_rossum(hparams, filename, trial):
   return tuple(out)
 
 
+def trial_victor_purpura(hparams, filename, trial):
+  """`trial_van_rossum` for the Victor-Purpura distances (--victor_purpura)."""
+  out = []
+  for f in (hparams.validation_cache, filename):
+    d = spike_metrics.victor_purpura_distance_frames(
+        _spikes(hparams, f, 'CW', trial=trial), q=getattr(hparams, 'vp_q', 1.0))
+    out.append(d[np.triu_indices(len(d), k=1)])
+  assert out[0].shape == out[1].shape
+  return tuple(out)
+
+
 def sort_heatmap(matrix):
   """:361-386: rows / columns reordered so that the minimum sits top left --
   columns by the row holding the global minimum, then for every column in turn
@@ -207,6 +226,11 @@ def compute_epoch_spike_metrics(hparams, filename, epoch):
   out['van_rossum_kl'] = dict(mean=float(np.mean(kl)))
   if hparams.verbose:
     print('\tvan Rossum         KL mean: {:.04f}'.format(np.mean(kl)))
+  if getattr(hparams, 'victor_purpura', False):
+    kl = pairs_kl_divergence(_map(hparams, trial_victor_purpura, trials))
+    out['victor_purpura_kl'] = dict(mean=float(np.mean(kl)))
+    if hparams.verbose:
+      print('\tVictor-Purpura     KL mean: {:.04f}'.format(np.mean(kl)))
   return out
 
 
@@ -247,16 +271,23 @@ def trial_statistics_device(hparams, filename):
   """Of the first num_samples trials of `filename`, on the device: firing rates
   (n, C) float32 (cg_spike_stats), correlation coefficients and van Rossum
   distances between the trial's neurons (n, C, C) float64 (cg_spike_corrcoef,
-  cg_van_rossum), brought to the host."""
+  cg_van_rossum), brought to the host; with --victor_purpura the Victor-Purpura
+  distances (cg_victor_purpura) as well."""
   spikes = utils.set_array_format(
       np.asarray(h5_helper.get(filename, name='spikes')), 'NWC', hparams)
-  rates, corr, dist = [], [], []
+  rates, corr, dist, vp = [], [], [], []
   for batch in _batches(hparams, spikes[:hparams.num_samples]):
     rates.append(spike_metrics.batch_statistics_device(batch)[0].cpu().numpy())
     corr.append(spike_metrics.correlation_coefficients_device(batch).cpu().numpy())
     dist.append(spike_metrics.van_rossum_distance_device(batch).cpu().numpy())
-  return dict(rates=np.concatenate(rates), correlation=np.concatenate(corr),
-              van_rossum=np.concatenate(dist))
+    if getattr(hparams, 'victor_purpura', False):
+      vp.append(spike_metrics.victor_purpura_distance_device(
+          batch, q=getattr(hparams, 'vp_q', 1.0)).cpu().numpy())
+  stats = dict(rates=np.concatenate(rates), correlation=np.concatenate(corr),
+               van_rossum=np.concatenate(dist))
+  if vp:
+    stats['victor_purpura'] = np.concatenate(vp)
+  return stats
 
 
 def neuron_van_rossum_blocks_device(hparams, filename, neurons, num_trials=45):
@@ -290,12 +321,16 @@ def device_pairs(hparams, filename):
   n = hparams.num_neurons
   iu = np.triu_indices(n, k=1)
   trials = range(min(len(real['rates']), len(fake['rates'])))
-  return dict(
+  pairs = dict(
       firing_rate=[(real['rates'][:, c], fake['rates'][:, c]) for c in range(n)],
       correlation=[(_upper(real['correlation'][i], n),
                     _upper(fake['correlation'][i], n)) for i in trials],
       van_rossum=[(real['van_rossum'][i][iu], fake['van_rossum'][i][iu])
                   for i in trials])
+  if 'victor_purpura' in fake:
+    pairs['victor_purpura'] = [(real['victor_purpura'][i][iu],
+                                fake['victor_purpura'][i][iu]) for i in trials]
+  return pairs
 
 
 def compute_epoch_spike_metrics_device(hparams, filename, epoch):
@@ -323,6 +358,11 @@ def compute_epoch_spike_metrics_device(hparams, filename, epoch):
   out['van_rossum_kl'] = dict(mean=float(np.mean(kl)))
   if hparams.verbose:
     print('\tvan Rossum         KL mean: {:.04f}'.format(np.mean(kl)))
+  if 'victor_purpura' in pairs:
+    kl = pairs_kl_divergence(pairs['victor_purpura'])
+    out['victor_purpura_kl'] = dict(mean=float(np.mean(kl)))
+    if hparams.verbose:
+      print('\tVictor-Purpura     KL mean: {:.04f}'.format(np.mean(kl)))
   return out
 
 
@@ -385,6 +425,15 @@ def build_parser():
                       help='gpu: deconvolution and statistics on the device')
   parser.add_argument('--batch_trials', default=128, type=int,
                       help='--device gpu: trials per launch')
+  # (absent from the namespace unless given, as main.py --spike_metrics: read
+  # them with getattr(hparams, 'victor_purpura', False) / (..., 'vp_q', 1.0))
+  parser.add_argument('--victor_purpura', action='store_true',
+                      default=argparse.SUPPRESS,
+                      help='also report victor_purpura_kl, the KL of the '
+                      'Victor-Purpura distances between the neurons of a trial')
+  parser.add_argument('--vp_q', type=float, default=argparse.SUPPRESS,
+                      help='--victor_purpura: cost per second of shifting a '
+                      'spike (default 1.0)')
   return parser
 
 

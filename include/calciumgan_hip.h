@@ -730,6 +730,33 @@ int cg_van_rossum(const float* spikes, int B, int T, int C, long long s_b,
  * bit for bit.  CG_EINVAL as cg_spike_stats: nb < 2, or 4 C + nb C > 60 KiB. */
 int cg_spike_corrcoef(const float* spikes, int B, int T, int C, long long s_b,
                       long long s_t, long long s_c, double* corr, void* stream);
+/* Victor-Purpura edit distances between the C trains of every sample, on the
+ * 24-Hz frame grid (victor_purpura.hip; the numpy statement is
+ * spike_metrics.victor_purpura_distance_frames).  With f_i the ascending frame
+ * indices of the non-zero entries of train i and n_i their number,
+ *   G[k][0] = k, G[0][l] = l,
+ *   G[k][l] = min(G[k-1][l] + 1, G[k][l-1] + 1,
+ *                 G[k-1][l-1] + fl(qf |f_a[k-1] - f_b[l-1]|)),
+ *   dist[.][a][b] = G[n_a][n_b]   (a, b the two trains of the pair),
+ * every operation rounded to float64 on its own (no fused multiply-add), the
+ * frame difference an exact integer.  qf = q / 24 is formed by the caller
+ * (spike_metrics.victor_purpura_cost).  Only sums and minima of non-NaN values:
+ * the result equals the statement bit for bit.  dist: float64 [B][C][C],
+ * symmetric bit for bit, diagonal exactly 0, the same bits every call (no
+ * atomics; nothing in ws or dist has to be zeroed beforehand).  Two launches on
+ * `stream`: the trains are compacted to frame indices in ws, then one 16-lane
+ * row per pair sweeps the programme in strips of 16 columns.  A pair costs
+ * O(n_a n_b) whatever qf is (no time band).
+ * ws: cg_victor_purpura_ws_bytes(B, T, C) bytes, 8-byte aligned: one boundary
+ * line of T + 1 float64 per resident pair (at most 8192 of them), 4 B C bytes
+ * of counts and 2 B C T bytes of frame indices.  -1 for an unsupported shape.
+ * Limits: B <= 65536, T <= 16384 (uint16 frame indices), C <= 4096.
+ * CG_EINVAL (nothing launched): a NULL spikes, dist or ws, B, T or C < 1 or over
+ * the limits, qf negative or NaN, ws_bytes too small or ws misaligned. */
+long long cg_victor_purpura_ws_bytes(int B, int T, int C);
+int cg_victor_purpura(const float* spikes, int B, int T, int C, long long s_b,
+                      long long s_t, long long s_c, double qf, double* dist,
+                      void* ws, long long ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
