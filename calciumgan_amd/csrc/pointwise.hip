@@ -193,6 +193,30 @@ __device__ __forceinline__ float group_sum(float v, int lpr) {
   return group_sum_n(v, lpr);  // DPP / permlane swaps, no LDS round trips
 }
 
+// Load batches and minimum runs of the three LayerNorm kernels.  A wave owns
+// rows_per_slot rows per lane slot and walks them kRB at a time: the loop `for
+// (it0 = 0; it0 < rows_per_slot; it0 += kRB)` touches kRB rows per pass, so a
+// rows_per_slot that is not a multiple of kRB would run into the next wave's
+// rows (a racing store in the forward, rows counted twice in the backward's
+// sums).  rows_per_slot_for returns lo * 2^k: every call site's lo must be a
+// multiple of the kRB of the kernel it launches (asserted there).
+#ifndef CG_LN_RB
+#define CG_LN_RB 4
+#endif
+#ifndef CG_LN_RPS_LO
+#define CG_LN_RPS_LO 4
+#define CG_LN_RPS_HI 8
+#endif
+constexpr int kLnFwdRB = CG_LN_RB;   // ln_fwd_kernel
+constexpr int kLnFwd8RB = 2;         // ln_fwd8_kernel
+constexpr int kLnBwdRB = 2;          // ln_bwd_kernel
+constexpr int kLnFwdRpsLo = CG_LN_RPS_LO, kLnFwdRpsHi = CG_LN_RPS_HI;
+constexpr int kLnFwd8RpsLo = 2, kLnFwd8RpsHi = 8;
+constexpr int kLnBwdRpsLoWs = 4, kLnBwdRpsHiWs = 16;    // partial rows (ws)
+constexpr int kLnBwdRpsLoAt = 16, kLnBwdRpsHiAt = 64;   // atomics (ws == NULL)
+static_assert(CG_LN_RPS_LO % CG_LN_RB == 0,
+              "CG_LN_RPS_LO must be a multiple of CG_LN_RB");
+
 __global__ __launch_bounds__(kThreads) void ln_fwd_kernel(
     const uint16_t* __restrict__ y, const float* __restrict__ gamma,
     const float* __restrict__ beta, uint16_t* __restrict__ h,
@@ -218,10 +242,7 @@ __global__ __launch_bounds__(kThreads) void ln_fwd_kernel(
   const long long row0 = wave_id * (long long)rpw * rows_per_slot + slot;
   // kRB rows' loads are issued before any of them is reduced: one 16-byte load
   // per lane in flight cannot cover the HBM latency at this occupancy
-#ifndef CG_LN_RB
-#define CG_LN_RB 4
-#endif
-  constexpr int kRB = CG_LN_RB;
+  constexpr int kRB = kLnFwdRB;
   for (int it0 = 0; it0 < rows_per_slot; it0 += kRB) {
    uint4 raw[kRB];
 #pragma unroll
@@ -298,7 +319,7 @@ __global__ __launch_bounds__(kThreads) void ln_fwd8_kernel(
   const int ng = Cp >> 3;
   const float invC = 1.f / C;
   const long long row0 = wave_id * (long long)rpw * rows_per_slot + slot;
-  constexpr int kRB = 2;
+  constexpr int kRB = kLnFwd8RB;
   for (int it0 = 0; it0 < rows_per_slot; it0 += kRB) {
     uint4 raw[kRB][GPL];
 #pragma unroll
@@ -397,7 +418,7 @@ __global__ __launch_bounds__(kThreads) void ln_bwd_kernel(
   }
   const float invC = 1.f / C;
   const long long row0 = wave_id * (long long)rpw * rows_per_slot + slot;
-  constexpr int kRB = 2;  // rows whose loads are in flight together
+  constexpr int kRB = kLnBwdRB;  // rows whose loads are in flight together
   for (int it0 = 0; it0 < rows_per_slot; it0 += kRB) {
    uint4 rd[kRB], rh[kRB], ry[kRB];
    float rmean[kRB], rrstd[kRB];
@@ -1632,15 +1653,12 @@ extern "C" int cg_ln_lrelu_fwd(const void* y_pre, const float* gamma,
   const int rpw = 64 / lpr;
   // rows per lane slot: enough waves to fill the chip (256 CUs x 32) before
   // each wave gets a longer sequential run; a multiple of the load batch
-#ifndef CG_LN_RPS_LO
-#define CG_LN_RPS_LO 4
-#define CG_LN_RPS_HI 8
-#endif
   static const bool pow2_only = getenv("CALCIUMGAN_LN_POW2") != nullptr;  // (A/B)
   if (lpr * 8 != Cp && Cp >= 64 && !pow2_only) {
     // a pitch whose 8-channel groups are not a power of two: 8 lanes per row
     const int gpl = (Cp / 8 + 7) / 8;
-    const int rps = rows_per_slot_for(rows, 8, 2, 8);
+    static_assert(kLnFwd8RpsLo % kLnFwd8RB == 0, "ln_fwd8_kernel: lo % kRB");
+    const int rps = rows_per_slot_for(rows, 8, kLnFwd8RpsLo, kLnFwd8RpsHi);
     const dim3 grid(grid1d(rows, 4 * 8 * rps, 1LL << 31));
 #define CG_LN8(G)                                                                 \
   case G:                                                                         \
@@ -1655,7 +1673,8 @@ extern "C" int cg_ln_lrelu_fwd(const void* y_pre, const float* gamma,
 #undef CG_LN8
     CG_LAUNCH_CHECK();
   }
-  const int rows_per_slot = rows_per_slot_for(rows, rpw, CG_LN_RPS_LO, CG_LN_RPS_HI);
+  static_assert(kLnFwdRpsLo % kLnFwdRB == 0, "ln_fwd_kernel: lo % kRB");
+  const int rows_per_slot = rows_per_slot_for(rows, rpw, kLnFwdRpsLo, kLnFwdRpsHi);
   hipLaunchKernelGGL(ln_fwd_kernel,
                      dim3(grid1d(rows, 4 * rpw * rows_per_slot, 1LL << 31)),
                      dim3(kThreads), 0, S_(stream), U16(y_pre), gamma, beta,
@@ -1693,8 +1712,10 @@ extern "C" int cg_ln_lrelu_bwd(const void* dh, const void* h, const void* y_pre,
   // addresses, which serialise -- fewer, longer blocks); partial rows: a block
   // ends with one coalesced store, so shorter runs and more blocks in flight,
   // capped at kMaxParts blocks (the workspace's size)
-  int rows_per_slot = ws ? rows_per_slot_for(rows, rpw, 4, 16)
-                         : rows_per_slot_for(rows, rpw, 16, 64);
+  static_assert(kLnBwdRpsLoWs % kLnBwdRB == 0 && kLnBwdRpsLoAt % kLnBwdRB == 0,
+                "ln_bwd_kernel: lo % kRB");
+  int rows_per_slot = ws ? rows_per_slot_for(rows, rpw, kLnBwdRpsLoWs, kLnBwdRpsHiWs)
+                         : rows_per_slot_for(rows, rpw, kLnBwdRpsLoAt, kLnBwdRpsHiAt);
   if (ws) {
     while ((rows + 4ll * rpw * rows_per_slot - 1) / (4ll * rpw * rows_per_slot) >
            kMaxParts)

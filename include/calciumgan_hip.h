@@ -394,12 +394,22 @@ int cg_unshuffle_fixup(const void* side, const void* h, void* delta,
                        int side_rows, float alpha, void* stream);
 
 /* ---------------------------------------------------------------------------
- * LayerNormalization(axis=-1, eps) + LeakyReLU, one wavefront per row.
- * Replaces layers.LayerNormalization + activation_fn
- * (calciumgan.py:44-46 etc.) and their autodiff backward.
+ * LayerNormalization(axis=-1, eps) + LeakyReLU.  Replaces
+ * layers.LayerNormalization + activation_fn (calciumgan.py:44-46 etc.) and
+ * their autodiff backward.  Activations are of the build's activation type
+ * (bf16 or fp16), [rows][Cp] with C real channels; Cp % 8 == 0, Cp <= 512,
+ * C <= Cp, rows >= 1 (else CG_EINVAL, nothing launched).  A row is covered by
+ * the lanes of part of a wavefront (8 channels per lane), several rows per wave.
+ *   mean / var: over the C real channels, two passes (mean, then the mean of
+ *     (y - mean)^2, biased); rstd = 1 / sqrt(var + eps);
+ *   h = lrelu((y - mean) rstd gamma + beta), lrelu(t) = t > 0 ? t : alpha t.
+ * Channels [C, Cp) of y_pre are never read into a result (they may hold
+ * anything, NaN included); channels [C, Cp) of h are stored as +0.  gamma / beta
+ * are read for c < C only.  mean / rstd may each be NULL: that statistic is not
+ * stored, h is the same.
  * ------------------------------------------------------------------------- */
-int cg_ln_lrelu_fwd(const void* y_pre /*bf16 [rows][Cp]*/, const float* gamma,
-                    const float* beta, void* h /*bf16 [rows][Cp]*/,
+int cg_ln_lrelu_fwd(const void* y_pre /*act [rows][Cp]*/, const float* gamma,
+                    const float* beta, void* h /*act [rows][Cp]*/,
                     float* mean /*[rows] or NULL*/, float* rstd /*[rows] or NULL*/,
                     long long rows, int C, int Cp, float eps, float alpha,
                     void* stream);
@@ -420,12 +430,20 @@ long long cg_reduce_ws_elems(void);
  * (cg_bn_bwd does: not deferrable).  cg_finish_defer returns the previous mode. */
 int cg_finish_defer(int on);
 int cg_finish_flush(void* stream);
-/* dy = d(loss)/d(y_pre); dgamma/dbeta (and, when dbias != NULL, the bias
- * gradient of the producing conv = column sums of dy): stored (ws) or
- * accumulated with f32 atomics (ws == NULL). */
-int cg_ln_lrelu_bwd(const void* dh /*bf16*/, const void* h /*bf16*/,
-                    const void* y_pre /*bf16*/, const float* mean,
-                    const float* rstd, const float* gamma, void* dy /*bf16*/,
+/* Backward of cg_ln_lrelu_fwd (same limits on Cp, C, rows).  mean / rstd [rows]
+ * are used AS GIVEN (not recomputed from y_pre).  With mask = h > 0 ? 1 : alpha
+ * (h = +0, -0 and NaN take alpha), do = dh mask, xhat = (y_pre - mean) rstd,
+ * dyh = do gamma and mean_c the mean over the C real channels:
+ *   dy = rstd (dyh - mean_c(dyh) - xhat mean_c(dyh xhat))
+ *   dgamma[c] = sum_rows do xhat, dbeta[c] = sum_rows do, and, when dbias !=
+ *   NULL, dbias[c] = sum_rows of the STORED (rounded) dy: the bias gradient of
+ *   the producing conv.
+ * The three sums are stored (ws) or accumulated with f32 atomics onto outputs
+ * the caller zeroed (ws == NULL), for c < C only.  Channels [C, Cp) of dh, h and
+ * y_pre are never read into a result; channels [C, Cp) of dy are stored as +0. */
+int cg_ln_lrelu_bwd(const void* dh /*act*/, const void* h /*act*/,
+                    const void* y_pre /*act*/, const float* mean,
+                    const float* rstd, const float* gamma, void* dy /*act*/,
                     float* dgamma, float* dbeta, float* dbias, long long rows,
                     int C, int Cp, float alpha, float* ws, void* stream);
 
@@ -440,8 +458,17 @@ int cg_ln_lrelu_bwd(const void* dh /*bf16*/, const void* h /*bf16*/,
  *     max(t, alpha t) (alpha = 1: no activation); inference passes the moving
  *     statistics.
  *   cg_bn_bwd: do = dout * (act ? lrelu'(h) : 1); dbeta = sum do, dgamma = sum
- *     do * xhat (both STORED); dy = gamma rstd (do - dbeta / R - xhat dgamma / R).
- * y / out / dout / h / dy bf16 [rows][Cp], Cp <= 2048.
+ *     do * xhat (both STORED); dy = gamma rstd (do - dbeta / R - xhat dgamma / R),
+ *     rstd = rsqrt(var + eps), xhat = (y - mean) rstd, R = rows, lrelu'(h) = h > 0
+ *     ? 1 : alpha (h = +0, -0 and NaN take alpha); act == 0: h is not read (NULL).
+ * y / out / dout / h / dy are of the build's activation type, [rows][Cp] with C
+ * real channels; Cp % 8 == 0, C <= Cp, rows >= 1, and Cp <= 2048 for cg_bn_stats
+ * and cg_bn_bwd (cg_bn_apply takes any pitch).  A NULL among the required
+ * pointers, one of moving_mean / moving_var without the other, or act != 0 with
+ * h == NULL: CG_EINVAL, nothing launched.  Channels [C, Cp) of the inputs are
+ * never read into a result (they may hold anything, NaN included); channels
+ * [C, Cp) of out / dy are stored as +0; the f32 vectors are read and written
+ * for c < C only.
  * ------------------------------------------------------------------------- */
 int cg_bn_stats(const void* y, long long rows, int C, int Cp, float* mean,
                 float* var, float* moving_mean /* or NULL */,
@@ -507,9 +534,15 @@ int cg_dense1_bce(const void* h /*[2B][Lt][Cp]*/, const float* w,
 /* ---------------------------------------------------------------------------
  * Backward of LeakyReLU + PhaseShuffle between discriminator layers:
  *   delta[b][r][c] = lrelu'(h[b][r][c]) * sum_{t: src(t)=r} e[b][t][c]
- * where src is the reflect gather of PhaseShuffle (calciumgan.py:117-138).
+ * where src is the reflect gather of PhaseShuffle (calciumgan.py:117-138): a
+ * row has no, one or two sources; the f32 sum times the mask is rounded once.
+ * lrelu'(h) = h > 0 ? 1 : alpha (h = +0, -0 and NaN take alpha).  Sample b takes
+ * shifts[b / seg_size] (|shift| < w; shifts == NULL: 0 everywhere).  e / h /
+ * delta are of the build's activation type; Cp % 8 == 0.  There is no channel
+ * count: all Cp channels are computed, so zero padding in e gives +0 padding in
+ * delta.
  * ------------------------------------------------------------------------- */
-int cg_unshuffle_mask(const void* e /*bf16 [nB][w][Cp]*/, const void* h,
+int cg_unshuffle_mask(const void* e /*act [nB][w][Cp]*/, const void* h,
                       void* delta, const int* shifts, int nB, int w, int Cp,
                       int seg_size, float alpha, void* stream);
 
