@@ -198,6 +198,9 @@ SIGNATURES = {
     'cg_victor_purpura_ws_bytes': [c_i, c_i, c_i],
     'cg_victor_purpura': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_d, c_vp, c_vp,
                           c_ll, c_vp],
+    # pair_hist.hip: the histogram counts behind the KL figures of the report
+    'cg_pair_histogram': [c_vp, c_ll, c_ll, c_ll, c_vp, c_ll, c_ll, c_ll, c_i,
+                          c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {'cg_packed_elems': c_ll, 'cg_pack_plan_bytes': c_ll,
              'cg_pack_plan_build': c_ll, 'cg_wgrad_partials_elems': c_ll,

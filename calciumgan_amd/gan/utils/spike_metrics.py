@@ -422,3 +422,105 @@ def victor_purpura_distance_device(spikes, q=1.0):
            spikes.stride(1), spikes.stride(2), victor_purpura_cost(q),
            nets._p(dist), nets._p(ws), nbytes, nets._stream())
   return dist
+
+
+# -- the histogram counts behind the KL figures of compute_metrics.py ------------
+def pair_histograms(real, fake, num_bins=30):
+  """What pandas.cut(pooled, bins=num_bins) makes of every (recorded, synthetic)
+  pair, as integer counts: float64 host arrays (P, C, C) -> (counts (P, 2,
+  num_bins) int32, valid (P, 2) int32, edges (P, num_bins + 1) float64, status
+  (P,) int32).  Side 0 of pair p is the set of real[p][i][j], i < j, that are not
+  NaN (compute_metrics._upper), side 1 the same from fake; valid holds the two
+  set sizes.  With mn, mx the pooled minimum and maximum (a zero maximum taken
+  as +0: numpy's own choice between the zeros depends on its reduction order),
+    mn == mx:  mn -= (0.001 |mn| if mn != 0 else 0.001),
+               mx += (0.001 |mx| if mx != 0 else 0.001)
+    otherwise: adj = (mx - mn) 0.001
+    step = (mx - mn) / num_bins
+    e[k] = fl(fl(k step) + mn)   (step == 0: fl(fl(fl(k / num_bins) (mx - mn)) + mn))
+    e[num_bins] = mx;  mn != mx: e[0] -= adj
+    id(x) = number of edges < x;  x counts in bin id - 1 when 1 <= id <= num_bins
+  -- pandas.core.reshape.tile._nbins_to_bins and _bins_to_cuts with right=True
+  and np.linspace restated, every operation rounded to float64 on its own.
+  status is a bit set: 1 a side is empty, 2 a pooled value is infinite, 4 two
+  edges coincide (looked for only when there is a value and none is infinite);
+  pandas raises ValueError for 2 and 4.  With status != 0 the pair's counts and
+  edges are zeros.  The statement cg_pair_histogram (csrc/pair_hist.hip) is
+  tested against, bit for bit.  No pandas here."""
+  real, fake = np.asarray(real), np.asarray(fake)
+  if not (real.dtype == fake.dtype == np.float64 and real.ndim == 3 and
+          real.shape == fake.shape and real.shape[1] == real.shape[2] >= 2):
+    raise ValueError('two float64 arrays (P, C, C), C >= 2, expected')
+  num_bins = int(num_bins)
+  if num_bins < 1:
+    raise ValueError('num_bins < 1')
+  P, C = real.shape[:2]
+  iu = np.triu_indices(C, k=1)
+  counts = np.zeros((P, 2, num_bins), np.int32)
+  valid = np.zeros((P, 2), np.int32)
+  edges = np.zeros((P, num_bins + 1), np.float64)
+  status = np.zeros((P,), np.int32)
+  k = np.arange(num_bins + 1).astype(np.float64)
+  for p in range(P):
+    sides = [m[iu] for m in (real[p], fake[p])]
+    sides = [s[~np.isnan(s)] for s in sides]
+    valid[p] = [len(s) for s in sides]
+    pooled = np.concatenate(sides)
+    st = 1 if min(len(s) for s in sides) == 0 else 0
+    if len(pooled) and np.isinf(pooled).any():
+      st |= 2
+    if len(pooled) and not st & 2:
+      mn, mx = np.float64(pooled.min()), np.float64(pooled.max()) + 0.0
+      flat = mn == mx
+      with np.errstate(over='ignore', invalid='ignore'):
+        if flat:
+          mn = mn - (0.001 * abs(mn) if mn != 0 else 0.001)
+          mx = mx + (0.001 * abs(mx) if mx != 0 else 0.001)
+        else:
+          adj = (mx - mn) * 0.001
+        delta = mx - mn
+        step = delta / np.float64(num_bins)
+        e = (k / np.float64(num_bins)) * delta if step == 0 else k * step
+        e = e + mn
+        e[num_bins] = mx
+        if not flat:
+          e[0] = e[0] - adj
+      if np.any(e[1:] == e[:-1]):
+        st |= 4
+    status[p] = st
+    if st == 0:
+      edges[p] = e
+      for s, x in enumerate(sides):
+        ids = np.searchsorted(e, x, side='left')
+        ids = ids[(ids >= 1) & (ids <= num_bins)]
+        counts[p, s] = np.bincount(ids - 1, minlength=num_bins)
+  return counts, valid, edges, status
+
+
+def pair_histograms_device(real, fake, num_bins=30, return_edges=True):
+  """`pair_histograms` on the GPU (cg_pair_histogram): float64 device tensors
+  (P, C, C), any strides, -> device (counts int32 (P, 2, num_bins), valid int32
+  (P, 2), edges float64 (P, num_bins + 1) or None without return_edges, status
+  int32 (P,)), the statement's bits.  One launch, no workspace, nothing zeroed
+  beforehand, no host synchronisation."""
+  import torch
+  from ... import _lib as hip
+  from ... import nets
+  ok = all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and
+           t.dim() == 3 for t in (real, fake))
+  if not (ok and real.shape == fake.shape and real.shape[1] == real.shape[2] and
+          real.device == fake.device):
+    raise ValueError('two float64 device tensors (P, C, C) expected')
+  P, C = real.shape[:2]
+  num_bins = int(num_bins)
+  dev = real.device
+  counts = torch.empty(P, 2, num_bins, dtype=torch.int32, device=dev)
+  valid = torch.empty(P, 2, dtype=torch.int32, device=dev)
+  status = torch.empty(P, dtype=torch.int32, device=dev)
+  edges = (torch.empty(P, num_bins + 1, dtype=torch.float64, device=dev)
+           if return_edges else None)
+  hip.call('cg_pair_histogram', nets._p(real), real.stride(0), real.stride(1),
+           real.stride(2), nets._p(fake), fake.stride(0), fake.stride(1),
+           fake.stride(2), P, C, num_bins, nets._p(counts), nets._p(valid),
+           nets._p(edges), nets._p(status), nets._stream())
+  return counts, valid, edges, status

@@ -20,9 +20,14 @@ the per-trial correlations and the van Rossum matrices through the HIP kernels
 (csrc/spikes.hip, csrc/van_rossum.hip) in batches of --batch_trials trials: the
 spike trains written back are the host's byte for byte, the firing rates equal,
 correlations and distances equal to float64 rounding (a value within that of a
-histogram edge may change bins in the KL).  The KL and the heatmap ordering stay
-on the host.  No process pool is created on that path (--num_processors is
-ignored): a pool forked after the GPU is open is not safe.
+histogram edge may change bins in the KL).  The per-trial matrices stay on the
+device: cg_pair_histogram (csrc/pair_hist.hip) cuts every pair of upper
+triangles into the bins pandas.cut would give them, and only the integer counts
+come to the host, where the KL's thirty float32 operations a pair and the
+heatmap ordering stay (CALCIUMGAN_DEVICE_KL=0: the matrices come to the host and
+pandas cuts them, as before; the same report).  No process pool is created on
+that path (--num_processors is ignored): a pool forked after the GPU is open is
+not safe.
 
 --victor_purpura (not a reference flag either; absent from the namespace unless
 given) adds `victor_purpura_kl`, built exactly as `van_rossum_kl` from the
@@ -78,6 +83,15 @@ def pairs_kl_divergence(pairs):
                         dtype=np.float32) / len(fake)
     kl[i] = kl_divergence(real_pdf, fake_pdf)
   return kl
+
+
+def kl_from_counts(real_counts, fake_counts, n_real, n_fake):
+  """The tail of `pairs_kl_divergence` for one pair: from the NUM_BINS integer
+  bin counts of either sample and the sample sizes the same float32 it stores
+  (counts as float32 divided by the size, then `kl_divergence`)."""
+  real_pdf = np.asarray(real_counts).astype(np.float32) / int(n_real)
+  fake_pdf = np.asarray(fake_counts).astype(np.float32) / int(n_fake)
+  return np.float32(kl_divergence(real_pdf, fake_pdf))
 
 
 def _spikes(hparams, filename, data_format, neuron=None, trial=None,
@@ -267,26 +281,33 @@ def deconvolve_from_file_device(hparams, filename):
   return spikes
 
 
-def trial_statistics_device(hparams, filename):
+def trial_statistics_device(hparams, filename, matrices_on_device=False):
   """Of the first num_samples trials of `filename`, on the device: firing rates
   (n, C) float32 (cg_spike_stats), correlation coefficients and van Rossum
   distances between the trial's neurons (n, C, C) float64 (cg_spike_corrcoef,
   cg_van_rossum), brought to the host; with --victor_purpura the Victor-Purpura
-  distances (cg_victor_purpura) as well."""
+  distances (cg_victor_purpura) as well.  matrices_on_device: the (n, C, C)
+  matrices stay device tensors (the firing rates come to the host either way)."""
+  import torch
   spikes = utils.set_array_format(
       np.asarray(h5_helper.get(filename, name='spikes')), 'NWC', hparams)
   rates, corr, dist, vp = [], [], [], []
   for batch in _batches(hparams, spikes[:hparams.num_samples]):
     rates.append(spike_metrics.batch_statistics_device(batch)[0].cpu().numpy())
-    corr.append(spike_metrics.correlation_coefficients_device(batch).cpu().numpy())
-    dist.append(spike_metrics.van_rossum_distance_device(batch).cpu().numpy())
+    corr.append(spike_metrics.correlation_coefficients_device(batch))
+    dist.append(spike_metrics.van_rossum_distance_device(batch))
     if getattr(hparams, 'victor_purpura', False):
       vp.append(spike_metrics.victor_purpura_distance_device(
-          batch, q=getattr(hparams, 'vp_q', 1.0)).cpu().numpy())
-  stats = dict(rates=np.concatenate(rates), correlation=np.concatenate(corr),
-               van_rossum=np.concatenate(dist))
+          batch, q=getattr(hparams, 'vp_q', 1.0)))
+    if not matrices_on_device:
+      for per_batch in (corr, dist, vp):
+        if per_batch:
+          per_batch[-1] = per_batch[-1].cpu().numpy()
+  join = torch.cat if matrices_on_device else np.concatenate
+  stats = dict(rates=np.concatenate(rates), correlation=join(corr),
+               van_rossum=join(dist))
   if vp:
-    stats['victor_purpura'] = np.concatenate(vp)
+    stats['victor_purpura'] = join(vp)
   return stats
 
 
@@ -333,20 +354,83 @@ def device_pairs(hparams, filename):
   return pairs
 
 
+def device_kl_enabled():
+  """CALCIUMGAN_DEVICE_KL=0: the histograms behind the KL figures are cut on the
+  host (`device_pairs`, then `pairs_kl_divergence`), as before cg_pair_histogram."""
+  return os.environ.get('CALCIUMGAN_DEVICE_KL', '1') != '0'
+
+
+def pairs_kl_divergence_device(hparams, real, fake, remove_nan):
+  """`pairs_kl_divergence` of the upper triangles of the float64 device matrices
+  real[i], fake[i] (n, C, C): the bin counts from cg_pair_histogram in one
+  launch, only counts, sizes and status brought to the host, `kl_from_counts`
+  there.  remove_nan: the samples are what `_upper` keeps (the correlations),
+  so the divisor is the pair's own size; otherwise it is C (C - 1) / 2, as the
+  host divides the distances.  A pair whose status is not 0 goes through
+  `pairs_kl_divergence` itself, its two triangles fetched for it alone
+  (counted in hparams._kl_host_fallbacks)."""
+  n = min(len(real), len(fake))
+  real, fake = real[:n], fake[:n]
+  C = real.shape[1]
+  counts, valid, _, status = spike_metrics.pair_histograms_device(
+      real, fake, NUM_BINS, return_edges=False)
+  counts, valid, status = (t.cpu().numpy() for t in (counts, valid, status))
+  full = C * (C - 1) // 2
+  iu = np.triu_indices(C, k=1)
+  kl = np.zeros((n,), dtype=np.float32)
+  for i in range(n):
+    if status[i] != 0:
+      r, f = real[i].cpu().numpy(), fake[i].cpu().numpy()
+      pair = (_upper(r, C), _upper(f, C)) if remove_nan else (r[iu], f[iu])
+      hparams._kl_host_fallbacks = getattr(hparams, '_kl_host_fallbacks', 0) + 1
+      kl[i] = pairs_kl_divergence([pair])[0]
+    else:
+      n_real, n_fake = valid[i] if remove_nan else (full, full)
+      kl[i] = kl_from_counts(counts[i, 0], counts[i, 1], n_real, n_fake)
+  return kl
+
+
+def device_kl(hparams, filename):
+  """name -> callable giving the float32 KL per pair behind each figure of the
+  device report.  The matrices of both files stay on the device (the recorded
+  side cached across epochs) and are cut there; the firing rates (one pair per
+  neuron of float32 values) are cut on the host."""
+  real = getattr(hparams, '_recorded_statistics_device', None)
+  if real is None:  # the validation set is the same for every epoch
+    real = hparams._recorded_statistics_device = trial_statistics_device(
+        hparams, hparams.validation_cache, matrices_on_device=True)
+  fake = trial_statistics_device(hparams, filename, matrices_on_device=True)
+  hparams._kl_host_fallbacks = getattr(hparams, '_kl_host_fallbacks', 0)
+  n = hparams.num_neurons
+  figures = dict(firing_rate=lambda: pairs_kl_divergence(
+      [(real['rates'][:, c], fake['rates'][:, c]) for c in range(n)]))
+  for name in ('correlation', 'van_rossum', 'victor_purpura'):
+    if name in fake:
+      figures[name] = (lambda name=name: pairs_kl_divergence_device(
+          hparams, real[name], fake[name], remove_nan=name == 'correlation'))
+  return figures
+
+
 def compute_epoch_spike_metrics_device(hparams, filename, epoch):
-  """`compute_epoch_spike_metrics` with the statistics from the device; the KL
-  and `sort_heatmap` on the host as there."""
+  """`compute_epoch_spike_metrics` with the statistics from the device; the
+  histograms behind the KL from cg_pair_histogram (`device_kl`) unless
+  CALCIUMGAN_DEVICE_KL=0, the KL's arithmetic and `sort_heatmap` on the host."""
   if not h5_helper.contains(filename, 'spikes'):
     deconvolve_from_file_device(hparams, filename)
-  pairs = device_pairs(hparams, filename)
+  if device_kl_enabled():
+    figures = device_kl(hparams, filename)
+  else:
+    pairs = device_pairs(hparams, filename)
+    figures = {name: (lambda name=name: pairs_kl_divergence(pairs[name]))
+               for name in pairs}
   out = {}
-  kl = pairs_kl_divergence(pairs['firing_rate'])
+  kl = figures['firing_rate']()
   out['firing_rate_kl'] = dict(
       mean=float(np.mean(kl)),
       neurons={int(n): float(kl[n]) for n in hparams.neurons})
   if hparams.verbose:
     print('\tfiring rate        KL mean: {:.04f}'.format(np.mean(kl)))
-  kl = pairs_kl_divergence(pairs['correlation'])
+  kl = figures['correlation']()
   out['correlation_kl'] = dict(mean=float(np.mean(kl)))
   if hparams.verbose:
     print('\tcorrelation        KL mean: {:.04f}'.format(np.mean(kl)))
@@ -354,12 +438,12 @@ def compute_epoch_spike_metrics_device(hparams, filename, epoch):
   out['van_rossum_heatmap_min'] = {
       int(n): float(np.nanmin(sort_heatmap(b)[0]))
       for n, b in zip(hparams.neurons, blocks)}
-  kl = pairs_kl_divergence(pairs['van_rossum'])
+  kl = figures['van_rossum']()
   out['van_rossum_kl'] = dict(mean=float(np.mean(kl)))
   if hparams.verbose:
     print('\tvan Rossum         KL mean: {:.04f}'.format(np.mean(kl)))
-  if 'victor_purpura' in pairs:
-    kl = pairs_kl_divergence(pairs['victor_purpura'])
+  if 'victor_purpura' in figures:
+    kl = figures['victor_purpura']()
     out['victor_purpura_kl'] = dict(mean=float(np.mean(kl)))
     if hparams.verbose:
       print('\tVictor-Purpura     KL mean: {:.04f}'.format(np.mean(kl)))

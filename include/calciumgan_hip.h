@@ -790,6 +790,36 @@ long long cg_victor_purpura_ws_bytes(int B, int T, int C);
 int cg_victor_purpura(const float* spikes, int B, int T, int C, long long s_b,
                       long long s_t, long long s_c, double qf, double* dist,
                       void* ws, long long ws_bytes, void* stream);
+/* Histogram counts behind the KL figures of that report (pair_hist.hip; the
+ * numpy statement is spike_metrics.pair_histograms).  Added under ABI 20.  For
+ * pair p, side a is the set of a[p][i][j] with i < j that are not NaN, side b
+ * the same from b; valid[p] holds the two set sizes.  The pooled values are cut
+ * exactly as pandas.cut(pooled, bins=num_bins) cuts them (right-closed bins):
+ *   mn, mx the pooled minimum and maximum (a zero maximum is taken as +0)
+ *   mn == mx:  mn -= (mn != 0 ? 0.001 |mn| : 0.001),
+ *              mx += (mx != 0 ? 0.001 |mx| : 0.001)
+ *   otherwise: adj = (mx - mn) 0.001
+ *   step = (mx - mn) / num_bins
+ *   e[k] = fl(fl(k step) + mn)  (step == 0: fl(fl(fl(k / num_bins) (mx - mn)) + mn))
+ *   e[num_bins] = mx;  mn != mx: e[0] -= adj
+ *   id(x) = number of edges < x;  x counts in bin id - 1 when 1 <= id <= num_bins
+ * every operation rounded to float64 on its own (no fused multiply-add).  The
+ * bin comes from comparing x with the edges, not from (x - mn) / step.
+ * status[p] is a bit set: 1 a side is empty, 2 a pooled value is infinite, 4 two
+ * edges coincide (looked for only when there is a value and none is infinite).
+ * With status != 0 the pair's counts and edges are written as zeros, valid as
+ * counted.  counts: int32 [P][2][num_bins]; valid: int32 [P][2]; edges: float64
+ * [P][num_bins + 1] or NULL; status: int32 [P].  One launch, one workgroup per
+ * pair; every output element is written (nothing has to be zeroed beforehand),
+ * no global atomics, no workspace, the same bits every call.  Strides in
+ * elements, any sign.
+ * CG_EINVAL (nothing launched): a NULL a, b, counts, valid or status, P < 1,
+ * C < 2 or C > 4096, num_bins < 1 or num_bins > 256. */
+int cg_pair_histogram(const double* a, long long a_sp, long long a_si,
+                      long long a_sj, const double* b, long long b_sp,
+                      long long b_si, long long b_sj, int P, int C, int num_bins,
+                      int* counts, int* valid, double* edges, int* status,
+                      void* stream);
 
 #ifdef __cplusplus
 }
