@@ -2,7 +2,27 @@
 AR(1) deconvolution bit-identical to the host library, per-trial firing rates /
 binned covariances and their ordered error sums, GAN.spike_statistics against
 the host chain, main.py --spike_metrics and compute_dg_metrics.py --device gpu.
-Every case is one launch on valid input."""
+Every case is one launch on valid input.
+
+cg_spike_stats is compared bit for bit with the exact statement of
+tests/spike_stats_cases.py (integer sums, one float64 division, one rounding to
+float32; tied to spike_metrics.batch_statistics in tests/test_spike_stats.py) at
+the (T, C) grid of the older test and at: C = 300 (the second trip of the loops
+over c += 256, P = 45 150 pairs on the capped `split` of 8, 61 200 B of LDS),
+C = 240 at the 61 440 B that are the most admitted, one bin more refused by both
+entries with nothing written, C = 44 / 45 and 119 / 120 on either side of a step
+of `split`, channel-major storage and a slice of a wider buffer beside the
+contiguous batch, and planted trains (12 spikes in every bin; 2.0, -1.0, a
+subnormal and NaN as spikes; -0.0 as none).  cg_spike_stats_error is compared
+exactly on planted powers of two -- a dropped, doubled or misplaced element
+changes the sums -- from no element to past the 1024 x 2048 elements at which
+the grid is capped and a thread strides over a ninth one, and under a derived
+rounding bar on random input; its workspace is exactly the size asked for
+inside a NaN buffer.  Outputs are over-allocated: their tails keep the fill.
+(cg_spike_corrcoef at the same large shapes: tests/test_hip_van_rossum.py.)
+
+Out of scope: C between 301 and the 4096 the entries admit needs T < 2400, a
+regime without a path of its own; timing."""
 import json
 import os
 from types import SimpleNamespace
@@ -15,8 +35,11 @@ import compute_dg_metrics as cdm
 import main as cli
 import oracle as O
 from calciumgan_amd.data import dg
+from calciumgan_amd import _lib, nets
 from calciumgan_amd.gan.utils import (dataset_helper, spike_helper,
                                       spike_metrics, utils)
+
+import spike_stats_cases as SC
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +49,6 @@ DEV = 'cuda:0'
 @pytest.fixture(autouse=True)
 def _back_to_bf16():
   yield
-  from calciumgan_amd import _lib
   _lib.use('bf16')
 
 
@@ -129,12 +151,40 @@ def test_deconvolution_in_groups_of_traces_matches_one_launch():
   assert np.array_equal(out.cpu().numpy(), spike_helper.deconvolve_signals(rows))
 
 
-def _trains(B, T, C, seed):
-  rng = np.random.RandomState(seed)
-  rate = rng.uniform(0.02, 0.3, (1, 1, C))
-  sp = (rng.uniform(size=(B, T, C)) < rate).astype(np.float32)
-  sp[:, :, 0] = 0.0  # a silent neuron
-  return sp
+_trains = SC.trains
+TAIL = 64             # sentinel elements behind every output
+FILL = -7.0
+
+
+def _bits32(a):
+  return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+def _stats_entry(x):
+  """cg_spike_stats on a (B, T, C) device tensor read in place, into outputs
+  filled with NaN that are TAIL elements longer than needed, the tail -7: every
+  element must be written, the tail must not.  -> numpy (rates, covs)."""
+  B, T, C = x.shape
+  P = C * (C + 1) // 2
+  rates = torch.full((B * C + TAIL,), float('nan'), dtype=torch.float32, device=DEV)
+  covs = torch.full((B * P + TAIL,), float('nan'), dtype=torch.float32, device=DEV)
+  rates[B * C:] = FILL
+  covs[B * P:] = FILL
+  _lib.call('cg_spike_stats', nets._p(x), B, T, C, x.stride(0), x.stride(1),
+            x.stride(2), nets._p(rates), nets._p(covs), nets._stream())
+  torch.cuda.synchronize()
+  rates, covs = rates.cpu().numpy(), covs.cpu().numpy()
+  assert np.all(rates[B * C:] == FILL) and np.all(covs[B * P:] == FILL)
+  assert not np.isnan(rates[:B * C]).any() and not np.isnan(covs[:B * P]).any()
+  return rates[:B * C].reshape(B, C), covs[:B * P].reshape(B, P)
+
+
+def _assert_cov_bits(covs, sp):
+  want = SC.exact_covariance(sp)
+  diff = _bits32(covs) != _bits32(want)
+  print('%d of %d covariances differ from the exact statement' % (
+      int(diff.sum()), diff.size))
+  assert not diff.any(), np.argwhere(diff)[:8]
 
 
 @pytest.mark.parametrize('C', [6, 102])
@@ -161,12 +211,78 @@ def test_statistics_against_spike_metrics(T, C):
   assert np.all(covs[zero] == 0)
   np.testing.assert_allclose(covs[~zero], want_c[~zero], rtol=1e-6, atol=0)
   assert (~zero).sum() > 0
+  # the exact statement: the same bits
+  _assert_cov_bits(covs, sp)
   # a strided view gives the same bits
   buf = torch.zeros(B, T, C + 5, dtype=torch.float32, device=DEV)
   buf[:, :, :C] = torch.from_numpy(sp).to(DEV)
   r2, c2 = spike_metrics.batch_statistics_device(buf[:, :, :C])
   assert np.array_equal(r2.cpu().numpy(), rates)
   assert np.array_equal(c2.cpu().numpy(), covs)
+
+
+@pytest.mark.parametrize('name', sorted(SC.SHAPES))
+def test_statistics_bit_equal_to_the_exact_statement(name):
+  """Rates: the float32 the host code returns for the trains `spikes != 0`.
+  Covariances: the bits of the exact statement."""
+  sp = SC.stats_case(name)
+  T, C = SC.SHAPES[name]
+  x = torch.from_numpy(sp.copy()).to(DEV)
+  rates, covs = _stats_entry(x)
+  want_r, _ = spike_metrics.batch_statistics(SC.binary(sp))
+  assert np.array_equal(_bits32(rates), _bits32(want_r))
+  _assert_cov_bits(covs, sp)
+  # the wrapper's outputs hold the same bits, and so does a second call
+  r2, c2 = spike_metrics.batch_statistics_device(x)
+  assert np.array_equal(_bits32(r2.cpu().numpy()), _bits32(rates))
+  assert np.array_equal(_bits32(c2.cpu().numpy()), _bits32(covs))
+  if name == 'planted_c6_t48':
+    # the {0, 1} trains the host's rule makes of the planted values: same bits
+    r3, c3 = _stats_entry(torch.from_numpy(SC.binary(sp)).to(DEV))
+    assert np.array_equal(_bits32(r3), _bits32(rates))
+    assert np.array_equal(_bits32(c3), _bits32(covs))
+    iu = np.triu_indices(C)
+    assert np.all(covs[:, (iu[0] == 0) | (iu[0] == 2) | (iu[1] == 2)] == 0)
+
+
+def test_statistics_same_bits_from_three_layouts():
+  """(2, 250, 130) contiguous, stored channel-major (s_t = 1, s_c = T) and as a
+  slice of a (2, 250, 136) buffer whose other channels hold 7.0."""
+  name = 'c130_t250'
+  sp = SC.stats_case(name)
+  B, T, C = sp.shape
+  want = _stats_entry(torch.from_numpy(sp.copy()).to(DEV))
+  _assert_cov_bits(want[1], sp)
+  rows = torch.from_numpy(np.ascontiguousarray(sp.transpose(0, 2, 1))).to(DEV)
+  x = rows.transpose(1, 2)                             # stored (B, C, T)
+  assert tuple(x.shape) == (B, T, C) and x.stride() == (C * T, 1, T)
+  buf = torch.full((B, T, 136), 7.0, dtype=torch.float32, device=DEV)
+  buf[:, :, :C] = torch.from_numpy(sp.copy()).to(DEV)
+  y = buf[:, :, :C]
+  assert y.stride() == (T * 136, 136, 1)
+  for view in (x, y):
+    got = _stats_entry(view)
+    assert np.array_equal(_bits32(got[0]), _bits32(want[0]))
+    assert np.array_equal(_bits32(got[1]), _bits32(want[1]))
+
+
+@pytest.mark.parametrize('T,C', SC.REFUSED)
+def test_statistics_one_bin_past_the_lds_limit_are_refused(T, C):
+  """One more 500-ms bin than 60 KiB of LDS holds: CG_EINVAL, decided on the
+  host, with the outputs untouched."""
+  assert SC.lds_bytes(T, C) > SC.STATS_MAX_LDS >= SC.lds_bytes(T - 12, C)
+  B, P = 2, C * (C + 1) // 2
+  x = torch.ones(B, T, C, dtype=torch.float32, device=DEV)
+  rates = torch.full((B * C,), FILL, dtype=torch.float32, device=DEV)
+  covs = torch.full((B * P,), FILL, dtype=torch.float32, device=DEV)
+  rc = _lib.load().cg_spike_stats(nets._p(x), B, T, C, x.stride(0), x.stride(1),
+                                  x.stride(2), nets._p(rates), nets._p(covs),
+                                  nets._stream())
+  torch.cuda.synchronize()
+  assert rc == _lib.CG_EINVAL
+  assert bool((rates == FILL).all()) and bool((covs == FILL).all())
+  with pytest.raises(ValueError):
+    spike_metrics.batch_statistics_device(x)
 
 
 def test_statistics_refuse_fewer_than_two_bins():
@@ -191,6 +307,65 @@ def test_error_sums_against_numpy_and_bitwise_repeatable(B, C):
   np.testing.assert_allclose(got1.cpu().numpy(), want, rtol=1e-5)
   assert np.array_equal(got1.cpu().numpy().view(np.int32),
                         got2.cpu().numpy().view(np.int32))
+
+
+ERR_LEAD = 96         # NaN floats before the workspace of the error sums
+
+
+def _error_entry(ra, rb, ca, cb):
+  """cg_spike_stats_error on host float32 arrays (an empty side is handed over
+  as null pointers), its workspace exactly cg_spike_stats_error_ws_elems floats
+  inside a NaN buffer whose surroundings must stay NaN, `out` with a fifth
+  element that must keep its fill; run twice, the two results the same bits.
+  -> float32 (4,)."""
+  n_fr, n_cov = len(ra), len(ca)
+  elems = _lib.load().cg_spike_stats_error_ws_elems(n_fr, n_cov)
+  assert elems == 4 * SC.err_parts(n_fr, n_cov)
+  t = [torch.from_numpy(a.copy()).to(DEV) if len(a) else None
+       for a in (ra, rb, ca, cb)]
+  outs = []
+  for _ in range(2):
+    buf = torch.full((ERR_LEAD + elems + TAIL,), float('nan'), dtype=torch.float32,
+                     device=DEV)
+    out = torch.full((5,), FILL, dtype=torch.float32, device=DEV)
+    _lib.call('cg_spike_stats_error', nets._p(t[0]), nets._p(t[1]), n_fr,
+              nets._p(t[2]), nets._p(t[3]), n_cov, nets._p(out),
+              nets._p(buf[ERR_LEAD:]), nets._stream())
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(buf[:ERR_LEAD]).all()), 'floats before the workspace'
+    assert bool(torch.isnan(buf[ERR_LEAD + elems:]).all()), 'floats behind it'
+    assert not bool(torch.isnan(buf[ERR_LEAD:ERR_LEAD + elems]).any())
+    out = out.cpu().numpy()
+    assert out[4] == FILL
+    outs.append(out[:4])
+  assert np.array_equal(_bits32(outs[0]), _bits32(outs[1]))
+  return outs[0]
+
+
+@pytest.mark.parametrize('n_fr,n_cov', SC.ERROR_SIZES)
+def test_error_sums_of_planted_powers_of_two_are_exact(n_fr, n_cov):
+  """The two sets differ at a few indices by distinct powers of two: every
+  partial sum is a float32 whatever the order, so the device's sums equal the
+  float64 ones exactly."""
+  ra, rb, ca, cb = SC.planted_error_inputs(n_fr, n_cov)
+  got = _error_entry(ra, rb, ca, cb)
+  want = spike_metrics.error_sums(ra, rb, ca, cb)
+  print('device', got.tolist(), 'float64', want.tolist())
+  assert np.array_equal(got.astype(np.float64), want)
+  assert np.all(_bits32(got) >= 0)                     # +0.0 for an empty side
+
+
+@pytest.mark.parametrize('n_fr,n_cov', SC.RANDOM_ERROR_SIZES)
+def test_error_sums_of_random_input_within_the_rounding_bar(n_fr, n_cov):
+  """Against the float64 sums of the float32 inputs, within SC.error_bars."""
+  ra, rb, ca, cb = SC.random_error_inputs(n_fr, n_cov)
+  got = _error_entry(ra, rb, ca, cb).astype(np.float64)
+  want = spike_metrics.error_sums(ra, rb, ca, cb)
+  bars = SC.error_bars(n_fr, n_cov, want)
+  err = np.abs(got - want)
+  print('worst fraction of the bar: %.3g (relative errors %s)' % (
+      float((err / bars).max()), (err / want).tolist()))
+  assert np.all(err <= bars), (err / bars).tolist()
 
 
 def _tiny_gan(algorithm, L=256, C=16):

@@ -15,6 +15,7 @@ import compute_metrics as cm
 from calciumgan_amd import _lib, nets
 from calciumgan_amd.data import dg
 from calciumgan_amd.gan.utils import h5_helper, spike_metrics
+import spike_stats_cases as SC
 from van_rossum_cases import (correlation_cases, dg_batch, gram_reference,
                               random_trains)
 
@@ -233,6 +234,55 @@ def test_correlations(name):
   host = spike_metrics.correlation_coefficients(sp)
   assert np.abs(r[fin] - host[fin]).max() <= 4 * (T // 12) * U
   assert np.array_equal(_bits(r), _bits(r.T))
+
+
+CORR_TAIL = 64        # sentinel elements behind the correlation matrices
+
+
+@pytest.mark.parametrize('name', SC.CORRCOEF_CASES)
+def test_correlations_past_256_neurons_and_at_the_lds_limit(name):
+  """cg_spike_corrcoef on the batches of the cg_spike_stats tests: C = 300 (the
+  second trip of the loop over c += 256, 45 150 pairs on the capped grid of 8
+  workgroups a trial, 61 200 B of LDS) and C = 240 at the 61 440 B that are the
+  most admitted -- under the bars of test_correlations, trial by trial.  The
+  output starts as NaN with a tail of -7 that must survive."""
+  sp = SC.stats_case(name)                           # (2, T, C)
+  B, T, C = sp.shape
+  x = torch.from_numpy(sp.copy()).to(DEV)
+  out = torch.full((B * C * C + CORR_TAIL,), float('nan'), dtype=torch.float64,
+                   device=DEV)
+  out[B * C * C:] = -7.0
+  _lib.call('cg_spike_corrcoef', nets._p(x), B, T, C, x.stride(0), x.stride(1),
+            x.stride(2), nets._p(out), nets._stream())
+  torch.cuda.synchronize()
+  out = out.cpu().numpy()
+  assert np.all(out[B * C * C:] == -7.0)
+  r = out[:B * C * C].reshape(B, C, C)
+  for b in range(B):
+    want = spike_metrics.correlation_coefficients_exact(sp[b].T)
+    assert np.array_equal(np.isnan(r[b]), np.isnan(want))
+    fin = np.isfinite(want)
+    assert fin.any() and not fin.all()               # (neuron 0 is silent)
+    assert np.abs(_bits(r[b][fin]) - _bits(want[fin])).max() <= 2
+    host = spike_metrics.correlation_coefficients(sp[b].T)
+    assert np.abs(r[b][fin] - host[fin]).max() <= 4 * (T // 12) * U
+    assert np.array_equal(_bits(r[b]), _bits(r[b].T))
+  again = spike_metrics.correlation_coefficients_device(x)
+  assert np.array_equal(_bits(again.cpu().numpy()), _bits(r))
+
+
+@pytest.mark.parametrize('T,C', SC.REFUSED)
+def test_correlations_one_bin_past_the_lds_limit_are_refused(T, C):
+  assert SC.lds_bytes(T, C) > SC.STATS_MAX_LDS >= SC.lds_bytes(T - 12, C)
+  x = torch.ones(2, T, C, dtype=torch.float32, device=DEV)
+  out = torch.full((2 * C * C,), -7.0, dtype=torch.float64, device=DEV)
+  rc = _lib.load().cg_spike_corrcoef(nets._p(x), 2, T, C, x.stride(0),
+                                     x.stride(1), x.stride(2), nets._p(out),
+                                     nets._stream())
+  torch.cuda.synchronize()
+  assert rc == _lib.CG_EINVAL and bool((out == -7.0).all())
+  with pytest.raises(ValueError):
+    spike_metrics.correlation_coefficients_device(x)
 
 
 def test_device_functions_refuse_host_arrays_and_too_few_bins():

@@ -3,7 +3,25 @@ distances between the trains of a trial, one 16-lane row per pair) against its
 numpy statement spike_metrics.victor_purpura_distance_frames -- bit for bit: the
 programme only adds and takes minima -- and of compute_metrics.py
 --victor_purpura on both devices.  Every case is one or two launches on valid
-input.  Shapes are (B, T, C)."""
+input.  Shapes are (B, T, C).
+
+Covered, beside the small cases: the pair kernel past one pass of its grid of
+512 x 16 row slots -- slots that walk a second pair of unrelated counts over the
+boundary line and the LDS rings the first one left (reuse_3x96x102,
+reuse_40x48x27, dg_2x2048x102 in a pitch-128 buffer), also on a workspace that
+still holds an earlier call's contents; more than 13 strips of the shorter train
+and the boundary line up to row T (long_1x2048x6: 64 strips of 129 blocks beside
+pairs a hundred times shorter in the same wave); frame index 16383 at T = 16384,
+the largest admitted; the pair index -> (i, j) decode at every one of the
+8 386 560 pairs of C = 4096, the largest admitted, against two closed forms; a
+workspace of exactly cg_victor_purpura_ws_bytes between 0xFF guards and guard
+rows of NaN behind `dist`; T = 16385 and C = 4097 refused with nothing written.
+
+Out of scope: B near the limit of 65 536 trials (the workspace alone is out of
+reach of a test of a few seconds); two trains of more than 1024 spikes in one
+pair (128 strips: the statement's sweep over their 4096 anti-diagonals is
+cheap, a batch that makes the test worth more than long_1x2048x6 is not);
+timing."""
 import functools
 import os
 
@@ -17,8 +35,9 @@ from calciumgan_amd.data import dg
 from calciumgan_amd.gan.utils import h5_helper, spike_metrics
 from test_hip_van_rossum import _run_dir
 from van_rossum_cases import dg_batch
-from victor_purpura_cases import (counts_difference, crafted_trial, first_set,
-                                  second_set, unmatched_spikes)
+from victor_purpura_cases import (ROW_SLOTS, counts_difference, crafted_trial,
+                                  first_set, grid_case, pair_count, second_set,
+                                  unmatched_spikes)
 
 pytestmark = pytest.mark.gpu
 
@@ -53,13 +72,14 @@ def _case(name):
   elif name == 'crafted_1x200x13':
     sp = np.ascontiguousarray(crafted_trial().T[None])
   else:
-    raise KeyError(name)
+    return grid_case(name)
   sp.setflags(write=False)
   return sp
 
 
 CASES = ('random_3x96x7', 'dense_2x40x17', 'one_spike', 'no_spike', 'dg_3x480x17',
-         'crafted_1x200x13')
+         'crafted_1x200x13', 'reuse_3x96x102', 'reuse_40x48x27', 'long_1x2048x6',
+         't16384_1x16384x3')
 
 
 @functools.lru_cache(maxsize=None)
@@ -137,6 +157,114 @@ def test_nothing_in_the_workspace_needs_zeroing(name):
             nets._p(ws), nbytes, nets._stream())
   torch.cuda.synchronize()
   assert np.array_equal(_bits(dist.cpu().numpy()), _bits(_statement(name)))
+
+
+GUARD = 4096          # bytes of 0xFF on either side of the workspace
+GUARD_ROWS = 3        # rows of NaN behind dist
+
+
+def _entry(x, q=1.0, ws_buf=None):
+  """The C entry on a (B, T, C) device tensor read in place, with a workspace of
+  exactly cg_victor_purpura_ws_bytes inside a larger buffer of 0xFF bytes (or
+  inside `ws_buf`, an earlier call's buffer, as it was left) and `dist` NaN
+  with guard rows behind it.  The bytes around the workspace and the guard rows
+  must come back untouched.  -> (dist as numpy, the buffer)."""
+  B, T, C = x.shape
+  nbytes = _lib.load().cg_victor_purpura_ws_bytes(B, T, C)
+  assert nbytes > 0
+  if ws_buf is None:
+    ws_buf = torch.full((GUARD + nbytes + GUARD,), 0xFF, dtype=torch.uint8,
+                        device=DEV)
+  assert ws_buf.numel() == GUARD + nbytes + GUARD
+  ws = ws_buf[GUARD:GUARD + nbytes]
+  assert ws.data_ptr() % 8 == 0
+  dist = torch.full((B * C + GUARD_ROWS, C), float('nan'), dtype=torch.float64,
+                    device=DEV)
+  _lib.call('cg_victor_purpura', nets._p(x), B, T, C, x.stride(0), x.stride(1),
+            x.stride(2), spike_metrics.victor_purpura_cost(q), nets._p(dist),
+            nets._p(ws), nbytes, nets._stream())
+  torch.cuda.synchronize()
+  assert bool((ws_buf[:GUARD] == 0xFF).all()), 'bytes before the workspace'
+  assert bool((ws_buf[GUARD + nbytes:] == 0xFF).all()), 'bytes after the workspace'
+  assert bool(torch.isnan(dist[B * C:]).all()), 'guard rows of dist'
+  return dist[:B * C].view(B, C, C).cpu().numpy(), ws_buf
+
+
+def test_dg_trials_of_the_workload_shape_in_a_pitch_128_buffer():
+  """(2, 2048, 102) DG trials read through a pitch-128 buffer whose padding
+  holds 7.0: 10 302 pairs on 8192 row slots."""
+  name = 'dg_2x2048x102'
+  sp = _case(name)
+  assert pair_count(sp) > ROW_SLOTS
+  buf = torch.full((2, 2048, 128), 7.0, dtype=torch.float32, device=DEV)
+  buf[:, :, :102] = torch.from_numpy(sp.copy()).to(DEV)
+  x = buf[:, :, :102]
+  assert x.stride() == (2048 * 128, 128, 1)
+  D = _device(x)
+  diff = _bits(D) != _bits(_statement(name))
+  print('%s: %d of %d elements differ' % (name, int(diff.sum()), diff.size))
+  assert not diff.any(), np.argwhere(diff)[:8]
+  _check_structure(D)
+  assert np.array_equal(_bits(_device(x)), _bits(D))
+
+
+@pytest.mark.parametrize('name', ['reuse_3x96x102', 'long_1x2048x6'])
+def test_workspace_of_exactly_the_size_asked_for_between_guards(name):
+  x = torch.from_numpy(_case(name).copy()).to(DEV)
+  D, _ = _entry(x)
+  diff = _bits(D) != _bits(_statement(name))
+  assert not diff.any(), np.argwhere(diff)[:8]
+
+
+def test_slot_reuse_on_a_workspace_an_earlier_call_left():
+  """The second call finds the first call's boundary lines, counts and frames in
+  place of 0xFF: the same bits."""
+  name = 'reuse_3x96x102'
+  x = torch.from_numpy(_case(name).copy()).to(DEV)
+  D1, buf = _entry(x)
+  left = buf.clone()
+  assert bool((left[GUARD:-GUARD] != 0xFF).any())
+  D2, buf = _entry(x, ws_buf=buf)
+  assert np.array_equal(_bits(D1), _bits(_statement(name)))
+  assert np.array_equal(_bits(D2), _bits(D1))
+
+
+@pytest.mark.parametrize('q', [0.0, 1000.0])
+def test_every_pair_index_decodes_at_the_largest_admitted_C(q):
+  """(1, 4, 4096): q = 0 gives |n_i - n_j| and q = 1000 gives n_i + n_j - 2
+  |f_i & f_j| -- small integers, so exact -- at every one of the 8 386 560
+  pairs; `dist` starts as NaN, so an element not written, or written from
+  another pair's (i, j), shows."""
+  sp = _case('decode_1x4x4096')
+  assert sp.shape == (1, 4, 4096)
+  want = counts_difference(sp[0].T) if q == 0 else unmatched_spikes(sp[0].T)
+  assert np.array_equal(want, np.rint(want))          # no non-integer entry
+  D, _ = _entry(torch.from_numpy(sp.copy()).to(DEV), q=q)
+  assert not np.isnan(D).any()
+  diff = _bits(D[0]) != _bits(want)
+  print('q=%g: %d of %d elements differ' % (q, int(diff.sum()), diff.size))
+  assert not diff.any(), np.argwhere(diff)[:8]
+  _check_structure(D)
+
+
+@pytest.mark.parametrize('shape', [(1, 16385, 3), (1, 4, 4097)])
+def test_shapes_past_the_limits_are_refused_with_nothing_written(shape):
+  B, T, C = shape
+  lib = _lib.load()
+  assert lib.cg_victor_purpura_ws_bytes(B, T, C) == -1
+  assert lib.cg_victor_purpura_ws_bytes(B, min(T, 16384), min(C, 4096)) > 0
+  x = torch.ones(shape, dtype=torch.float32, device=DEV)
+  nbytes = 4 << 20     # (more than either shape would need, were it admitted)
+  ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=DEV)
+  dist = torch.full((B, C, C), float('nan'), dtype=torch.float64, device=DEV)
+  rc = lib.cg_victor_purpura(nets._p(x), B, T, C, x.stride(0), x.stride(1),
+                             x.stride(2), spike_metrics.victor_purpura_cost(1.0),
+                             nets._p(dist), nets._p(ws), nbytes, nets._stream())
+  torch.cuda.synchronize()
+  assert rc == _lib.CG_EINVAL
+  assert bool(torch.isnan(dist).all()) and bool((ws == 0xFF).all())
+  with pytest.raises(ValueError):
+    spike_metrics.victor_purpura_distance_device(x)
 
 
 def test_wrapper_refuses_host_arrays_wrong_dtype_and_rank():

@@ -12,6 +12,8 @@ import compute_dg_metrics as cdm
 from calciumgan_amd.data import dg
 from calciumgan_amd.gan.utils import h5_helper, spike_helper, spike_metrics
 
+import spike_stats_cases as SC
+
 
 def test_oasis_c_matches_python_restatement():
   rng = np.random.RandomState(0)
@@ -70,6 +72,77 @@ def test_firing_rate_and_covariance_definitions():
   cross = spike_metrics.covariance(sp[:1], sp[1:])
   assert cross.shape == (1, 1)
   np.testing.assert_allclose(cross[0, 0], np.cov(counts)[1, 0])
+
+
+def _tie_exact_covariance(sp):
+  """exact_covariance against batch_statistics by the rule of the GPU test
+  test_statistics_against_spike_metrics: entries whose exact value is 0 -- below
+  half of the smallest non-zero magnitude 1 / (nb (nb - 1)) on the host -- are
+  exactly 0 in the statement, wherever the host has 0 the statement has 0, all
+  others agree to rtol = 1e-6."""
+  nb = sp.shape[1] // 12
+  _, want = spike_metrics.batch_statistics(SC.binary(sp))
+  got = SC.exact_covariance(sp)
+  assert got.dtype == np.float32 and got.shape == want.shape
+  zero = np.abs(want) < 0.5 / (nb * (nb - 1))
+  assert np.abs(want[zero]).max() < 1e-12
+  assert np.all(got[want == 0] == 0) and np.all(got[zero] == 0)
+  np.testing.assert_allclose(got[~zero], want[~zero], rtol=1e-6, atol=0)
+  assert (~zero).sum() > 0
+  return got
+
+
+def test_exact_covariance_statement_against_batch_statistics():
+  for T, C in SC.GRID:
+    _tie_exact_covariance(SC.trains(3, T, C, seed=T + C))
+  for name in SC.SHAPES:
+    _tie_exact_covariance(SC.stats_case(name))
+
+
+def test_exact_covariance_by_hand_and_the_planted_trains():
+  sp = np.zeros((1, 48, 2), np.float32)
+  sp[0, [0, 5, 13, 30], 0] = 1
+  sp[0, [1, 14, 15, 40, 41, 42], 1] = 1
+  # counts [2, 1, 1, 0] and [1, 2, 0, 3]: S = 4, 6; S_00 = 6, S_01 = 4, S_11 = 14
+  want = np.array([[4 * 6 - 16, 4 * 4 - 24, 4 * 14 - 36]], np.float64) / 12.0
+  assert np.array_equal(SC.exact_covariance(sp), want.astype(np.float32))
+  sp = SC.stats_case('planted_c6_t48')
+  assert np.isnan(sp).sum() == 2 and (sp == np.float32(2.0**-149)).sum() == 2
+  cov = SC.exact_covariance(sp)
+  iu = np.triu_indices(6)
+  # a train that fires in every frame, and one that never does, vary with none
+  assert np.all(cov[:, (iu[0] == 0) | (iu[0] == 2) | (iu[1] == 2)] == 0)
+  assert np.all(cov[:, (iu[0] == 1) & (iu[1] == 1)] > 0)
+  rates, _ = spike_metrics.batch_statistics(SC.binary(sp))
+  assert np.array_equal(rates[:, :3], [[24.0, 2.0, 0.0], [24.0, 1.5, 0.0]])
+
+
+def test_statistics_cases_reach_what_they_are_for():
+  lds = {n: SC.lds_bytes(*SC.SHAPES[n]) for n in SC.SHAPES}
+  assert lds['c300_t2405'] == 61200 and lds['c240_t3029'] == 61440 == SC.STATS_MAX_LDS
+  assert [SC.lds_bytes(T, C) for T, C in SC.REFUSED] == [61680, 61500]
+  assert all(SC.lds_bytes(T - 12, C) <= SC.STATS_MAX_LDS for T, C in SC.REFUSED)
+  assert [SC.split(C) for C in (44, 45, 119, 120, 240, 300)] == [1, 2, 7, 8, 8, 8]
+  assert 300 * 301 // 2 == 45150 > 8 * 4 * SC.STATS_THREADS
+  assert 2405 % 12 == 5 and 3029 // 12 == 252
+  # the error kernel's grid
+  assert SC.err_parts(3, 2097152) == 1024 == -(-2097152 // 2048)
+  assert SC.err_parts(3, 2097152 + 257) == 1024 < -(-(2097152 + 257) // 2048)
+  assert SC.err_parts(0, 5) == 1 and SC.err_parts(2049, 2047) == 2
+  for n_fr, n_cov in SC.ERROR_SIZES:
+    ra, rb, ca, cb = SC.planted_error_inputs(n_fr, n_cov)
+    parts = SC.err_parts(n_fr, n_cov)
+    for a, b, n in ((ra, rb, n_fr), (ca, cb, n_cov)):
+      idx = np.nonzero(a != b)[0]
+      assert sorted(idx) == sorted(SC.planted_indices(n, parts))
+      if n:
+        assert 0 in idx and n - 1 in idx
+      if n > parts * 256:
+        assert parts * 256 - 1 in idx and parts * 256 in idx and 255 in idx
+    sums = spike_metrics.error_sums(ra, rb, ca, cb)
+    # every sum is a float32
+    assert np.array_equal(sums, sums.astype(np.float32).astype(np.float64))
+    assert (sums[0] > 0) == (n_fr > 0) and (sums[2] > 0) == (n_cov > 0)
 
 
 def test_dg_metrics_report(tmp_path):

@@ -18,8 +18,10 @@ from calciumgan_amd import build as cg_build
 from calciumgan_amd.data import dg
 from calciumgan_amd.gan.utils import h5_helper, spike_metrics
 from van_rossum_cases import dg_trial
-from victor_purpura_cases import (QS, counts_difference, crafted_trial, first_set,
-                                  second_set, unmatched_spikes)
+from victor_purpura_cases import (GRID_CASES, QS, ROW_SLOTS, counts_difference,
+                                  crafted_trial, double_loop_pair, first_set,
+                                  grid_case, pair_count, second_set,
+                                  unmatched_spikes)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'calciumgan_hip.h')
@@ -109,6 +111,82 @@ def test_statement_runs_a_whole_trial_at_the_flagship_shape():
   got = d[np.ix_(few, few)]
   assert np.all(np.abs(got - want) <= 3 * (n[few][:, None] + n[few][None, :]) *
                 U * want)
+
+
+def test_grid_cases_are_what_their_names_say():
+  shapes = {n: grid_case(n).shape for n in GRID_CASES}
+  assert shapes == {'reuse_3x96x102': (3, 96, 102), 'reuse_40x48x27': (40, 48, 27),
+                    'long_1x2048x6': (1, 2048, 6),
+                    't16384_1x16384x3': (1, 16384, 3),
+                    'dg_2x2048x102': (2, 2048, 102),
+                    'decode_1x4x4096': (1, 4, 4096)}
+  for name in GRID_CASES:
+    sp = grid_case(name)
+    assert sp.dtype == np.float32 and set(np.unique(sp)) <= {0.0, 1.0}
+  sp = grid_case('reuse_3x96x102')
+  assert pair_count(sp) == 15453 and pair_count(sp) - ROW_SLOTS == 7261
+  n = sp.sum(1)
+  assert np.all((n == 0).sum(1) >= 1) and np.all((n == 96).sum(1) >= 1)
+  # most pairs need two to six strips of 16 columns of the shorter train
+  I, J = np.triu_indices(102, k=1)
+  strips = (np.minimum(n[:, I], n[:, J]) + 15) // 16
+  assert ((strips >= 2) & (strips <= 6)).mean() > 0.5
+  sp = grid_case('reuse_40x48x27')
+  assert pair_count(sp) == 14040 > ROW_SLOTS and (27 * 26 // 2) % 4 != 0
+  assert pair_count(grid_case('dg_2x2048x102')) == 10302 > ROW_SLOTS
+  assert pair_count(grid_case('decode_1x4x4096')) == 8386560
+  sp = grid_case('t16384_1x16384x3')[0]
+  assert sp[0, 0] == 1 and sp[16383, 0] == 1 and sp[16383, 2] == 1
+  assert sp[255, 1] == 1 and sp[256, 1] == 1 and sp[256, 2] == 1
+  assert np.all(np.abs(sp.mean(0) - 0.02) < 0.005)
+
+
+# (case, trial, i, j): a handful of pairs per case for the plain double loop --
+# silent / full / ordinary trains, the last pair of a trial, and the longest
+# pair of the long-train case (2048 against 1024 spikes, 2 M cells)
+LOOP_PAIRS = (
+    ('reuse_3x96x102', 0, 0, 1), ('reuse_3x96x102', 0, 1, 2),
+    ('reuse_3x96x102', 1, 37, 90), ('reuse_3x96x102', 2, 100, 101),
+    ('reuse_40x48x27', 0, 0, 1), ('reuse_40x48x27', 23, 12, 26),
+    ('reuse_40x48x27', 39, 25, 26),
+    ('long_1x2048x6', 0, 0, 1), ('long_1x2048x6', 0, 1, 3),
+    ('long_1x2048x6', 0, 3, 4), ('long_1x2048x6', 0, 0, 5),
+    ('t16384_1x16384x3', 0, 0, 1), ('t16384_1x16384x3', 0, 1, 2),
+    ('dg_2x2048x102', 0, 3, 77), ('dg_2x2048x102', 1, 100, 101),
+    ('decode_1x4x4096', 0, 0, 4095), ('decode_1x4x4096', 0, 2047, 2048),
+)
+
+
+def test_statement_against_the_plain_double_loop_on_the_grid_cases():
+  """Bit for bit: the double loop performs the statement's operations."""
+  qf = spike_metrics.victor_purpura_cost(1.0)
+  for name, b, i, j in LOOP_PAIRS:
+    trial = grid_case(name)[b].T                       # (C, T)
+    got = vp(trial[[i, j]])
+    want = double_loop_pair(trial[i], trial[j], qf)
+    assert _bits(got[0, 1]) == _bits(want) and _bits(got[1, 0]) == _bits(want), (
+        name, b, i, j, got[0, 1], want)
+  # the whole trial gives the pair what the two trains alone give it
+  trial = grid_case('reuse_3x96x102')[1].T
+  assert _bits(vp(trial)[37, 90]) == _bits(
+      double_loop_pair(trial[37], trial[90], qf))
+  # and the longest pair is worth running: its distance is no count difference
+  long_ = grid_case('long_1x2048x6')[0].T
+  assert vp(long_[:2])[0, 1] == 1024.0
+  assert vp(long_[[1, 2]])[0, 1] > abs(long_[1].sum() - long_[2].sum())
+
+
+def test_closed_forms_on_a_slice_of_the_decode_case():
+  sp = grid_case('decode_1x4x4096')[0].T[:64]         # (64, 4)
+  assert np.array_equal(_bits(vp(sp, q=0.0)), _bits(counts_difference(sp)))
+  want = unmatched_spikes(sp)
+  assert np.array_equal(want, np.rint(want))
+  assert np.array_equal(_bits(vp(sp, q=1000.0)), _bits(want))
+  # the whole case: the forms hold small integers only
+  full = grid_case('decode_1x4x4096')[0].T
+  for form in (counts_difference(full), unmatched_spikes(full)):
+    assert form.shape == (4096, 4096) and np.array_equal(form, np.rint(form))
+    assert form.min() == 0 and form.max() <= 8
 
 
 def test_header_signatures_and_both_libraries_carry_the_entry_points():
