@@ -1,22 +1,29 @@
-"""ctypes binding of the C ABI in include/calciumgan_hip.h.
+"""ctypes binding of the C ABI in include/calciumgan_hip.h, derived from that
+header at import: its prototypes, descriptor structs and CG_* constants are
+written down nowhere else in Python.
 
 The HIP library is the ONLY compute path of this package: if it is missing or
 fails to load, every op raises (there is no CPU / eager fallback).
 """
 import ctypes as C
 import os
+import re
+
+# torch before the library is loaded: its wheel bundles a HIP runtime, and the
+# library must bind to THAT copy -- loaded before torch, it pulled in
+# /opt/rocm's libamdhip64 and the process ended up with two runtimes (first
+# launch: hipErrorNoDevice)
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER = os.path.normpath(
+    os.path.join(_HERE, '..', 'include', 'calciumgan_hip.h'))
 # CALCIUMGAN_HIP_LIB points at another build of the same C ABI (development)
 LIB_PATH = os.environ.get('CALCIUMGAN_HIP_LIB') or os.path.join(
     _HERE, 'csrc', 'libcalciumgan_hip.so')
 # the same sources with fp16 activations: the reference's mixed_float16 mode
 LIB_PATH_F16 = os.environ.get('CALCIUMGAN_HIP_LIB_F16') or os.path.join(
     _HERE, 'csrc', 'libcalciumgan_hip_f16.so')
-DTYPE_BF16, DTYPE_F16 = 0, 1
-
-CG_EINVAL = 100001
-EPI_NONE, EPI_LRELU, EPI_MASK, EPI_SIGMOID, EPI_LN_LRELU = 0, 1, 2, 3, 4
 # CG_TILE_*: value -> (rows, cols, mfma rows)
 TILES = {0: (256, 64, 16), 1: (64, 64, 16), 2: (128, 64, 16),
          3: (256, 64, 32), 4: (128, 64, 32), 5: (256, 128, 32),
@@ -32,189 +39,135 @@ def tile_shape(tile):
   return TILES[tile][:2] if tile in TILES else SWP_TILES[tile]
 
 
-c_vp = C.c_void_p
-c_i = C.c_int
-c_ll = C.c_longlong
-c_f = C.c_float
-c_d = C.c_double
+class HipLibraryError(RuntimeError):
+  pass
 
 
-class ConvDesc(C.Structure):
-  """struct cg_conv_desc."""
-  _fields_ = [
-      ('x', c_vp), ('w', c_vp), ('y', c_vp), ('bias', c_vp), ('mask_src', c_vp),
-      ('shifts', c_vp),
-      ('nB', c_i), ('Lx', c_i), ('Cx', c_i), ('seg_size', c_i),
-      ('taps', c_i), ('stride', c_i), ('off', c_i), ('Lu', c_i),
-      ('N', c_i), ('Ly', c_i), ('Cy', c_i), ('y_stride', c_i), ('y_off', c_i),
-      ('CK', c_i),
-      ('epilogue', c_i), ('out_f32', c_i),
-      ('alpha', c_f),
-      ('nphase', c_i),
-      ('w_phase_stride', c_ll),
-      ('off_phase_step', c_i), ('yoff_phase_step', c_i),
-      ('tile', c_i),
-      ('stage_ksteps', c_i),
-      ('rowsumsq', c_vp),
-      ('w_parity_major', c_i),
-      ('split_parity', c_i),
-      ('ln_gamma', c_vp), ('ln_beta', c_vp), ('ln_h', c_vp),
-      ('ln_mean', c_vp), ('ln_rstd', c_vp), ('ln_eps', c_f),
-      ('w_narrow_last', c_i),
-      ('out_shifts', c_vp), ('out_seg_size', c_i), ('side', c_vp),
-      ('side_rows', c_i),
-      ('ksplit', c_i), ('split_ws', c_vp), ('split_ws_elems', c_ll),
-      ('row_scale', c_vp),
-      ('rowsumsq_ws', c_vp), ('rowsumsq_ws_elems', c_ll),
-      ('rowsumsq_defer', c_i),
-  ]
+class DataPtr(C.c_void_p):
+  """Argtype of a `[const] void|float|double|int *` parameter.  Takes a torch
+  tensor as its data_ptr() once its dtype matches the element type (`void*`
+  takes any; device and contiguity are the caller's business: several entry
+  points take host buffers), None as NULL, and whatever c_void_p itself takes:
+  ctypes arrays, byref(...), pointer instances, ints."""
 
 
-class PackDesc(C.Structure):
-  """struct cg_pack_desc."""
-  _fields_ = [
-      ('src', c_vp), ('dst', c_vp),
-      ('taps', c_i), ('tap0', c_i), ('tap_step', c_i),
-      ('s_tap', c_ll), ('s_c', c_ll), ('s_n', c_ll),
-      ('C_real', c_i), ('N_real', c_i), ('Cx', c_i), ('CK', c_i),
-      ('parity_major', c_i),
-      ('narrow_last', c_i),
-  ]
+def _data_ptr(ctype, dtype):
+  # (closed-over names, not class attributes: this runs once per pointer
+  # argument of every launch)
+  tensor, address, other = torch.Tensor, C.c_void_p, C.c_void_p.from_param
+
+  def from_param(cls, obj):
+    if not isinstance(obj, tensor):
+      return other(obj)
+    if dtype is not None and obj.dtype is not dtype:
+      raise TypeError('a {} parameter takes a {} tensor, not {}'.format(
+          ctype, dtype, obj.dtype))
+    return address(obj.data_ptr())
+
+  return type('DataPtr_' + ctype[:-1], (DataPtr,), {
+      'ctype': ctype, 'dtype': dtype, 'from_param': classmethod(from_param)})
 
 
-class WgradDesc(C.Structure):
-  """struct cg_wgrad_desc."""
-  _fields_ = [
-      ('x', c_vp), ('g', c_vp), ('dw', c_vp), ('shifts', c_vp),
-      ('nB', c_i), ('Lx', c_i), ('Cx', c_i), ('seg_size', c_i),
-      ('Lu', c_i), ('Cg', c_i),
-      ('taps', c_i), ('stride', c_i), ('off', c_i),
-      ('Cx_real', c_i), ('Cg_real', c_i),
-      ('nsplit', c_i),
-      ('tile_rows', c_i),
-      ('no_xcd_group', c_i),
-      ('classic_staging', c_i),
-      ('dbias', c_vp),
-      ('bias_rows', c_ll),
-      ('partials', c_vp),
-      ('partials_elems', c_ll),
-      ('store', c_i),
-  ]
+_SCALARS = {'int': C.c_int, 'long long': C.c_longlong, 'float': C.c_float,
+            'double': C.c_double}
+_DATA_PTRS = {'void': _data_ptr('void*', None),
+              'float': _data_ptr('float*', torch.float32),
+              'double': _data_ptr('double*', torch.float64),
+              'int': _data_ptr('int*', torch.int32)}
 
 
-# name -> argtypes (restype is int unless listed in _RESTYPES)
-SIGNATURES = {
-    'cg_abi_version': [],
-    'cg_act_dtype': [],
-    'cg_struct_size': [c_i],
-    'cg_tile_shape': [c_i, C.POINTER(c_i), C.POINTER(c_i)],
-    'cg_debug_lean_epilogue': [c_i],
-    'cg_debug_wgrad_flex': [c_i],
-    'cg_wgrad_flex_plan': [C.POINTER(WgradDesc), c_i, c_i, C.POINTER(c_i), c_ll,
-                           C.POINTER(c_i)],
-    'cg_profile_enable': [c_i],
-    'cg_profile_collect': [C.POINTER(c_f), C.POINTER(c_i), c_i],
-    'cg_swconv': [C.POINTER(ConvDesc), c_vp],
-    'cg_swconv_check': [C.POINTER(ConvDesc)],
-    'cg_rowsumsq_ws_elems': [C.POINTER(ConvDesc)],
-    'cg_reduce_ws_elems': [],
-    'cg_finish_defer': [c_i],
-    'cg_finish_flush': [c_vp],
-    'cg_dense_rows': [c_vp, c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_i, c_i, c_vp],
-    'cg_dense_rows_interp': [c_vp, c_vp, c_vp, c_vp, c_vp, C.POINTER(c_vp), c_i, c_i,
-                             c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
-    'cg_dense_rows_act': [c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_i, c_vp],
-    'cg_dense_wgrad': [c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_i, c_i, c_vp, c_ll,
-                       c_vp],
-    'cg_dense_wgrad_ws_elems': [c_ll, c_i, c_i],
-    'cg_packed_elems': [c_i, c_i, c_i, c_i],
-    'cg_pack_weights': [C.POINTER(PackDesc), c_vp],
-    'cg_pack_plan_bytes': [c_i, c_ll],
-    'cg_pack_plan_build': [C.POINTER(PackDesc), c_i, c_vp, c_ll],
-    'cg_pack_batched': [c_vp, c_i, c_ll, c_vp],
-    'cg_wgrad': [C.POINTER(WgradDesc), c_vp],
-    'cg_wgrad_batched': [C.POINTER(WgradDesc), c_i, c_vp],
-    'cg_wgrad_partials_elems': [C.POINTER(WgradDesc)],
-    'cg_ln_lrelu_fwd': [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_f,
-                        c_f, c_vp],
-    'cg_ln_lrelu_bwd': [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                        c_vp, c_ll, c_i, c_i, c_f, c_vp, c_vp],
-    'cg_bn_stats': [c_vp, c_ll, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_f, c_vp, c_vp],
-    'cg_bn_apply': [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_f, c_f,
-                    c_vp],
-    'cg_bn_bwd': [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_i,
-                  c_i, c_f, c_f, c_i, c_vp, c_vp],
-    'cg_dense1_fwd': [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp],
-    'cg_dense1_fwd_bwd': [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i,
-                          c_i, c_f, c_vp],
-    'cg_dense1_bce': [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                      c_vp, c_i, c_i, c_i, c_i, c_f, c_vp, c_vp],
-    'cg_gp_critic_loss': [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_i, c_f, c_vp],
-    'cg_gp_loss_scale': [c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f,
-                         c_vp, c_vp, c_ll, c_vp],
-    'cg_dense1_bwd': [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f,
-                      c_vp],
-    'cg_dense1_wgrad': [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i,
-                        c_vp, c_vp],
-    'cg_unshuffle_mask': [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_f,
-                          c_vp],
-    'cg_unshuffle_fixup': [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f,
-                           c_vp],
-    'cg_interp_pack': [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i,
-                       c_i, c_vp],
-    'cg_cast_pad': [c_vp, c_vp, c_ll, c_i, c_i, c_i, c_vp],
-    'cg_rownorm': [c_vp, c_vp, c_i, c_ll, c_vp, c_vp],
-    'cg_gp_finalize': [c_vp, c_vp, c_vp, c_i, c_f, c_i, c_vp],
-    'cg_scale_rows': [c_vp, c_vp, c_vp, c_i, c_ll, c_vp],
-    'cg_critic_loss': [c_vp, c_vp, c_f, c_vp, c_i, c_vp],
-    'cg_neg_mean': [c_vp, c_vp, c_i, c_vp],
-    'cg_colsum': [c_vp, c_vp, c_ll, c_i, c_i, c_vp, c_vp],
-    'cg_sigmoid_bwd': [c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_i, c_vp],
-    'cg_lrelu_bwd': [c_vp, c_vp, c_vp, c_ll, c_f, c_vp],
-    'cg_lrelu_mix': [c_vp, c_vp, c_vp, c_vp, c_i, c_ll, c_f, c_vp],
-    'cg_adam': [c_vp, c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_f, c_f, c_vp,
-                c_vp],
-    'cg_grad_finite': [c_vp, c_ll, c_vp, c_vp],
-    'cg_adam_scaled': [c_vp, c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_f, c_f,
-                       c_vp, c_vp],
-    'cg_loss_scale_update': [c_vp, c_i, c_vp],
-    'cg_signal_metrics': [c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_i, c_f, c_f,
-                          c_vp, c_vp],
-    'cg_step_outputs': [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp],
-    # spikes.hip: deconvolution and spike statistics during validation
-    'cg_oasis_ws_bytes': [c_ll, c_i],
-    'cg_oasis_ar1_batched': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_f, c_f,
-                             c_d, c_d, c_d, c_vp, c_vp, c_ll, c_ll, c_ll, c_vp,
-                             c_vp, c_vp, c_ll, c_vp],
-    'cg_spike_stats': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_vp, c_vp, c_vp],
-    'cg_spike_stats_error_ws_elems': [c_ll, c_ll],
-    'cg_spike_stats_error': [c_vp, c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_vp,
-                             c_vp],
-    # van_rossum.hip / spikes.hip: per-trial statistics of compute_metrics.py
-    'cg_van_rossum': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_d, c_vp, c_vp,
-                      c_vp],
-    'cg_spike_corrcoef': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_vp, c_vp],
-    # victor_purpura.hip: the edit distances between the trains of a trial
-    'cg_victor_purpura_ws_bytes': [c_i, c_i, c_i],
-    'cg_victor_purpura': [c_vp, c_i, c_i, c_i, c_ll, c_ll, c_ll, c_d, c_vp, c_vp,
-                          c_ll, c_vp],
-    # pair_hist.hip: the histogram counts behind the KL figures of the report
-    'cg_pair_histogram': [c_vp, c_ll, c_ll, c_ll, c_vp, c_ll, c_ll, c_ll, c_i,
-                          c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp],
-}
-_RESTYPES = {'cg_packed_elems': c_ll, 'cg_pack_plan_bytes': c_ll,
-             'cg_pack_plan_build': c_ll, 'cg_wgrad_partials_elems': c_ll,
-             'cg_dense_wgrad_ws_elems': c_ll, 'cg_rowsumsq_ws_elems': c_ll,
-             'cg_reduce_ws_elems': c_ll, 'cg_wgrad_flex_plan': c_ll,
-             'cg_oasis_ws_bytes': c_ll, 'cg_spike_stats_error_ws_elems': c_ll,
-             'cg_victor_purpura_ws_bytes': c_ll}
+def _unknown(decl):
+  raise HipLibraryError('calciumgan_amd: no ctypes binding for this '
+                        'declaration of {}: "{}"'.format(
+                            HEADER, ' '.join(decl.split())))
+
+
+def _declarator(text, structs, decl, field=False):
+  """(ctypes type, name) of one `type name`; `decl` is what an error quotes."""
+  *tokens, name = text.replace('*', ' * ').split() or ['']
+  if tokens[:1] == ['const']:
+    tokens = tokens[1:]
+  spelled = ' '.join(tokens)
+  if not re.fullmatch(r'[A-Za-z_]\w*', name):
+    _unknown(decl)
+  if spelled in _SCALARS:
+    return _SCALARS[spelled], name
+  if spelled == 'void * const *':  # a host table of device pointers
+    return C.POINTER(C.c_void_p), name
+  if spelled[:-2] in structs and spelled.endswith(' *'):
+    return C.POINTER(structs[spelled[:-2]]), name
+  if spelled[:-2] in _DATA_PTRS and spelled.endswith(' *'):
+    # (a struct field is assigned an address, never a tensor)
+    return (C.c_void_p if field else _DATA_PTRS[spelled[:-2]]), name
+  _unknown(decl)
+
+
+def parse_header(text):
+  """(constants, structs, prototypes) of a header written like
+  calciumgan_hip.h: `#define CG_NAME integer`, `typedef struct cg_x_desc {...}
+  cg_x_desc;` and `int|long long cg_name(...);`.  name -> int, name ->
+  ctypes.Structure, name -> (argtypes, restype).  Anything else raises."""
+  text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+  text = re.sub(r'#\s*ifdef\s+__cplusplus\b.*?#\s*endif', ' ', text, flags=re.S)
+  constants, structs, protos = {}, {}, {}
+  for line in re.findall(r'^[ \t]*#[ \t]*define[ \t]+CG_.*$', text, re.M):
+    m = re.fullmatch(r'\s*#\s*define\s+(CG_\w+)\s+(-?\d+)\s*', line)
+    if not m:
+      _unknown(line)
+    constants[m.group(1)] = int(m.group(2))
+  text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)
+
+  def struct(m):
+    tag, body, name = m.groups()
+    fields = []
+    for decl in filter(str.strip, body.split(';')):
+      first, *more = decl.split(',')  # `int nB, Lx, Cx;`
+      ctype, fname = _declarator(first, structs, decl, field=True)
+      for other in more:
+        if not re.fullmatch(r'\s*[A-Za-z_]\w*\s*', other):
+          _unknown(decl)
+      fields += [(n.strip(), ctype) for n in [fname] + more]
+    if tag != name or not fields:
+      _unknown(m.group(0))
+    cls = ''.join(w.title() for w in name.split('_')[1:])  # cg_conv_desc: ConvDesc
+    structs[name] = type(cls, (C.Structure,), {
+        '_fields_': fields, '__doc__': 'struct {}.'.format(name)})
+    return ' '
+
+  text = re.sub(r'typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;', struct,
+                text)
+  for decl in filter(str.strip, text.split(';')):
+    m = re.fullmatch(r'\s*(int|long\s+long)\s+(\w+)\s*\(([^()]*)\)\s*', decl)
+    if not m:
+      _unknown(decl)
+    params = [] if m.group(3).strip() == 'void' else m.group(3).split(',')
+    protos[m.group(2)] = ([_declarator(p, structs, decl)[0] for p in params],
+                          _SCALARS[' '.join(m.group(1).split())])
+  return constants, structs, protos
+
+
+def _read_header():
+  try:
+    with open(HEADER) as f:
+      return f.read()
+  except OSError as e:
+    raise HipLibraryError('calciumgan_amd: cannot read the C header {}: {}'
+                          .format(HEADER, e))
+
+
+CONSTANTS, STRUCTS, _PROTOS = parse_header(_read_header())
+CG_EINVAL, CG_ABI_VERSION = CONSTANTS['CG_EINVAL'], CONSTANTS['CG_ABI_VERSION']
+EPI_NONE, EPI_LRELU, EPI_MASK, EPI_SIGMOID, EPI_LN_LRELU = (
+    CONSTANTS['CG_EPI_' + n]
+    for n in ('NONE', 'LRELU', 'MASK', 'SIGMOID', 'LN_LRELU'))
+DTYPE_BF16, DTYPE_F16 = CONSTANTS['CG_DTYPE_BF16'], CONSTANTS['CG_DTYPE_F16']
+# in the order of cg_struct_size(which)
+ConvDesc, PackDesc, WgradDesc = (
+    STRUCTS[n] for n in ('cg_conv_desc', 'cg_pack_desc', 'cg_wgrad_desc'))
+SIGNATURES = {name: argtypes for name, (argtypes, _) in _PROTOS.items()}
 
 _libs = {}       # precision -> ctypes handle
 _active = 'bf16'  # precision of the library `call` / `load()` address
-
-
-class HipLibraryError(RuntimeError):
-  pass
 
 
 def use(precision):
@@ -240,10 +193,6 @@ def load(precision=None):
   precision = precision or _active
   if precision in _libs:
     return _libs[precision]
-  # torch first: its wheel bundles a HIP runtime, and the library must bind to
-  # THAT copy -- loaded before torch, it pulled in /opt/rocm's libamdhip64 and
-  # the process ended up with two runtimes (first launch: hipErrorNoDevice)
-  import torch  # noqa: F401
   path = LIB_PATH_F16 if precision == 'f16' else LIB_PATH
   if not os.path.exists(path):
     raise HipLibraryError(
@@ -254,11 +203,16 @@ def load(precision=None):
     lib = C.CDLL(path)
   except OSError as e:
     raise HipLibraryError('calciumgan_amd: cannot load {}: {}'.format(path, e))
-  for name, argtypes in SIGNATURES.items():
+  for name, (argtypes, restype) in _PROTOS.items():
     fn = getattr(lib, name)  # AttributeError if the symbol is missing
     fn.argtypes = argtypes
-    fn.restype = _RESTYPES.get(name, c_i)
-  # the ctypes mirrors of the descriptor structs must match the compiled header
+    fn.restype = restype
+  if lib.cg_abi_version() != CG_ABI_VERSION:
+    raise HipLibraryError(
+        'calciumgan_amd: ABI version {} in the header, {} in {} -- stale build '
+        'or binding (rebuild with `python -m calciumgan_amd.build`)'.format(
+            CG_ABI_VERSION, lib.cg_abi_version(), path))
+  # the structs as parsed from the header must match the ones the compiler laid out
   for which, cls in enumerate((ConvDesc, PackDesc, WgradDesc)):
     if lib.cg_struct_size(which) != C.sizeof(cls):
       raise HipLibraryError(
@@ -284,5 +238,13 @@ def check(rc, what):
 def call(name, *args):
   """Invoke an int-returning entry point of the active build and raise on a
   non-zero code."""
-  rc = getattr(load(), name)(*args)
+  try:
+    rc = getattr(load(), name)(*args)
+  except C.ArgumentError as e:  # "argument 3: TypeError: a float* parameter..."
+    raise TypeError('{}: {}'.format(name, e)) from None
   check(rc, name)
+
+
+def stream():
+  """The current torch stream as the `void* stream` argument."""
+  return C.c_void_p(torch.cuda.current_stream().cuda_stream)

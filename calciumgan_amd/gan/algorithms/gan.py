@@ -104,9 +104,8 @@ class GAN(object):
       buf = torch.empty(4, dtype=torch.float32, device=self.device)
     else:
       buf = torch.zeros(4, dtype=torch.float32, device=self.device)
-    _lib.call('cg_signal_metrics', nets._p(real), nets._p(fake), nets._p(buf),
-              rows, C, C, fake_pitch or C, self._signals_min,
-              self._signals_max, nets._p(rws), nets._stream())
+    _lib.call('cg_signal_metrics', real, fake, buf, rows, C, C, fake_pitch or C,
+              self._signals_min, self._signals_max, rws, _lib.stream())
     if rws is None:
       buf.mul_(1.0 / rows)
     return {
@@ -219,29 +218,26 @@ class GAN(object):
     B = real.shape[0]
     lay, last = net_d.layers[0], net_d.layers[-1]
     dws, pd = st['dws'], st['dis']
-    s = nets._stream()
+    s = _lib.stream()
     if shifts is not None:
       st['stage_dev'][:12].copy_(shifts)
     fake = st['gws'].forward(z, keep=training, training=training)
     x0 = pd.x0
-    _lib.call('cg_cast_pad', nets._p(fake), nets._p(x0), B * lay.lin, lay.cin,
-              net_g.Cf, lay.cinp, s)
-    _lib.call('cg_cast_pad', nets._p(real), nets._p(x0[B:2 * B]), B * lay.lin,
-              lay.cin, lay.cin, lay.cinp, s)
+    _lib.call('cg_cast_pad', fake, x0, B * lay.lin, lay.cin, net_g.Cf, lay.cinp,
+              s)
+    _lib.call('cg_cast_pad', real, x0[B:2 * B], B * lay.lin, lay.cin, lay.cin,
+              lay.cinp, s)
     pd.forward(head=False)
     rws = nets.reduce_ws(self.device)
     if rws is None:
       st['loss'].zero_()  # (the atomics form adds onto it)
     sd = self.dis_optimizer.loss_scale if seeds else None
     sg = self.gen_optimizer.loss_scale if seeds else None
-    _lib.call('cg_dense1_bce', nets._p(dws.act[-1]), nets._p(net_d.dense_w),
-              nets._p(net_d.dense_b), nets._p(dws.d_out),
-              nets._p(st['coef_d'] if seeds else None),
-              nets._p(st['coef_g'] if seeds else None),
-              nets._p(dws.delta[-1] if seeds else None),
-              nets._p(st['delta_g'] if seeds else None), nets._p(st['loss']),
-              nets._p(sd), nets._p(sg), B, last.lout, last.cout, last.coutp,
-              net_d.alpha, nets._p(rws), s)
+    _lib.call('cg_dense1_bce', dws.act[-1], net_d.dense_w, net_d.dense_b,
+              dws.d_out, st['coef_d'] if seeds else None,
+              st['coef_g'] if seeds else None, dws.delta[-1] if seeds else None,
+              st['delta_g'] if seeds else None, st['loss'], sd, sg, B,
+              last.lout, last.cout, last.coutp, net_d.alpha, rws, s)
     return fake
 
   def _bce_compute(self, real, r=None):
@@ -291,9 +287,8 @@ class GAN(object):
   def _bce_outputs(self, st, metrics):
     """[gen_loss, dis_loss, 0, metrics x 4] into the state's out buffer."""
     loss = st['loss']
-    _lib.call('cg_step_outputs', nets._p(loss[0:1]), nets._p(loss[1:2]),
-              nets._p(st['zero']), nets._p(metrics[_METRIC_KEYS[0]]), 1,
-              nets._p(st['out']), nets._stream())
+    _lib.call('cg_step_outputs', loss[0:1], loss[1:2], st['zero'],
+              metrics[_METRIC_KEYS[0]], 1, st['out'], _lib.stream())
     return st['out']
 
   def _outputs(self, o):

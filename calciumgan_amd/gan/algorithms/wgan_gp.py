@@ -171,7 +171,7 @@ class WGAN_GP(GAN):
     B = real.shape[0]
     lay = net_d.layers[0]
     plan = st['critic'] if plan is None else plan
-    s = nets._stream()
+    s = _lib.stream()
     # (host-drawn shifts of an eager step are a pageable temporary: a
     # non-blocking copy could read it after it is gone once the host runs ahead
     # of the GPU; the graph path hands a device view)
@@ -182,10 +182,10 @@ class WGAN_GP(GAN):
       if fake is None:
         fake = st['gws'].forward(z, keep=False, training=training)
       # (a plan that mixes layer 1 of x^ never reads x^: [real | fake] only)
-      _lib.call('cg_interp_pack', nets._p(real), nets._p(fake),
-                nets._p(None if plan.mixes_layer1 else alpha),
-                nets._p(plan.x0), B, lay.lin, lay.cin, lay.cin,
-                self.generator.net.Cf, lay.cinp, 0 if real_cached else 1, s)
+      _lib.call('cg_interp_pack', real, fake,
+                None if plan.mixes_layer1 else alpha, plan.x0, B, lay.lin,
+                lay.cin, lay.cin, self.generator.net.Cf, lay.cinp,
+                0 if real_cached else 1, s)
     plan.forward(seed_backward=True,
                  mix=alpha.reshape(-1) if plan.mixes_layer1 else None)
     plan.backward_chain(seeded=True)
@@ -196,10 +196,9 @@ class WGAN_GP(GAN):
       norm = plan.sumsq
       slots, P = plan.ssq
       g, dst, ns = scale if scale is not None else (None, None, 0)
-      _lib.call('cg_gp_loss_scale', nets._p(slots), P, nets._p(norm),
-                nets._p(st['gp'][slot:]), nets._p(st['coef_gp']),
-                nets._p(st['dws'].d_out), nets._p(st['loss'][slot]), B,
-                self.penalty, 1.0, nets._p(g), nets._p(dst), ns, s)
+      _lib.call('cg_gp_loss_scale', slots, P, norm, st['gp'][slot:],
+                st['coef_gp'], st['dws'].d_out, st['loss'][slot], B,
+                self.penalty, 1.0, g, dst, ns, s)
       st['norm_out'] = norm
       return fake
     if plan.sumsq is not None:  # ||g||^2 came out of the dgrad epilogue
@@ -208,13 +207,13 @@ class WGAN_GP(GAN):
     else:
       norm = st['norm']
       squared = 0
-      _lib.call('cg_rownorm', nets._p(plan.gin), nets._p(norm), B, n,
-                nets._p(nets.reduce_ws(self.device)), s)
+      _lib.call('cg_rownorm', plan.gin, norm, B, n, nets.reduce_ws(self.device),
+                s)
     # gp = mean((||g|| - 1)^2), v's per-sample factor and the critic loss: one
     # launch (two single-block reductions over the batch)
-    _lib.call('cg_gp_critic_loss', nets._p(norm), nets._p(st['gp'][slot:]),
-              nets._p(st['coef_gp']), nets._p(st['dws'].d_out),
-              nets._p(st['loss'][slot]), B, self.penalty, squared, 1.0, s)
+    _lib.call('cg_gp_critic_loss', norm, st['gp'][slot:], st['coef_gp'],
+              st['dws'].d_out, st['loss'][slot], B, self.penalty, squared, 1.0,
+              s)
     if self.dis_optimizer.loss_scale is not None:
       st['coef_gp'].mul_(self.dis_optimizer.loss_scale)  # d(S * lambda * gp)/dg
     st['norm_out'] = norm
@@ -296,10 +295,10 @@ class WGAN_GP(GAN):
       scale = (plan.gin, plan.x0[2 * B:], n)
     self._critic_forward(st, real, None, alpha, shifts, slot, real_cached,
                          fake=fake, scale=scale, plan=plan, packed=packed)
-    s = nets._stream()
+    s = _lib.stream()
     if not plan.norm_deferred:  # (else cg_gp_loss_scale has scaled the rows)
-      _lib.call('cg_scale_rows', nets._p(scale[0]), nets._p(st['coef_gp']),
-                nets._p(scale[1]), B, scale[2], s)
+      _lib.call('cg_scale_rows', scale[0], st['coef_gp'], scale[1], B, scale[2],
+                s)
     plan.jvp_forward()
     if not nets.DETERMINISTIC:  # (the ordered reductions store every gradient)
       net_d.params.grad.zero_()
@@ -335,15 +334,14 @@ class WGAN_GP(GAN):
       shifts = r['shifts_dev']
     else:
       shifts = torch.as_tensor(r['shifts'], dtype=torch.int32).reshape(4, 1)
-    s = nets._stream()
+    s = _lib.stream()
     if shifts.data_ptr() != plan.shifts.data_ptr():
       plan.shifts.copy_(shifts, non_blocking=shifts.is_cuda)
     self._scale_seeds(st, 'gen', self.gen_optimizer)
-    _lib.call('cg_cast_pad', nets._p(fake), nets._p(st['dws'].act[0]),
-              B * lay.lin, lay.cin, self.generator.net.Cf, lay.cinp, s)
+    _lib.call('cg_cast_pad', fake, st['dws'].act[0], B * lay.lin, lay.cin,
+              self.generator.net.Cf, lay.cinp, s)
     plan.forward(seed_backward=True)
-    _lib.call('cg_neg_mean', nets._p(st['dws'].d_out), nets._p(st['gen_loss']),
-              B, s)
+    _lib.call('cg_neg_mean', st['dws'].d_out, st['gen_loss'], B, s)
     plan.backward_chain(seeded=True)
     if not nets.DETERMINISTIC:
       net_g.params.grad.zero_()
@@ -453,9 +451,8 @@ class WGAN_GP(GAN):
     def last_seg():
       metrics = self._gen_apply(real, lr(n), metrics=box.pop('metrics'))
       # (metrics are views of one 4-float buffer: GAN.metrics)
-      _lib.call('cg_step_outputs', nets._p(st['gen_loss']), nets._p(st['loss']),
-                nets._p(st['gp']), nets._p(metrics[_METRIC_KEYS[0]]), n,
-                nets._p(st['out']), nets._stream())
+      _lib.call('cg_step_outputs', st['gen_loss'], st['loss'], st['gp'],
+                metrics[_METRIC_KEYS[0]], n, st['out'], _lib.stream())
 
     segs = []
     def first_seg():

@@ -113,9 +113,9 @@ class Discriminator(_Model):
     plan.shifts.copy_(
         torch.as_tensor(shifts, dtype=torch.int32).reshape(4, 1))
     lay = net.layers[0]
-    from ..._lib import call
-    call('cg_cast_pad', nets._p(x), nets._p(ws.act[0]), B * lay.lin, lay.cin,
-         lay.cin, lay.cinp, nets._stream())
+    from ..._lib import call, stream
+    call('cg_cast_pad', x, ws.act[0], B * lay.lin, lay.cin, lay.cin, lay.cinp,
+         stream())
     plan.forward()
     return ws.d_out[:B].clone().reshape(B, 1)
 

@@ -169,7 +169,6 @@ def deconvolve_signals_device(signals, threshold=0.5, scale=1.0, offset=0.0,
   float64 (traces, T) calcium and spike-size arrays (tests)."""
   import torch
   from ... import _lib as hip
-  from ... import nets
   if not (torch.is_tensor(signals) and signals.is_cuda):
     raise ValueError('deconvolve_signals_device needs a device tensor '
                      '(deconvolve_signals is the host path)')
@@ -199,8 +198,7 @@ def deconvolve_signals_device(signals, threshold=0.5, scale=1.0, offset=0.0,
   if return_cs:
     c = torch.empty(traces, T, dtype=torch.float64, device=dev)
     s = torch.empty(traces, T, dtype=torch.float64, device=dev)
-  hip.call('cg_oasis_ar1_batched', nets._p(signals), n_outer, n_inner, T, sx[0],
-           sx[1], sx[2], scale, offset, g, s_min, threshold, nets._p(gpow),
-           nets._p(out), so[0], so[1], so[2], nets._p(c), nets._p(s),
-           nets._p(ws), nbytes, nets._stream())
+  hip.call('cg_oasis_ar1_batched', signals, n_outer, n_inner, T, sx[0], sx[1],
+           sx[2], scale, offset, g, s_min, threshold, gpow, out, so[0], so[1],
+           so[2], c, s, ws, nbytes, hip.stream())
   return (out, c, s) if return_cs else out

@@ -319,7 +319,6 @@ def batch_statistics_device(spikes):
   often: equal to ~1e-7 relative)."""
   import torch
   from ... import _lib as hip
-  from ... import nets
   if not (torch.is_tensor(spikes) and spikes.is_cuda and
           spikes.dtype == torch.float32 and spikes.dim() == 3):
     raise ValueError('float32 device tensor (B, T, C) expected')
@@ -327,9 +326,8 @@ def batch_statistics_device(spikes):
   rates = torch.empty(B, C, dtype=torch.float32, device=spikes.device)
   covs = torch.empty(B, C * (C + 1) // 2, dtype=torch.float32,
                      device=spikes.device)
-  hip.call('cg_spike_stats', nets._p(spikes), B, T, C, spikes.stride(0),
-           spikes.stride(1), spikes.stride(2), nets._p(rates), nets._p(covs),
-           nets._stream())
+  hip.call('cg_spike_stats', spikes, B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), rates, covs, hip.stream())
   return rates, covs
 
 
@@ -338,7 +336,6 @@ def error_sums_device(rates_a, rates_b, covs_a, covs_b):
   ordered two-stage reduction -- the same bits every call."""
   import torch
   from ... import _lib as hip
-  from ... import nets
   ts = [rates_a, rates_b, covs_a, covs_b]
   if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
              for t in ts):
@@ -350,9 +347,8 @@ def error_sums_device(rates_a, rates_b, covs_a, covs_b):
   ws = torch.empty(hip.load().cg_spike_stats_error_ws_elems(n_r, n_c),
                    dtype=torch.float32, device=dev)
   out = torch.empty(4, dtype=torch.float32, device=dev)
-  hip.call('cg_spike_stats_error', nets._p(rates_a), nets._p(rates_b), n_r,
-           nets._p(covs_a), nets._p(covs_b), n_c, nets._p(out), nets._p(ws),
-           nets._stream())
+  hip.call('cg_spike_stats_error', rates_a, rates_b, n_r, covs_a, covs_b, n_c,
+           out, ws, hip.stream())
   return out
 
 
@@ -378,13 +374,11 @@ def van_rossum_distance_device(spikes, tau=1.0, return_gram=False):
   every call."""
   import torch
   from ... import _lib as hip
-  from ... import nets
   B, T, C = _trial_batch(spikes)
   dist = torch.empty(B, C, C, dtype=torch.float64, device=spikes.device)
   gram = torch.empty_like(dist) if return_gram else None
-  hip.call('cg_van_rossum', nets._p(spikes), B, T, C, spikes.stride(0),
-           spikes.stride(1), spikes.stride(2), van_rossum_decay(tau),
-           nets._p(gram), nets._p(dist), nets._stream())
+  hip.call('cg_van_rossum', spikes, B, T, C, spikes.stride(0), spikes.stride(1),
+           spikes.stride(2), van_rossum_decay(tau), gram, dist, hip.stream())
   return (dist, gram) if return_gram else dist
 
 
@@ -394,11 +388,10 @@ def correlation_coefficients_device(spikes):
   -> float64 device (B, C, C); NaN where a train's bin counts do not vary."""
   import torch
   from ... import _lib as hip
-  from ... import nets
   B, T, C = _trial_batch(spikes)
   corr = torch.empty(B, C, C, dtype=torch.float64, device=spikes.device)
-  hip.call('cg_spike_corrcoef', nets._p(spikes), B, T, C, spikes.stride(0),
-           spikes.stride(1), spikes.stride(2), nets._p(corr), nets._stream())
+  hip.call('cg_spike_corrcoef', spikes, B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), corr, hip.stream())
   return corr
 
 
@@ -411,16 +404,15 @@ def victor_purpura_distance_device(spikes, q=1.0):
   host synchronisation."""
   import torch
   from ... import _lib as hip
-  from ... import nets
   B, T, C = _trial_batch(spikes)
   nbytes = hip.load().cg_victor_purpura_ws_bytes(B, T, C)
   if nbytes < 0:
     raise ValueError('cg_victor_purpura: unsupported shape {}'.format((B, T, C)))
   ws = torch.empty(nbytes, dtype=torch.uint8, device=spikes.device)
   dist = torch.empty(B, C, C, dtype=torch.float64, device=spikes.device)
-  hip.call('cg_victor_purpura', nets._p(spikes), B, T, C, spikes.stride(0),
-           spikes.stride(1), spikes.stride(2), victor_purpura_cost(q),
-           nets._p(dist), nets._p(ws), nbytes, nets._stream())
+  hip.call('cg_victor_purpura', spikes, B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), victor_purpura_cost(q), dist, ws,
+           nbytes, hip.stream())
   return dist
 
 
@@ -505,7 +497,6 @@ def pair_histograms_device(real, fake, num_bins=30, return_edges=True):
   beforehand, no host synchronisation."""
   import torch
   from ... import _lib as hip
-  from ... import nets
   ok = all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and
            t.dim() == 3 for t in (real, fake))
   if not (ok and real.shape == fake.shape and real.shape[1] == real.shape[2] and
@@ -519,8 +510,7 @@ def pair_histograms_device(real, fake, num_bins=30, return_edges=True):
   status = torch.empty(P, dtype=torch.int32, device=dev)
   edges = (torch.empty(P, num_bins + 1, dtype=torch.float64, device=dev)
            if return_edges else None)
-  hip.call('cg_pair_histogram', nets._p(real), real.stride(0), real.stride(1),
-           real.stride(2), nets._p(fake), fake.stride(0), fake.stride(1),
-           fake.stride(2), P, C, num_bins, nets._p(counts), nets._p(valid),
-           nets._p(edges), nets._p(status), nets._stream())
+  hip.call('cg_pair_histogram', real, real.stride(0), real.stride(1),
+           real.stride(2), fake, fake.stride(0), fake.stride(1), fake.stride(2),
+           P, C, num_bins, counts, valid, edges, status, hip.stream())
   return counts, valid, edges, status

@@ -42,8 +42,7 @@ def _p(t):
   return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = _lib.stream
 
 
 def precision_of(hp):
@@ -227,7 +226,7 @@ class PackPlan(object):
     self._keep = operands
 
   def run(self):
-    _lib.call('cg_pack_batched', _p(self.dev), self.n, self.blocks, _stream())
+    _lib.call('cg_pack_batched', self.dev, self.n, self.blocks, _stream())
 
 
 def _transpose_phases(k, pad_left):
@@ -1046,8 +1045,8 @@ class _DisPlan(object):
       B, lay = self.seg_size, net.layers[0]
       a1 = ws.act[1]
       _run_conv(self.fwd_l1_pair, st)
-      _lib.call('cg_lrelu_mix', _p(a1[:B]), _p(a1[B:2 * B]), _p(mix),
-                _p(a1[2 * B:3 * B]), B, lay.lout * lay.coutp, net.alpha, st)
+      _lib.call('cg_lrelu_mix', a1[:B], a1[B:2 * B], mix, a1[2 * B:3 * B], B,
+                lay.lout * lay.coutp, net.alpha, st)
       rest = self.fwd[1:]
     else:
       rest = self.fwd
@@ -1057,13 +1056,12 @@ class _DisPlan(object):
       return
     last = net.layers[-1]
     if seed_backward:
-      _lib.call('cg_dense1_fwd_bwd', _p(ws.act[-1]), _p(net.dense_w),
-                _p(net.dense_b), _p(ws.d_out), _p(self.coef), _p(ws.delta[-1]),
-                self.nB, last.lout, last.cout, last.coutp, self.seg_size,
-                net.alpha, st)
+      _lib.call('cg_dense1_fwd_bwd', ws.act[-1], net.dense_w, net.dense_b,
+                ws.d_out, self.coef, ws.delta[-1], self.nB, last.lout,
+                last.cout, last.coutp, self.seg_size, net.alpha, st)
       return
-    _lib.call('cg_dense1_fwd', _p(ws.act[-1]), _p(net.dense_w), _p(net.dense_b),
-              _p(ws.d_out), self.nB, last.lout, last.cout, last.coutp, st)
+    _lib.call('cg_dense1_fwd', ws.act[-1], net.dense_w, net.dense_b, ws.d_out,
+              self.nB, last.lout, last.cout, last.coutp, st)
 
   def backward_chain(self, seeded=False):
     """delta[5] = coef * w_d * lrelu'(h5) (unless forward(seed_backward=True)
@@ -1073,8 +1071,8 @@ class _DisPlan(object):
     net, ws = self.ws.net, self.ws
     last = net.layers[-1]
     if not seeded:
-      _lib.call('cg_dense1_bwd', _p(net.dense_w), _p(self.coef), _p(ws.act[-1]),
-                _p(ws.delta[-1]), self.nB, last.lout, last.cout, last.coutp,
+      _lib.call('cg_dense1_bwd', net.dense_w, self.coef, ws.act[-1],
+                ws.delta[-1], self.nB, last.lout, last.cout, last.coutp,
                 self.seg_size, net.alpha, st)
     for i, d in self.dgrad:
       _run_conv(d, st)
@@ -1083,13 +1081,13 @@ class _DisPlan(object):
         continue
       if i in self.side:
         side = self.side[i]
-        _lib.call('cg_unshuffle_fixup', _p(side), _p(ws.act[i]),
-                  _p(ws.delta[i]), _p(self.shifts[i - 1]), self.nB, lay.lout,
-                  lay.coutp, self.seg_size, side.shape[1], net.alpha, st)
+        _lib.call('cg_unshuffle_fixup', side, ws.act[i], ws.delta[i],
+                  self.shifts[i - 1], self.nB, lay.lout, lay.coutp,
+                  self.seg_size, side.shape[1], net.alpha, st)
       else:
-        _lib.call('cg_unshuffle_mask', _p(ws.e[i]), _p(ws.act[i]),
-                  _p(ws.delta[i]), _p(self.shifts[i - 1]), self.nB, lay.lout,
-                  lay.coutp, self.seg_size, net.alpha, st)
+        _lib.call('cg_unshuffle_mask', ws.e[i], ws.act[i], ws.delta[i],
+                  self.shifts[i - 1], self.nB, lay.lout, lay.coutp,
+                  self.seg_size, net.alpha, st)
     if self.input_grad is not None:
       if self.sumsq is not None and not self.input_grad.rowsumsq_ws:
         self.sumsq.zero_()  # (the atomics form adds into it)
@@ -1115,10 +1113,9 @@ class _DisPlan(object):
     coef, bias_coef, seg = self.coef, self.bias_coef, self.seg_size
     if head_coef is not None:
       coef, bias_coef, seg = head_coef, head_coef, 1
-    _lib.call('cg_dense1_wgrad', _p(ws.act[-1]), _p(coef),
-              _p(bias_coef), _p(net.params.grad_views[-2]),
-              _p(net.params.grad_views[-1]), self.nB, last.lout, last.cout,
-              last.coutp, seg, _p(reduce_ws(net.device)), st)
+    _lib.call('cg_dense1_wgrad', ws.act[-1], coef, bias_coef,
+              net.params.grad_views[-2], net.params.grad_views[-1], self.nB,
+              last.lout, last.cout, last.coutp, seg, reduce_ws(net.device), st)
 
 
 # ===========================================================================
@@ -1344,8 +1341,7 @@ class _GenWorkspace(object):
     net = self.net
     convs = self.f_conv if keep else self.f_conv_fwd_only
     st = _stream()
-    _lib.call('cg_cast_pad', _p(z_f32), _p(self.z), self.B, net.nd, net.nd,
-              net.nd, st)
+    _lib.call('cg_cast_pad', z_f32, self.z, self.B, net.nd, net.nd, net.nd, st)
     _run_conv(self.f_in, st)
     V = net.params.views
     for i, (lay, ic) in enumerate(zip(net.layers, net.idx_conv)):
@@ -1355,23 +1351,21 @@ class _GenWorkspace(object):
       if net.batch_norm:
         ib = net.idx_bn[i]
         if training:
-          _lib.call('cg_bn_stats', _p(self.ypre[i + 1]), rows, lay.cout,
-                    lay.coutp, _p(self.bn_mean[i + 1]), _p(self.bn_var[i + 1]),
-                    _p(V[ib + 2]), _p(V[ib + 3]), BN_MOMENTUM,
-                    _p(reduce_ws(net.device)), st)
+          _lib.call('cg_bn_stats', self.ypre[i + 1], rows, lay.cout, lay.coutp,
+                    self.bn_mean[i + 1], self.bn_var[i + 1], V[ib + 2],
+                    V[ib + 3], BN_MOMENTUM, reduce_ws(net.device), st)
           mean, var = self.bn_mean[i + 1], self.bn_var[i + 1]
         else:
           mean, var = V[ib + 2], V[ib + 3]
         out = self.ybn[i + 1] if net.layer_norm else self.h[i + 1]
-        _lib.call('cg_bn_apply', _p(self.ypre[i + 1]), _p(mean), _p(var),
-                  _p(V[ib]), _p(V[ib + 1]), _p(out), rows, lay.cout, lay.coutp,
-                  BN_EPS, 1.0 if net.layer_norm else net.alpha, st)
+        _lib.call('cg_bn_apply', self.ypre[i + 1], mean, var, V[ib], V[ib + 1],
+                  out, rows, lay.cout, lay.coutp, BN_EPS,
+                  1.0 if net.layer_norm else net.alpha, st)
         ln_in = out
       if net.layer_norm and not self.ln_fused[i]:
         il = net.idx_ln[i]
-        _lib.call('cg_ln_lrelu_fwd', _p(ln_in), _p(V[il]),
-                  _p(V[il + 1]), _p(self.h[i + 1]), _p(self.mean[i + 1]),
-                  _p(self.rstd[i + 1]), rows, lay.cout, lay.coutp,
+        _lib.call('cg_ln_lrelu_fwd', ln_in, V[il], V[il + 1], self.h[i + 1],
+                  self.mean[i + 1], self.rstd[i + 1], rows, lay.cout, lay.coutp,
                   LN_EPS, net.alpha, st)
     if interp is not None:
       # the fake batches of all critic updates of a step: Dense + sigmoid with the
@@ -1381,16 +1375,15 @@ class _GenWorkspace(object):
       n = len(x0s)
       Bu = self.B // n
       ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in x0s])
-      _lib.call('cg_dense_rows_interp', _p(self.h[-1]), _p(net.w_out.buf),
-                _p(V[net.idx_out + 1]), _p(real), _p(alpha), ptrs, n, Bu, net.L,
-                net.Cp, net.C, net.C, net.Cp,
+      _lib.call('cg_dense_rows_interp', self.h[-1], net.w_out.buf,
+                V[net.idx_out + 1], real, alpha, ptrs, n, Bu, net.L, net.Cp,
+                net.C, net.C, net.Cp,
                 _lib.EPI_SIGMOID if net.normalize else _lib.EPI_NONE, st)
       return None
     if net.streaming_out:
       # HBM-bound per-timestep Dense (+ sigmoid): the streaming kernel
-      _lib.call('cg_dense_rows', _p(self.h[-1]), _p(net.w_out.buf),
-                _p(V[net.idx_out + 1]), _p(self.fake), self.B * net.L, net.Cp,
-                net.C, net.Cf,
+      _lib.call('cg_dense_rows', self.h[-1], net.w_out.buf, V[net.idx_out + 1],
+                self.fake, self.B * net.L, net.Cp, net.C, net.Cf,
                 _lib.EPI_SIGMOID if net.normalize else _lib.EPI_NONE, st)
     else:
       _run_conv(self.f_out, st)
@@ -1411,11 +1404,11 @@ class _GenWorkspace(object):
       regions = reduce_ws_regions(net.device, len(net.layers) + 2)
       _lib.load().cg_finish_defer(1)
       try:
-        self._backward(dfake, st, lambda k: _p(regions[k]))
+        self._backward(dfake, st, lambda k: regions[k])
       finally:
         _lib.call('cg_finish_flush', st)
     else:
-      rws = _p(reduce_ws(net.device))
+      rws = reduce_ws(net.device)
       self._backward(dfake, st, lambda k: rws)
 
   def _backward(self, dfake, st, rws_of):
@@ -1424,21 +1417,21 @@ class _GenWorkspace(object):
     V = net.params.views
     rows = self.B * net.L
     if net.normalize:
-      _lib.call('cg_sigmoid_bwd', _p(dfake), _p(self.fake), _p(self.dz),
-                rows, net.C, net.Cf, net.Cp, st)
+      _lib.call('cg_sigmoid_bwd', dfake, self.fake, self.dz, rows, net.C,
+                net.Cf, net.Cp, st)
     else:
       self.dz.copy_(dfake.view_as(self.dz))  # linear output: dz = dfake
     # dW of the per-timestep Dense: the streaming kernel (the generic cg_wgrad
     # path, taps = 1, reads its operands in 64-byte slivers: 92 -> 31 us at cfg2)
-    _lib.call('cg_dense_wgrad', _p(self.h[-1]), _p(self.dz), _p(G[net.idx_out]),
-              rows, net.Cp, net.Cp, net.C, net.C, _p(self.out_wgrad_ws),
+    _lib.call('cg_dense_wgrad', self.h[-1], self.dz, G[net.idx_out], rows,
+              net.Cp, net.Cp, net.C, net.C, self.out_wgrad_ws,
               0 if self.out_wgrad_ws is None else self.out_wgrad_ws.numel(), st)
     nl = len(net.layers)
-    _lib.call('cg_colsum', _p(self.dz), _p(G[net.idx_out + 1]), rows, net.C,
-              net.Cp, rws_of(nl), st)
+    _lib.call('cg_colsum', self.dz, G[net.idx_out + 1], rows, net.C, net.Cp,
+              rws_of(nl), st)
     if net.streaming_out_dgrad:
-      _lib.call('cg_dense_rows_act', _p(self.dz), _p(net.w_out_t.buf),
-                _p(self.dh[-1]), rows, net.Cp, net.C, net.Cp, st)
+      _lib.call('cg_dense_rows_act', self.dz, net.w_out_t.buf, self.dh[-1],
+                rows, net.Cp, net.C, net.Cp, st)
     else:
       _run_conv(self.b_out_dgrad, st)
     for i in range(len(net.layers) - 1, -1, -1):
@@ -1449,38 +1442,36 @@ class _GenWorkspace(object):
         dout, hmask, act = self.dh[i + 1], self.h[i + 1], 1
         if net.layer_norm:
           il = net.idx_ln[i]
-          _lib.call('cg_ln_lrelu_bwd', _p(self.dh[i + 1]), _p(self.h[i + 1]),
-                    _p(self.ybn[i + 1]), _p(self.mean[i + 1]),
-                    _p(self.rstd[i + 1]), _p(V[il]), _p(self.dybn[i + 1]),
-                    _p(G[il]), _p(G[il + 1]), None, n, lay.cout, lay.coutp,
-                    net.alpha, rws_of(i), st)
+          _lib.call('cg_ln_lrelu_bwd', self.dh[i + 1], self.h[i + 1],
+                    self.ybn[i + 1], self.mean[i + 1], self.rstd[i + 1], V[il],
+                    self.dybn[i + 1], G[il], G[il + 1], None, n, lay.cout,
+                    lay.coutp, net.alpha, rws_of(i), st)
           dout, hmask, act = self.dybn[i + 1], None, 0
-        _lib.call('cg_bn_bwd', _p(dout), _p(hmask), _p(self.ypre[i + 1]),
-                  _p(self.bn_mean[i + 1]), _p(self.bn_var[i + 1]), _p(V[ib]),
-                  _p(self.dy[i + 1]), _p(G[ib]), _p(G[ib + 1]), n, lay.cout,
-                  lay.coutp, BN_EPS, net.alpha, act, rws_of(i), st)
+        _lib.call('cg_bn_bwd', dout, hmask, self.ypre[i + 1],
+                  self.bn_mean[i + 1], self.bn_var[i + 1], V[ib],
+                  self.dy[i + 1], G[ib], G[ib + 1], n, lay.cout, lay.coutp,
+                  BN_EPS, net.alpha, act, rws_of(i), st)
         # (the conv bias gradient: BatchNormalization removes the column mean, so
         # this sum is zero up to rounding -- as the reference's autodiff gives it)
-        _lib.call('cg_colsum', _p(self.dy[i + 1]), _p(G[ic + 1]), n, lay.cout,
+        _lib.call('cg_colsum', self.dy[i + 1], G[ic + 1], n, lay.cout,
                   lay.coutp, rws_of(i), st)
       elif net.layer_norm:
         il = net.idx_ln[i]
-        _lib.call('cg_ln_lrelu_bwd', _p(self.dh[i + 1]), _p(self.h[i + 1]),
-                  _p(self.ypre[i + 1]), _p(self.mean[i + 1]),
-                  _p(self.rstd[i + 1]), _p(V[il]), _p(self.dy[i + 1]),
-                  _p(G[il]), _p(G[il + 1]), _p(G[ic + 1]), n, lay.cout,
+        _lib.call('cg_ln_lrelu_bwd', self.dh[i + 1], self.h[i + 1],
+                  self.ypre[i + 1], self.mean[i + 1], self.rstd[i + 1], V[il],
+                  self.dy[i + 1], G[il], G[il + 1], G[ic + 1], n, lay.cout,
                   lay.coutp, net.alpha, rws_of(i), st)
       else:
-        _lib.call('cg_lrelu_bwd', _p(self.dh[i + 1]), _p(self.h[i + 1]),
-                  _p(self.dy[i + 1]), n * lay.coutp, net.alpha, st)
-        _lib.call('cg_colsum', _p(self.dy[i + 1]), _p(G[ic + 1]), n, lay.cout,
+        _lib.call('cg_lrelu_bwd', self.dh[i + 1], self.h[i + 1], self.dy[i + 1],
+                  n * lay.coutp, net.alpha, st)
+        _lib.call('cg_colsum', self.dy[i + 1], G[ic + 1], n, lay.cout,
                   lay.coutp, rws_of(i), st)
       _run_conv(self.b_dgrad[i], st)
     nflat = net.w0 * net.nd
-    _lib.call('cg_lrelu_bwd', _p(self.dh[0]), _p(self.h[0]), _p(self.dy[0]),
-              self.B * nflat, net.alpha, st)
+    _lib.call('cg_lrelu_bwd', self.dh[0], self.h[0], self.dy[0], self.B * nflat,
+              net.alpha, st)
     _run_wgrad(self.b_in_wgrad, st)
-    _lib.call('cg_colsum', _p(self.dy[0]), _p(G[1]), self.B, nflat, nflat,
+    _lib.call('cg_colsum', self.dy[0], G[1], self.B, nflat, nflat,
               rws_of(nl + 1), st)
     # the conv-transpose weight gradients read h[i] / dy[i+1], which the chain
     # above only produced: all of them together, at the end
@@ -1510,11 +1501,10 @@ def adam_update_scaled(params, lr, ls, grad_scale=1.0, beta1=0.9, beta2=0.999,
   (skipped when a gradient is inf / nan), then the scale's own update.  All on
   the device: nothing here depends on a host-side step count."""
   st = _stream()
-  _lib.call('cg_grad_finite', _p(params.grad), params.numel, _p(ls), st)
-  _lib.call('cg_adam_scaled', _p(params.data), _p(params.grad), _p(params.m),
-            _p(params.v), params.numel, lr, beta1, beta2, eps, grad_scale,
-            _p(ls), st)
-  _lib.call('cg_loss_scale_update', _p(ls), interval, st)
+  _lib.call('cg_grad_finite', params.grad, params.numel, ls, st)
+  _lib.call('cg_adam_scaled', params.data, params.grad, params.m, params.v,
+            params.numel, lr, beta1, beta2, eps, grad_scale, ls, st)
+  _lib.call('cg_loss_scale_update', ls, interval, st)
 
 
 def adam_update(params, step, lr, grad_scale=1.0, beta1=0.9, beta2=0.999,
@@ -1523,6 +1513,6 @@ def adam_update(params, step, lr, grad_scale=1.0, beta1=0.9, beta2=0.999,
   :31-34); `step` is the 1-based iteration count.  lr_t_dev (device scalar)
   overrides the host-computed step size (captured-graph replay)."""
   lr_t = adam_lr_t(step, lr, beta1, beta2)
-  _lib.call('cg_adam', _p(params.data), _p(params.grad), _p(params.m),
-            _p(params.v), params.numel, lr_t, beta1, beta2, eps, grad_scale,
-            _p(lr_t_dev), _stream())
+  _lib.call('cg_adam', params.data, params.grad, params.m, params.v,
+            params.numel, lr_t, beta1, beta2, eps, grad_scale, lr_t_dev,
+            _stream())
