@@ -1011,10 +1011,12 @@ __global__ __launch_bounds__(NT) void dense1_bce_kernel(
     unpack8(raw, v);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float g = (ch + e < C) ? act2f(f2act(wv[e])) * (v[e] > 0.f ? 1.f : alpha)
-                                   : 0.f;
-      od[e] = cd * g;
-      og[e] = cg * g;
+      // (channels [C, Cp) are stored as +0 like every other seed kernel's: a
+      // negative coefficient times a zero g would leave -0 there)
+      const bool valid = ch + e < C;
+      const float g = act2f(f2act(wv[e])) * (v[e] > 0.f ? 1.f : alpha);
+      od[e] = valid ? cd * g : 0.f;
+      og[e] = valid ? cg * g : 0.f;
     }
     store8(delta_d + (long long)b * F + i, od);
     if (gout) store8(gout + i, og);

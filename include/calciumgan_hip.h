@@ -517,7 +517,8 @@ int cg_dense1_wgrad(const void* x /*bf16 [nB][Lt][Cp]*/, const float* coef,
  *   coef_g[b] = S_g * (s(x_b) - 1) / B, b < B        (NULL: not written)
  *   delta_d[b][t][c] = coef_d[b] * bf16(w[t*C+c]) * lrelu'(h[b][t][c])  (2B rows)
  *   delta_g[b][t][c] = coef_g[b] * bf16(w[t*C+c]) * lrelu'(h[b][t][c])  (B rows)
- * (delta_d NULL: no seeds; delta_g NULL: no generator seeds).  S_d / S_g are
+ * (delta_d NULL: no seeds; delta_g NULL: no generator seeds; channels [C, Cp)
+ * of both are stored as +0; lrelu'(h) = h > 0 ? 1 : alpha).  S_d / S_g are
  * device scalars (the fp16 loss scales; NULL = 1).  Keras BCE from logits,
  * max(x,0) - x y + log1p(exp(-|x|)), averaged per segment:
  *   loss[0] = mean_fake BCE(1, x)                      (generator loss)

@@ -174,6 +174,171 @@ def dense1_wgrad_terms(x, coef, seg):
 
 
 # ---------------------------------------------------------------------------
+# BCE head of the vanilla GAN step (cg_dense1_bce)
+# ---------------------------------------------------------------------------
+def sigmoid64(x):
+  """s(x) with the sign split: e^-|x| never overflows, and for x < 0 the result
+  e / (1 + e) keeps its relative accuracy down to the smallest float64."""
+  x = np.asarray(x, np.float64)
+  e = np.exp(-np.abs(x))
+  return np.where(x >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+def bce_logits(x, y):
+  """Keras BCE from logits, max(x, 0) - x y + log1p(exp(-|x|)), for y in {0, 1}:
+  max(x, 0) - x y is exact (0, x or -x), so nothing cancels at any |x|."""
+  x = np.asarray(x, np.float64)
+  return np.maximum(x, 0.0) - x * y + np.log1p(np.exp(-np.abs(x)))
+
+
+def bce_from_logits(x, B, S_d=1.0, S_g=1.0):
+  """Everything cg_dense1_bce derives from the 2B logits x = [fake | real]:
+    t0, t1 (2B,): BCE(0, x), BCE(1, x);   td = [t0 fake | t1 real], tg = t1 fake
+    loss = [mean_fake t1, mean_real t1 + mean_fake t0]
+    coef_d = S_d (s(x) - y) / B (y = 0 fake, 1 real; s(x) - 1 as -s(-x): exact),
+    coef_g = S_g (s(x) - 1) / B on the fake segment."""
+  x = np.asarray(x, np.float64)
+  assert x.shape == (2 * B,)
+  t0, t1 = bce_logits(x, 0.0), bce_logits(x, 1.0)
+  sd = np.r_[sigmoid64(x[:B]), -sigmoid64(-x[B:])]
+  return dict(t0=t0, t1=t1, td=np.r_[t0[:B], t1[B:]], tg=t1[:B],
+              loss=np.array([t1[:B].mean(), t1[B:].mean() + t0[:B].mean()]),
+              coef_d=S_d * sd / B, coef_g=-S_g * sigmoid64(-x[:B]) / B)
+
+
+def bce_head(hq, wq, bias, B, alpha, S_d=1.0, S_g=1.0):
+  """The float64 statement of cg_dense1_bce (include/calciumgan_hip.h).  hq (2B,
+  Lt, Cp) activations [fake | real], wq (Lt, C) the weights as the kernel
+  multiplies them (round_act(w)), C <= Cp.  bce_from_logits of x = bias + <h, wq>
+  plus `x` and the unrounded seeds delta_d (2B, Lt, Cp), delta_g (B, Lt, Cp) =
+  coef * wq * lrelu'(h), channels [C, Cp) zero."""
+  hq, wq = np.asarray(hq, np.float64), np.asarray(wq, np.float64)
+  C, Cp = wq.shape[1], hq.shape[2]
+  x = dense1_fwd(hq[:, :, :C], wq, bias)
+  r = bce_from_logits(x, B, S_d, S_g)
+  r['x'] = x
+  g = np.zeros(hq.shape)
+  g[:, :, :C] = wq[None] * lrelu_grad(hq[:, :, :C], alpha)
+  r['delta_d'] = r['coef_d'][:, None, None] * g
+  r['delta_g'] = r['coef_g'][:, None, None] * g[:B]
+  return r
+
+
+def bce_planted_logits(f16):
+  """Logits where one guard of the head's arithmetic matters, each on one segment
+  at one sign: exponent overflow from 88.8 on, the cancellation of s(x) - 1 and
+  the loss of log(1 + e) from 17 on; expf(-|x|) is subnormal from 87.4 on and
+  zero at 104; the largest finite value of the activation type."""
+  big = act_limits(f16)[1]
+  v = [2.0**-10, 1.0, 20.0, 40.0, 88.0, 89.0, 104.0, big]
+  return np.array([0.0, -0.0] + [s * a for a in v for s in (1.0, -1.0)])
+
+
+# expf and log1pf: spacings charged per call.  An allowance taken from
+# documentation memory (the HIP math API's accuracy table lists single-digit ulp
+# maxima for both), NOT read off the kernel; tests/test_pointwise_ref.py shows
+# that the naive forms miss the bars by far more than any such allowance.
+LIBM_SPACINGS = 2.0
+
+
+def _sigmoid_bar(x):
+  """(s, E) of sigmoid_stable(x) in f32, spacings carried to the result by the
+  derivative: e = expf(-|x|) LIBM sp(e); d = 1 + e half a spacing; the quotient
+  (1 / d for x >= 0, e / d below) half a spacing -- LIBM + 1 spacings, each at
+  its own magnitude (2^-149 in the subnormals)."""
+  x = np.asarray(x, np.float64)
+  e = np.exp(-np.abs(x))
+  d = 1.0 + e
+  de = LIBM_SPACINGS * ulp_f32(e)
+  dd = de + 0.5 * ulp_f32(d)
+  s = np.where(x >= 0, 1.0 / d, e / d)
+  ds = np.where(x >= 0, dd / d**2, de / d + e * dd / d**2) + 0.5 * ulp_f32(s)
+  return s, ds
+
+
+def _coef_bar(s, ds, B, S):
+  """S s / B as (s * (1 / B)) * S: 1 / B and two products, half a spacing each
+  (1.5 spacings on top of the sigmoid's); the first product's rounding is
+  multiplied by S (it matters where s / B is subnormal)."""
+  q = s / B
+  dq = ds / B + U32 * q + 0.5 * ulp_f32(q)
+  return S * dq + 0.5 * ulp_f32(S * q)
+
+
+def _term_bar(x, y):
+  """BCE(y, x) in f32: max(x, 0) - x y is exact; e = expf(-|x|) LIBM sp(e), l =
+  log1pf(e) LIBM sp(l) (+ e's error, derivative 1 / (1 + e)), the final sum half
+  a spacing: 2 LIBM + 0.5 spacings."""
+  x = np.asarray(x, np.float64)
+  e = np.exp(-np.abs(x))
+  de = LIBM_SPACINGS * ulp_f32(e)
+  dl = de / (1.0 + e) + LIBM_SPACINGS * ulp_f32(np.log1p(e))
+  return dl + 0.5 * ulp_f32(bce_logits(x, y))
+
+
+def bce_bars(x, B, S_d=1.0, S_g=1.0):
+  """Error bars of an f32 evaluation of bce_from_logits on the SAME logits, in
+  f32 spacings counted from the operations (a rounding of + * / is half a
+  spacing, expf / log1pf LIBM_SPACINGS):
+    t0, t1, td, tg: _term_bar;  coef_d, coef_g: _sigmoid_bar then _coef_bar;
+    loss (ordered form): each segment's sum of B terms -- the terms' own bars and
+      sum_bound -- over B, the quotient's half spacing (x 2 segments and the
+      final sum's half spacing for loss[1]);
+    loss_atomic: every term times 1 / B first (1 / B, the product: 1.5
+      spacings of t / B), then one sum of B (loss[0]) / 2B (loss[1]) terms in
+      any order."""
+  x = np.asarray(x, np.float64)
+  r = bce_from_logits(x, B, S_d, S_g)
+  e_t0, e_t1 = _term_bar(x, 0.0), _term_bar(x, 1.0)
+  e_td, e_tg = np.r_[e_t0[:B], e_t1[B:]], e_t1[:B]
+  sf, dsf = _sigmoid_bar(x[:B])     # fake: s(x)
+  sn, dsn = _sigmoid_bar(-x)        # s(-x): real coef_d, every coef_g
+  e_cd = np.r_[_coef_bar(sf, dsf, B, S_d), _coef_bar(sn[B:], dsn[B:], B, S_d)]
+  e_cg = _coef_bar(sn[:B], dsn[:B], B, S_g)
+
+  def mean_bar(t, et):
+    return (et.sum() + sum_bound(t)) / B + 0.5 * ulp_f32(t.mean())
+
+  td, tg = r['td'], r['tg']
+  e_loss = np.array([mean_bar(tg, e_tg),
+                     mean_bar(td[B:], e_td[B:]) + mean_bar(td[:B], e_td[:B]) +
+                     0.5 * ulp_f32(r['loss'][1])])
+
+  def atomic_bar(t, et):
+    v = t / B
+    return (et / B + U32 * v + 0.5 * ulp_f32(v)).sum() + sum_bound(v)
+
+  return dict(t0=e_t0, t1=e_t1, td=e_td, tg=e_tg, coef_d=e_cd, coef_g=e_cg,
+              loss=e_loss,
+              loss_atomic=np.array([atomic_bar(tg, e_tg), atomic_bar(td, e_td)]))
+
+
+# ---------------------------------------------------------------------------
+# dynamic loss scale (cg_loss_scale_update)
+# ---------------------------------------------------------------------------
+def loss_scale_update(ls, interval):
+  """The state machine of the header on four f32 [S, good, t, flag], in f32
+  arithmetic: flag != 0 (finite gradients): t += 1, and the `interval`-th
+  consecutive one doubles S (unless 2 S overflows: S stays) and restarts the
+  count; flag == 0: S = max(S / 2, 1), the count restarts, t stays.  The flag is
+  1 afterwards."""
+  f = np.float32
+  S, good, t, flag = (f(v) for v in ls)
+  if flag != 0:
+    t = f(t + f(1))
+    if f(good + f(1)) >= f(interval):
+      with np.errstate(over='ignore'):
+        s2 = f(S * f(2))
+      S = s2 if np.isfinite(s2) else S
+      good = f(0)
+    else:
+      good = f(good + f(1))
+  else:
+    S, good = f(max(f(S * f(0.5)), f(1))), f(0)
+  return np.array([S, good, t, f(1)], np.float32)
+
+
+# ---------------------------------------------------------------------------
 # Keras Adam
 # ---------------------------------------------------------------------------
 def adam_lr_t(lr, b1, b2, t):

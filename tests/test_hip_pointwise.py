@@ -9,7 +9,13 @@ value, exact ties and (fp16) overflowing products.  What the contract says is
 not read is NaN (f32 channels past C, the workspace), what it says is stored is
 pre-filled with a sentinel.  Every bar is one of: bit-equal; k ulps with k
 counted from the operations of the header's formula; sum_bound (n 2^-24 sum
-|terms|) for an f32 sum of n terms -- never a measured number."""
+|terms|) for an f32 sum of n terms -- never a measured number.
+
+The BCE head (cg_dense1_bce) is the one entry point here that calls libm: its
+bars are f32 spacings counted per operation (pointwise_ref.bce_bars), with a
+stated allowance per expf / log1pf call.  The deferred finishing launches
+(cg_finish_defer / cg_finish_flush) are compared bit for bit with the
+undeferred launches of the same reductions, which have their own parity tests."""
 import ctypes
 
 import numpy as np
@@ -980,5 +986,466 @@ def test_grad_finite_refuses_lengths_that_are_not_multiples_of_four(n):
   g = dev32(np.full(8, np.nan))
   ls = sent32(4)
   assert _lib.load().cg_grad_finite(H.p(g), n, H.p(ls), H.stream()) != 0
+  H.sync()
+  assert is_sentinel(ls)
+
+
+# ---------------------------------------------------------------------------
+# cg_dense1_bce: the whole loss head of --algorithm gan
+# ---------------------------------------------------------------------------
+# Rows are laid out over the Lt * C valid positions of a sample: positions 0..5
+# hold the planted values of act_rows (weight 0), position ONE_HOT has the weight
+# 1.0 exactly, every other weight is a random f32 (most of them change when they
+# are rounded to the activation type).  A one-hot row -- v at ONE_HOT, zeros of
+# both signs elsewhere -- has the logit v + bias exactly, in any order of the sum.
+ONE_HOT = 6
+S_D, S_G = 1024.0, 256.0  # the fp16 build's loss scales (powers of two)
+
+
+def _bce_segment(rng, logits, n_rand, Lt, C, Cp, f16, scale):
+  n = Lt * C
+  v = np.zeros((len(logits) + n_rand, n))
+  v[:len(logits), 1] = -0.0        # under a weight of 0 ...
+  v[:len(logits), n - 1] = -0.0    # ... and under a random one
+  v[:len(logits), ONE_HOT] = logits
+  if n_rand:
+    v[len(logits):] = act_rows(rng, n_rand, n, f16, scale)
+  h = np.zeros((len(v), Lt, Cp))   # padding: as test_dense1_fwd_bwd has it
+  h[:, :, :C] = v.reshape(-1, Lt, C)
+  return h
+
+
+def _bce_case(seed, Lt, C, Cp, f16, fake, real, n_rand, bias=0.0):
+  """2B = 2 (len(fake) + n_rand) samples [fake | real]: one-hot rows with the
+  given logits (less the bias), then n_rand random dense rows per segment, scaled
+  so that their logits stay within +-30."""
+  assert len(fake) == len(real) and Lt * C >= 8
+  rng = np.random.RandomState(seed)
+  n = Lt * C
+  w = (rng.randn(n) / np.sqrt(n)).astype(np.float32)
+  w[:6] = 0.0
+  w[ONE_HOT] = 1.0
+  h = np.concatenate([_bce_segment(rng, s, n_rand, Lt, C, Cp, f16, 5.0)
+                      for s in (fake, real)])
+  nan = np.full(n_rand, np.nan)
+  d = dict(Lt=Lt, C=C, Cp=Cp, B=len(fake) + n_rand, h=h, w=w, bias=R.f32(bias),
+           wq=R.round_act(w, f16).reshape(Lt, C),
+           planted=np.r_[np.asarray(fake, np.float64), nan,
+                         np.asarray(real, np.float64), nan])
+  assert (d['wq'] != w.reshape(Lt, C)).any() or n == 8
+  d['hd'] = dev_act(h, f16)
+  # exactly Lt * C weights, then NaN: an over-read by any path of load8f shows
+  d['wd'] = dev32(np.r_[w.astype(np.float64), np.full(16, np.nan)])
+  d['bd'] = dev32([d['bias']])
+  return d
+
+
+def _bce_outputs(d, f16, zero_loss=False):
+  """[out, coef_d, coef_g, delta_d, delta_g, loss], one guard element / row each."""
+  B, Lt, Cp = d['B'], d['Lt'], d['Cp']
+  loss = sent32(3)
+  if zero_loss:
+    loss[:2] = 0.0
+  return [sent32(2 * B + 1), sent32(2 * B + 1), sent32(B + 1),
+          sent_act((2 * B + 1, Lt, Cp), f16), sent_act((B + 1, Lt, Cp), f16), loss]
+
+
+def _bce_launch(d, o, form, scales, ws):
+  """form 'all': every pointer; 'disc': delta_g = coef_g = NULL; 'validate': the
+  six optional pointers NULL (gan.py's validation call)."""
+  out, cd, cg, dd, dg, loss = o
+  sd, sg = scales
+  if form == 'disc':
+    cg = dg = None
+  elif form == 'validate':
+    cd = cg = dd = dg = sd = sg = None
+  _lib.call('cg_dense1_bce', H.p(d['hd']), H.p(d['wd']), H.p(d['bd']), H.p(out),
+            H.p(cd), H.p(cg), H.p(dd), H.p(dg), H.p(loss), H.p(sd), H.p(sg), d['B'],
+            d['Lt'], d['C'], d['Cp'], ALPHA, H.p(ws), H.stream())
+
+
+def _bce_scales(f16):
+  """bf16: NULL.  fp16: NULL, then device scalars."""
+  runs = [((None, None), 1.0, 1.0)]
+  if f16:
+    runs.append(((dev32([S_D]), dev32([S_G])), S_D, S_G))
+  return runs
+
+
+def _bce_check(d, o, terms, f16, form, S_d, S_g):
+  """Every output of one launch.  terms: the first floats of the workspace after
+  an ordered launch, None after the atomics form.
+
+  Logits: one-hot rows bit-equal to the planted value (+ bias), dense rows within
+  sum_bound of their Lt C products and the bias.  Everything else is compared
+  with float64 functions of the logit the launch STORED, inside the bars of
+  pointwise_ref.bce_bars -- f32 spacings counted per operation (half a spacing
+  per rounding of + * /; expf and log1pf two spacings per call, an allowance
+  taken from documentation memory of the HIP math API's accuracy table and not
+  from this kernel: tests/test_pointwise_ref.py shows the naive forms miss these
+  bars by four orders of magnitude and more)."""
+  B, Lt, C, Cp = d['B'], d['Lt'], d['C'], d['Cp']
+  n2 = 2 * B
+  out, cd, cg, dd, dg, loss = o
+  assert float(out[n2]) == SENT32 and float(loss[2]) == SENT32
+  x = host(out[:n2])
+  assert np.isfinite(x).all()  # (a NaN: the guard behind w was read)
+  terms64 = R.dense1_terms(d['h'][:, :, :C], d['wq']).reshape(n2, -1)
+  terms64 = np.concatenate([terms64, np.full((n2, 1), d['bias'])], axis=1)
+  want = terms64.sum(1)
+  assert_f32(out[:n2], want, R.sum_bound(terms64, axis=1), 'logit')
+  pl = ~np.isnan(d['planted'])
+  np.testing.assert_array_equal(want[pl], d['planted'][pl] + d['bias'])
+  np.testing.assert_array_equal(bits(out[:n2]).numpy()[pl],
+                                want.astype(np.float32).view(np.int32)[pl])
+  r, bar = R.bce_from_logits(x, B, S_d, S_g), R.bce_bars(x, B, S_d, S_g)
+  zero = pl & (d['planted'] == 0) & (d['bias'] == 0)  # x = +-0: closed forms
+  if terms is not None:
+    assert_f32(terms[:n2], r['td'], bar['td'], 'terms of loss[1]')
+    assert_f32(terms[n2:3 * B], r['tg'], bar['tg'], 'terms of loss[0]')
+    assert torch.isnan(terms[3 * B:]).all()
+    t = host(terms)
+    assert_f32(t[:n2][zero], np.log(2.0), bar['td'][zero], 'log 2')
+    assert_f32(t[n2:3 * B][zero[:B]], np.log(2.0), bar['tg'][zero[:B]], 'log 2')
+    assert_f32(loss[:2], r['loss'], bar['loss'], 'loss')
+  else:
+    assert_f32(loss[:2], r['loss'], bar['loss_atomic'], 'loss (atomics)')
+  mask = R.lrelu_grad(d['h'][:, :, :C], A32)
+  assert (mask[d['h'][:, :, :C] == 0] == A32).all()  # +0 and -0 take the slope
+  g = d['wq'][None] * mask
+  sign = np.r_[np.ones(B), -np.ones(B)]
+  for name, c, delta, k, on, closed in (
+      ('coef_d', cd, dd, n2, form != 'validate', sign * S_d / n2),
+      ('coef_g', cg, dg, B, form == 'all', np.full(B, -S_g / n2))):
+    if not on:
+      assert is_sentinel(c) and is_sentinel(delta), name
+      continue
+    assert_f32(c[:k], r[name], bar[name], name)
+    assert_f32(host(c[:k])[zero[:k]], closed[zero[:k]], bar[name][zero[:k]],
+               name + ' at 0')
+    # the seeds from the coefficient this launch stored: w lrelu', then the
+    # product with the coefficient -- two f32 roundings (2^-149 each where the
+    # product is subnormal), then the activation's
+    want = host(c[:k])[:, None, None] * g[:k]
+    assert_act(delta[:k, :, :C], want, f16,
+               f32_err=2 * U * np.abs(want) + 2 * 2.0**-149)
+    if Cp > C:  # +0 bit for bit
+      assert int(delta[:k, :, C:].view(torch.int16).count_nonzero()) == 0, name
+    assert float(c[k]) == SENT32 and is_sentinel(delta[k]), name
+
+
+def _bce_ordered(d, f16, form, scales):
+  ws = H.reduce_ws()
+  o = _bce_outputs(d, f16)
+  _bce_launch(d, o, form, scales, ws)
+  H.sync()
+  return o, ws[:3 * d['B'] + 16].clone()
+
+
+def test_bce_head_planted_logits(precision):
+  """Both segments carry every logit of pointwise_ref.bce_planted_logits (in
+  opposite orders) and four dense rows.  The three guards of the arithmetic --
+  the sign split of the sigmoid, -s(-x) for s(x) - 1, log1p -- each decide one
+  segment's seed or term at one sign; past |x| = 87 the f32 results run through
+  the subnormals down to 0, where the bars are multiples of 2^-149.  (bf16: the
+  largest finite logits make the LOSS bars as large as that term's rounding; the
+  losses are pinned by the other tests.)"""
+  f16 = precision
+  x = R.bce_planted_logits(f16)
+  d = _bce_case(1900, 4, 12, 16, f16, x, x[::-1], 4)
+  for scales, S_d, S_g in _bce_scales(f16):
+    def launch(o, ws):
+      _bce_launch(d, o, 'all', scales, ws)
+      if ws is not None:
+        launch.terms = ws[:3 * d['B'] + 16]
+    atom, order = three_forms(launch, lambda zero: _bce_outputs(d, f16, zero))
+    _bce_check(d, atom, None, f16, 'all', S_d, S_g)
+    _bce_check(d, order, launch.terms.clone(), f16, 'all', S_d, S_g)
+    # the dense rows' logits are where the issue wants them
+    assert (np.abs(host(order[0][:2 * d['B']])[np.isnan(d['planted'])]) <= 30).all()
+
+
+# F = Lt Cp: NT = 256 below 8192, 1024 from there on; F / 8 <= 4096 groups stay in
+# LDS between the passes, more are read again; C picks the path of load8f
+BCE_SHAPES = [(1, 8, 8),         # one lane
+              (3, 5, 8),         # scalar weight loads, padded channels
+              (5, 10, 16),       # 8-byte weight loads and a scalar tail group
+              (4, 12, 16),       # 16-byte weight loads, C < Cp
+              (341, 21, 24),     # F = 8184, the last size of NT = 256; 1023 groups
+              (256, 32, 32),     # F = 8192, the first size of NT = 1024
+              (2049, 6, 8),      # F = 16392: a second trip of the NT = 1024 loop
+              (128, 250, 256),   # F / 8 = 4096: the row array exactly full
+              (241, 130, 136)]   # F / 8 = 4097: the first size that reads h again
+
+
+def test_bce_shapes_sit_on_the_dispatch_edges():
+  F = [Lt * Cp for Lt, _, Cp in BCE_SHAPES]
+  assert 8184 in F and 8192 in F and 4096 * 8 in F and 4097 * 8 in F
+  assert any(f > 2 * 1024 * 8 for f in F)          # kNB = 2 loads x 1024 lanes x 8
+  assert {C % 4 == 0 for _, C, _ in BCE_SHAPES} == {True, False}
+  assert any(C % 2 == 0 and C % 4 for _, C, _ in BCE_SHAPES)
+
+
+@pytest.mark.parametrize('form', ['all', 'disc', 'validate'])
+@pytest.mark.parametrize('Lt,C,Cp', BCE_SHAPES)
+def test_bce_head_shapes(Lt, C, Cp, form, precision):
+  """B = 2: per segment one one-hot row (logits -0.75 and 20.25 with the bias)
+  and one dense row."""
+  f16 = precision
+  d = _bce_case(2000 + Lt + C, Lt, C, Cp, f16, [-1.0], [20.0], 1, bias=0.25)
+  for scales, S_d, S_g in _bce_scales(f16):
+    if form == 'validate' and scales[0] is not None:
+      continue  # (the form passes no scales: the same launch again)
+    o, terms = _bce_ordered(d, f16, form, scales)
+    _bce_check(d, o, terms, f16, form, S_d, S_g)
+    assert (np.abs(host(o[0][:4])[np.isnan(d['planted'])]) <= 30).all()
+
+
+@pytest.mark.parametrize('Lt,C,Cp', [(128, 250, 256), (241, 130, 136)])
+def test_bce_head_validate_form_has_the_bits_of_the_training_form(Lt, C, Cp,
+                                                                  precision):
+  """"Same sum order": with the row kept in LDS, with h read again, and in the
+  validate form's kernel without a second pass -- the same logits and losses."""
+  f16 = precision
+  d = _bce_case(2000 + Lt + C, Lt, C, Cp, f16, [-1.0], [20.0], 1, bias=0.25)
+  a, _ = _bce_ordered(d, f16, 'all', (None, None))
+  v, _ = _bce_ordered(d, f16, 'validate', (None, None))
+  assert torch.equal(bits(a[0]), bits(v[0])) and torch.equal(bits(a[5]), bits(v[5]))
+
+
+BCE_LIST = [0.0, -0.0, 2.0**-10, -2.0**-10, 1.0, -1.0, 20.0, -20.0, 40.0, -40.0,
+            88.0, -88.0, 0.5, -3.0, 7.25, -12.5]
+
+
+@pytest.mark.parametrize('B', BS)
+def test_bce_head_batch_sizes(B, precision):
+  """dense1_bce_finish strides over b by 256 and reads terms[B + b], terms[2B +
+  b]: B around the wave and the block, and B = 1.  Every logit is one of sixteen
+  exactly representable values, the segments five positions apart."""
+  f16 = precision
+  fake = [BCE_LIST[i % 16] for i in range(B)]
+  real = [BCE_LIST[(i + 5) % 16] for i in range(B)]
+  d = _bce_case(2200 + B, 1, 8, 8, f16, fake, real, 0)
+  scales, S_d, S_g = _bce_scales(f16)[-1]
+
+  def launch(o, ws):
+    _bce_launch(d, o, 'all', scales, ws)
+    if ws is not None:
+      launch.terms = ws[:3 * B + 16]
+
+  atom, order = three_forms(launch, lambda zero: _bce_outputs(d, f16, zero))
+  _bce_check(d, atom, None, f16, 'all', S_d, S_g)
+  _bce_check(d, order, launch.terms.clone(), f16, 'all', S_d, S_g)
+
+
+def test_bce_head_refusals():
+  """Every check of cg_dense1_bce precedes the launch: CG_EINVAL, and every
+  output still the sentinel."""
+  lib = _lib.load()
+  d = _bce_case(2300, 2, 8, 8, False, [1.0], [-1.0], 0)
+  o = _bce_outputs(d, False)
+  ws = H.reduce_ws()
+  p = [H.p(t) for t in (d['hd'], d['wd'], d['bd'])] + [H.p(t) for t in o]
+  h, w, bias, out, cd, cg, dd, dg, loss = range(9)
+
+  def rc(B=1, C=8, Cp=8, null=(), ws=ws):
+    a = [None if i in null else x for i, x in enumerate(p)]
+    return lib.cg_dense1_bce(a[h], a[w], a[bias], a[out], a[cd], a[cg], a[dd], a[dg],
+                             a[loss], None, None, B, 2, C, Cp, ALPHA, H.p(ws),
+                             H.stream())
+
+  assert rc(Cp=12, C=8) == _lib.CG_EINVAL   # Cp % 8
+  assert rc(C=9) == _lib.CG_EINVAL          # C > Cp
+  assert rc(B=0) == _lib.CG_EINVAL
+  for i in (h, w, bias, out, loss):
+    assert rc(null=(i,)) == _lib.CG_EINVAL, i
+  assert rc(null=(dd,)) == _lib.CG_EINVAL   # delta_g without delta_d
+  # the first B whose 3B terms do not fit the workspace (its size below is NOT
+  # launched: 2.8 M blocks)
+  B_big = lib.cg_reduce_ws_elems() // 3 + 1
+  assert 3 * B_big > lib.cg_reduce_ws_elems() >= 3 * (B_big - 1)
+  assert rc(B=B_big) == _lib.CG_EINVAL
+  H.sync()
+  for t in o:
+    assert is_sentinel(t)
+  assert torch.isnan(ws[:64]).all()
+
+
+# ---------------------------------------------------------------------------
+# cg_finish_defer / cg_finish_flush
+# ---------------------------------------------------------------------------
+def _defer_entries(f16):
+  """Thirteen ordered reductions -- one more than a batch holds.  Entry 5 needs
+  ten column blocks and the cg_ln_lrelu_bwd entries three outputs: every other
+  entry's surplus blocks of the batched grid must return early.  The two
+  cg_signal_metrics entries queue scale = 1 / rows with different rows."""
+  rng = np.random.RandomState(2400)
+  ract = lambda *s: dev_act(R.round_act(rng.randn(*s), f16), f16)
+
+  def colsum(rows, C, Cp):
+    x = ract(rows, Cp)
+
+    def run(o, ws):
+      _lib.call('cg_colsum', H.p(x), H.p(o[0]), rows, C, Cp, H.p(ws), H.stream())
+
+    return dict(name='colsum %d %d %d' % (rows, C, Cp), run=run, reduced=(0,),
+                cvalid=C, gx=(Cp + 63) // 64, outs=lambda: [sent32(Cp + 1)])
+
+  def ln_bwd(rows, C, Cp, dbias):
+    dh, h, y = ract(rows, Cp), ract(rows, Cp), ract(rows, Cp)
+    mean, rstd = dev32(0.5 * rng.randn(rows)), dev32(rng.uniform(0.3, 2.0, rows))
+    gamma = dev32(rng.rand(Cp) + 0.5)
+
+    def run(o, ws):
+      _lib.call('cg_ln_lrelu_bwd', H.p(dh), H.p(h), H.p(y), H.p(mean), H.p(rstd),
+                H.p(gamma), H.p(o[0]), H.p(o[1]), H.p(o[2]),
+                H.p(o[3]) if dbias else None, rows, C, Cp, ALPHA, H.p(ws),
+                H.stream())
+
+    nred = 3 if dbias else 2
+    return dict(name='ln_bwd %d %d %d %d' % (rows, C, Cp, dbias), run=run,
+                reduced=tuple(range(1, 1 + nred)), cvalid=C,
+                gx=(Cp + 63) // 64,
+                outs=lambda: [sent_act((rows + 1, Cp), f16)] +
+                [sent32(Cp + 1) for _ in range(nred)])
+
+  def metrics(rows, C, Cr, Cf):
+    real, fake = dev32(rng.rand(rows, Cr)), dev32(rng.rand(rows, Cf))
+
+    def run(o, ws):
+      _lib.call('cg_signal_metrics', H.p(real), H.p(fake), H.p(o[0]), rows, C, Cr, Cf,
+                -0.5, 2.5, H.p(ws), H.stream())
+
+    return dict(name='metrics %d %d' % (rows, C), run=run, reduced=(0,), cvalid=4,
+                gx=1, outs=lambda: [sent32(5)])
+
+  entries = [colsum(1, 1, 8), ln_bwd(37, 5, 8, True), metrics(63, 6, 7, 8),
+             colsum(300, 70, 72), ln_bwd(1000, 500, 512, False),
+             colsum(5000, 600, 608), metrics(3000, 102, 102, 103),
+             ln_bwd(300, 8, 8, False), ln_bwd(700, 512, 512, True),
+             colsum(2000, 5, 8), ln_bwd(129, 30, 32, True), colsum(257, 102, 104),
+             colsum(4097, 16, 16)]
+  assert len(entries) == 13
+  return entries
+
+
+def _same_bits(o, ref, what):
+  for k, (a, b) in enumerate(zip(o, ref)):
+    assert torch.equal(bits(a), bits(b)), (what, k)
+
+
+def _run_deferred(lib, entries, ref, regions):
+  """Queue the thirteen with deferred finishes, checking at every stage what has
+  and has not been stored; returns the outputs after the flush."""
+  regions.fill_(float('nan'))
+  outs = [e['outs']() for e in entries]
+  try:
+    assert lib.cg_finish_defer(1) == 0
+    assert lib.cg_finish_defer(1) == 1
+    for e, o, ws in zip(entries[:12], outs, regions):
+      e['run'](o, ws)
+    H.sync()
+    # twelve queued: no sum is stored yet, what is not a sum (dy) is
+    for e, o, r in zip(entries[:12], outs, ref):
+      for k in range(len(o)):
+        if k in e['reduced']:
+          assert is_sentinel(o[k]), (e['name'], k)
+        else:
+          assert torch.equal(bits(o[k]), bits(r[k])), (e['name'], k)
+    # the thirteenth finds the batch full: the twelve are added, it is queued
+    entries[12]['run'](outs[12], regions[12])
+    H.sync()
+    for e, o, r in zip(entries[:12], outs, ref):
+      _same_bits(o, r, e['name'])
+    for k in entries[12]['reduced']:
+      assert is_sentinel(outs[12][k]), (entries[12]['name'], k)
+    assert lib.cg_finish_flush(H.stream()) == 0
+    H.sync()
+    for e, o, r in zip(entries, outs, ref):
+      _same_bits(o, r, e['name'])
+      for k in e['reduced']:  # columns at or past cvalid, and the guard
+        assert is_sentinel(o[k][e['cvalid']:]), (e['name'], k)
+    assert lib.cg_finish_defer(0) == 0  # the flush left the mode
+  finally:
+    lib.cg_finish_flush(H.stream())
+    H.sync()
+  return outs
+
+
+def test_deferred_finishes_one_by_one(precision):
+  """Each of thirteen reductions, finished in batched launches (twelve at the
+  thirteenth call, one at the flush), has the bits of its own undeferred launch
+  -- whose float64 parity test_colsum, test_ln_bwd and test_signal_metrics hold
+  -- in either order of queueing."""
+  f16 = precision
+  lib = _lib.load()
+  entries = _defer_entries(f16)
+  # the widest grid (ten column blocks) is neither first nor last in either order
+  gx = [e['gx'] for e in entries]
+  assert max(gx) == 10 and gx.count(10) == 1 and gx.index(10) == 5
+  regions = torch.empty(13, lib.cg_reduce_ws_elems(), dtype=torch.float32,
+                        device=H.DEV)
+  regions.fill_(float('nan'))
+  assert lib.cg_finish_defer(0) == 0
+  ref = []
+  for e, ws in zip(entries, regions):
+    o = e['outs']()
+    e['run'](o, ws)
+    H.sync()
+    for k in e['reduced']:
+      assert not is_sentinel(o[k][:e['cvalid']]), e['name']
+    ref.append(o)
+  outs = _run_deferred(lib, entries, ref, regions)
+  # a flush with nothing queued: 0, and no buffer changes
+  keep = regions.clone()
+  assert lib.cg_finish_flush(H.stream()) == 0
+  H.sync()
+  for e, o, r in zip(entries, outs, ref):
+    _same_bits(o, r, e['name'])
+  assert torch.equal(regions.view(torch.int32), keep.view(torch.int32))
+  del keep
+  # the position in the batch does not matter
+  _run_deferred(lib, entries[::-1], ref[::-1], regions)
+
+
+# ---------------------------------------------------------------------------
+# cg_loss_scale_update
+# ---------------------------------------------------------------------------
+LS_TABLE = [  # (S, good, t, flag, interval)
+    (1024.0, 0.0, 4.0, 1.0, 3),        # finite, below the interval
+    (1024.0, 2.0, 4.0, 1.0, 3),        # reaching it: doubles, good back to 0
+    (1024.0, 0.0, 0.0, 1.0, 1),        # interval 1: doubles every time
+    (1024.0, 7.0, 9.0, 1.0, 1),
+    (2.0**127, 1999.0, 5.0, 1.0, 2000),  # doubling overflows: S stays, good to 0
+    (2.0**127, 3.0, 5.0, 1.0, 2000),
+    (1024.0, 5.0, 4.0, 0.0, 3),        # non-finite: halves, t stays, good 0
+    (1.0, 5.0, 4.0, 0.0, 3),           # the floor
+    (1.5, 5.0, 4.0, 0.0, 3),           # 0.75 -> 1
+    (3.0, 2.0, 4.0, 0.0, 1),           # 1.5: not a power of two, above the floor
+    (1.5, 2.0, 4.0, 1.0, 3),           # 3
+]
+
+
+@pytest.mark.parametrize('S,good,t,flag,interval', LS_TABLE)
+def test_loss_scale_update(S, good, t, flag, interval):
+  state = np.array([S, good, t, flag], np.float32)
+  ls = dev32(np.r_[state, SENT32])
+  _lib.call('cg_loss_scale_update', H.p(ls), interval, H.stream())
+  H.sync()
+  want = R.loss_scale_update(state, interval)
+  assert want[3] == 1.0 and np.isfinite(want).all()
+  np.testing.assert_array_equal(bits(ls[:4]).numpy(), want.view(np.int32))
+  assert float(ls[4]) == SENT32
+  if flag == 0:
+    assert want[2] == t and want[1] == 0 and want[0] == max(S / 2, 1.0)
+  elif good + 1 >= interval:
+    assert want[1] == 0 and want[0] == (S if S == 2.0**127 else 2 * S)
+
+
+def test_loss_scale_update_refusals():
+  lib = _lib.load()
+  ls = sent32(4)
+  assert lib.cg_loss_scale_update(None, 3, H.stream()) == _lib.CG_EINVAL
+  assert lib.cg_loss_scale_update(H.p(ls), 0, H.stream()) == _lib.CG_EINVAL
   H.sync()
   assert is_sentinel(ls)

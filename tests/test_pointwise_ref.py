@@ -2,6 +2,8 @@
 tests of tests/test_hip_pointwise.py compare a kernel with is tied here to an
 independent one -- torch autograd in float64 or the oracle of
 oracle/calciumgan_oracle.py -- and the rounding helpers to hand-picked values."""
+import decimal
+
 import numpy as np
 import torch
 
@@ -183,3 +185,128 @@ def test_ulps_and_sum_bound():
   exact = t.astype(np.float64).sum()
   assert abs(float(seq) - exact) <= R.sum_bound(t)
   assert abs(float(t.sum(dtype=np.float32)) - exact) <= R.sum_bound(t)
+
+
+# ---------------------------------------------------------------------------
+# the BCE head and the loss-scale state machine
+# ---------------------------------------------------------------------------
+def test_bce_head_under_autograd_f64():
+  """R.bce_head against binary_cross_entropy_with_logits on a LeakyReLU -> linear
+  head in float64: the losses, d(S_d loss[1]) / dy = delta_d and, over the fake
+  segment, d(S_g loss[0]) / dy = delta_g -- at logits within +-30, where autograd's
+  own sigmoid is accurate."""
+  bcel = torch.nn.functional.binary_cross_entropy_with_logits
+  rng = np.random.RandomState(8)
+  alpha = 0.3
+  for B, Lt, C, Cp, S_d, S_g in ((1, 2, 3, 8, 1.0, 1.0), (5, 4, 6, 8, 1024.0, 256.0),
+                                 (9, 3, 8, 8, 2.0, 0.5)):
+    y = rng.randn(2 * B, Lt, Cp) * 8
+    y[:, :, C:] = 0.0
+    w = rng.randn(Lt, C) / np.sqrt(Lt * C)
+    yt = torch.tensor(y, dtype=F64, requires_grad=True)
+    ht = torch.nn.functional.leaky_relu(yt, alpha)
+    x = (ht[:, :, :C] * torch.tensor(w)[None]).sum((1, 2)) + 0.25
+    assert float(x.detach().abs().max()) <= 30
+    loss0 = bcel(x[:B], torch.ones(B, dtype=F64))
+    loss1 = bcel(x[B:], torch.ones(B, dtype=F64)) + bcel(x[:B],
+                                                        torch.zeros(B, dtype=F64))
+    gd, = torch.autograd.grad(S_d * loss1, yt, retain_graph=True)
+    gg, = torch.autograd.grad(S_g * loss0, yt)
+    r = R.bce_head(ht.detach().numpy(), w, 0.25, B, alpha, S_d, S_g)
+    np.testing.assert_allclose(r['x'], x.detach().numpy(), rtol=1e-13)
+    np.testing.assert_allclose(r['loss'], [loss0.item(), loss1.item()], rtol=1e-12)
+    np.testing.assert_allclose(r['delta_d'], gd.numpy(), rtol=1e-11, atol=1e-300)
+    np.testing.assert_allclose(r['delta_g'], gg.numpy()[:B], rtol=1e-11, atol=1e-300)
+    assert (gg.numpy()[B:] == 0).all()
+    assert (r['delta_d'][:, :, C:] == 0).all() and (r['delta_g'][:, :, C:] == 0).all()
+    # the per-sample terms are the unreduced losses
+    none = lambda t: bcel(x, torch.full((2 * B,), t, dtype=F64), reduction='none')
+    # (torch's own log(1 + e) is absolute-accurate only: 1e-15 on terms of 1e-4)
+    np.testing.assert_allclose(r['t0'], none(0.0).detach().numpy(), rtol=1e-12,
+                               atol=1e-14)
+    np.testing.assert_allclose(r['t1'], none(1.0).detach().numpy(), rtol=1e-12,
+                               atol=1e-14)
+    np.testing.assert_array_equal(r['td'], np.r_[r['t0'][:B], r['t1'][B:]])
+    np.testing.assert_array_equal(r['tg'], r['t1'][:B])
+
+
+def test_bce_statement_keeps_its_accuracy_at_the_planted_logits():
+  """Against 60-digit closed forms where they are simple: x = +-0 gives log 2
+  and +-1/2; at x = +-104 the small side is e^-104 to float64's accuracy."""
+  x = np.array([0.0, -0.0, 104.0, -104.0])
+  r = R.bce_from_logits(np.r_[x, x], 4, 8.0, 2.0)
+  np.testing.assert_array_equal(r['t0'][:2], [np.log(2.0)] * 2)
+  np.testing.assert_array_equal(r['coef_d'][:2], [8.0 / 8] * 2)        # S_d / (2B)
+  np.testing.assert_array_equal(r['coef_d'][4:6], [-8.0 / 8] * 2)      # -S_d / (2B)
+  np.testing.assert_array_equal(r['coef_g'][:2], [-2.0 / 8] * 2)       # -S_g / (2B)
+  tiny = float(decimal.Context(prec=60).exp(decimal.Decimal(-104)))  # e^-104
+  np.testing.assert_allclose([r['t1'][2], r['t0'][3]], [tiny] * 2, rtol=1e-14)
+  np.testing.assert_allclose([r['t0'][2], r['t1'][3]], [104.0] * 2, rtol=1e-15)
+  np.testing.assert_allclose(r['coef_d'][[3, 6]], [8 * tiny / 4, -8 * tiny / 4],
+                             rtol=1e-14)
+  np.testing.assert_allclose(r['coef_g'][2], -2 * tiny / 4, rtol=1e-14)
+
+
+@np.errstate(over='ignore', divide='ignore')
+def test_the_bce_bars_bite_on_the_naive_f32_forms():
+  """The naive f32 forms -- log(1 + exp(-x)), 1 / (1 + exp(-x)) without the sign
+  split, s(x) - 1 -- evaluated with numpy float32 at the planted logits each miss
+  the bars the GPU test applies, by factors no libm allowance could hide; the
+  bars themselves are a few spacings of the result everywhere."""
+  f = np.float32
+  for f16 in (False, True):
+    x = R.bce_planted_logits(f16)
+    B = len(x)
+    x2 = np.r_[x, x]
+    r, bar = R.bce_from_logits(x2, B), R.bce_bars(x2, B)
+    x32 = x.astype(f)
+    one = f(1)
+    inv_b = one / f(B)
+    # BCE(1, x) = log(1 + exp(-x)): overflows for x <= -89, loses e^-x from x = 17
+    t1 = np.log(one + np.exp(-x32))
+    miss = np.abs(t1.astype(np.float64) - r['t1'][:B]) / bar['t1'][:B]
+    assert miss[x == -89].min() > 1e6 and miss[x == 20].min() > 1e6, miss
+    # mutation of the kernel's line: logf(1 + expf(-|x|)) in place of log1pf
+    t1m = np.maximum(x32, 0) - x32 + np.log(one + np.exp(-np.abs(x32)))
+    miss = np.abs(t1m.astype(np.float64) - r['t1'][:B]) / bar['t1'][:B]
+    assert miss[x == 20].min() > 1e6 and miss[x == 88].min() > 1e5, miss
+    # s(x) without the sign split: exp(-x) overflows, the seed is flushed to 0
+    s = one / (one + np.exp(-x32))
+    cd = (s * inv_b).astype(np.float64)
+    miss = np.abs(cd - r['coef_d'][:B]) / bar['coef_d'][:B]
+    assert miss[x == -89].min() > 1e4, miss
+    # s(x) - 1 on the real segment and for the generator: cancels from x = 17
+    cr = ((s - one) * inv_b).astype(np.float64)
+    miss = np.abs(cr - r['coef_d'][B:]) / bar['coef_d'][B:]
+    assert miss[x == 20].min() > 1e6 and miss[x == 40].min() > 1e6, miss
+    miss = np.abs(cr - r['coef_g']) / bar['coef_g']
+    assert miss[x == 20].min() > 1e6, miss
+    # every bar is a small number of spacings of its result (2^-149 at least)
+    for k, width in (('t0', 5), ('t1', 5), ('coef_d', 9), ('coef_g', 9)):
+      assert (bar[k] <= width * R.ulp_f32(r[k])).all(), k
+      assert (bar[k] >= 0.5 * R.ulp_f32(r[k])).all(), k
+
+
+def test_loss_scale_update_follows_the_oracles_dynamic_loss_scale():
+  """Doubles on the interval-th finite update, halves on a non-finite one, sits on
+  the floor of 1; t counts the applied updates only."""
+  good, bad = [torch.ones(3)], [torch.tensor([1.0, float('inf')])]
+  for S0, interval, flags in ((4.0, 2, [1, 1, 1, 0, 0, 0, 0, 1, 1, 1, 1, 0, 1]),
+                              (2.0**15, 3, [1, 1, 0, 1, 1, 1, 1, 1, 1, 0]),
+                              (1.5, 1, [0, 0, 1, 1, 0])):
+    orc = O.DynamicLossScale(S0, interval)
+    ls = np.array([S0, 0.0, 0.0, 1.0], np.float32)
+    applied = 0
+    seen = set()
+    for flag in flags:
+      ls[3] = flag  # what cg_grad_finite leaves
+      ls = R.loss_scale_update(ls, interval)
+      applied += int(orc.update(good if flag else bad))
+      assert list(ls) == [orc.scale, orc.good_steps, applied, 1.0], (S0, flag, ls)
+      seen.add(float(ls[0]))
+    if S0 == 4.0:  # this sequence doubles, halves and sits on the floor
+      assert 1.0 in seen and max(seen) > S0
+  # 2^127 doubles to infinity in f32: S stays, the count restarts
+  np.testing.assert_array_equal(
+      R.loss_scale_update([2.0**127, 4.0, 9.0, 1.0], 5), [2.0**127, 0.0, 10.0, 1.0])
+  assert list(R.loss_scale_update([1.5, 3.0, 9.0, 0.0], 5)) == [1.0, 0.0, 9.0, 1.0]
