@@ -59,8 +59,12 @@ def segment(raw, sequence_length, stride=2, max_segments=None):
 
 
 def make_dataset(num_neurons=102, sequence_length=2048, num_segments=9192,
-                 seed=1234, stride=2, rho=0.05):
-  """Returns dict(signals (N,L,C) float32 in [0,1], spikes (N,L,C), info)."""
+                 seed=1234, stride=2, rho=0.05, fft=False):
+  """Returns dict(signals (N,L,C) float32 in [0,1], spikes (N,L,C), info).
+  fft (generate_tfrecords.py --fft, :91-120): every segment's traces are
+  replaced by their spectra along time, channels [real | imag]
+  (utils.fft_channels), before the global min/max normalisation; signals are
+  then (N, L, 2C) and info carries fft=True, num_channels = 2C."""
   rng = np.random.RandomState(seed)  # generate_dg_data.py:9
   rates, gamma, _ = dg_parameters(num_neurons, rng, rho)
   duration = sequence_length + stride * num_segments
@@ -68,17 +72,22 @@ def make_dataset(num_neurons=102, sequence_length=2048, num_segments=9192,
   signals = spikes_to_signals(spikes, rng)
   sig = segment(signals.T, sequence_length, stride, num_segments)
   spk = segment(spikes.T, sequence_length, stride, num_segments)
+  num_channels = num_neurons
+  if fft:
+    from ..gan.utils import utils
+    sig = utils.fft_channels(sig)
+    num_channels = 2 * num_neurons
   smin, smax = float(sig.min()), float(sig.max())
   sig = (sig - smin) / (smax - smin)
   info = dict(
-      signal_shape=(sequence_length, num_neurons),
+      signal_shape=(sequence_length, num_channels),
       spike_shape=(sequence_length, num_neurons),
       sequence_length=sequence_length,
       num_neurons=num_neurons,
-      num_channels=num_neurons,
+      num_channels=num_channels,
       normalize=True,
       stride=stride,
-      fft=False,
+      fft=bool(fft),
       conv2d=False,
       signals_min=smin,
       signals_max=smax,

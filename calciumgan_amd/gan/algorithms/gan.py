@@ -62,6 +62,11 @@ class GAN(object):
     self._signals_max = float(getattr(hparams, 'signals_max', 1.0))
     if not hparams.normalize:
       self._signals_min, self._signals_max = 0.0, 1.0
+    # an FFT dataset (info['fft']): the channels are [real | imag] spectra of
+    # num_neurons traces; the spike statistics are taken of the traces
+    self._fft = bool(getattr(hparams, 'fft', False))
+    self._num_neurons = int(getattr(hparams, 'num_neurons',
+                                    self.signal_shape[-1]))
 
     self.device = generator.net.device
     # the build of the kernel library both models compute with ('f16' under
@@ -141,15 +146,28 @@ class GAN(object):
     spike_real_statistics(real_spikes) kept by the caller; sample i is paired
     with sample i.  Returns 0-d device tensors: the sums of |d| and d^2 of both
     statistics (compute_dg_metrics.report's MAE / RMSE / MSE are these sums
-    divided by the counts) and the two counts.  No host sync."""
+    divided by the counts) and the two counts.  On an FFT dataset (hparams.fft)
+    the C channels are the [real | imag] spectra of hparams.num_neurons traces:
+    they are denormalised and inverted by utils.ifft_channels_device first and
+    the statistics are those of the traces.  No host sync."""
     from ..utils import spike_helper, spike_metrics
     C = self.signal_shape[-1]
     fake = fake[:, :, :C]
     if real_stats is None:
       real_stats = self.spike_real_statistics(real_spikes)
-    spikes = spike_helper.deconvolve_signals_device(
-        fake, scale=self._signals_max - self._signals_min,
-        offset=self._signals_min)
+    if self._fft:
+      # [real | imag] spectra: denormalise and invert in one launch, then
+      # deconvolve the num_neurons traces as they are
+      from ..utils import utils
+      spikes = spike_helper.deconvolve_signals_device(
+          utils.ifft_channels_device(
+              fake, self._num_neurons,
+              scale=self._signals_max - self._signals_min,
+              offset=self._signals_min))
+    else:
+      spikes = spike_helper.deconvolve_signals_device(
+          fake, scale=self._signals_max - self._signals_min,
+          offset=self._signals_min)
     rates, covs = spike_metrics.batch_statistics_device(spikes)
     if rates.shape != real_stats[0].shape:
       raise ValueError('fake batch {} and real trains {} differ in shape'.format(

@@ -154,7 +154,12 @@ def cache_validation_set(hparams, validation):
     os.remove(hparams.validation_cache)
   if len(keep) != len(sig):
     sig, spikes = sig[keep], spikes[keep]
-  if hparams.normalize:
+  if getattr(hparams, 'fft', False):
+    # an FFT dataset: the cache holds (n, L, num_neurons) traces
+    # (dataset_helper.py:25 goes through utils.reverse_preprocessing)
+    from . import utils
+    sig = utils.reverse_preprocessing(hparams, sig)
+  elif hparams.normalize:
     sig = sig * (hparams.signals_max - hparams.signals_min) + hparams.signals_min
   h5_helper.write(hparams.validation_cache, {
       'signals': sig.astype(np.float32),

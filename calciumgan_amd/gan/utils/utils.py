@@ -28,8 +28,94 @@ def _to_numpy(x):
   return np.asarray(x)
 
 
+def fft_channels(signals):
+  """generate_tfrecords.py:30-42 (--fft): (N, L, C) float32 traces -> (N, L, 2C)
+  float32 spectra.  Per (n, c) the complex64 FFT along L; real parts in
+  channels [0, C), imaginary parts in [C, 2C) (neuron c's imaginary part is
+  channel C + c, not interleaved)."""
+  signals = np.asarray(signals, dtype=np.float32)
+  assert signals.ndim == 3
+  z = np.fft.fft(signals.astype(np.complex64), axis=1)
+  return np.concatenate([z.real, z.imag], axis=-1).astype(np.float32)
+
+
+def ifft_channels(x):
+  """utils.py:35-46: (N, L, 2C) float32 spectra in the [real | imag] layout of
+  `fft_channels` -> (N, L, C) float32, the real part of the complex64 inverse
+  FFT along L of x[..., c] + 1j * x[..., C + c].  (numpy 2.x keeps complex64 in
+  np.fft: the precision class of the reference's tf.signal.ifft.)"""
+  x = np.asarray(x, dtype=np.float32)
+  assert x.ndim == 3 and x.shape[-1] % 2 == 0
+  C = x.shape[-1] // 2
+  z = np.empty(x.shape[:2] + (C,), dtype=np.complex64)
+  z.real = x[..., :C]
+  z.imag = x[..., C:]
+  return np.ascontiguousarray(np.fft.ifft(z, axis=1).real, dtype=np.float32)
+
+
+IFFT_DEVICE_MIN_LENGTH, IFFT_DEVICE_MAX_LENGTH = 32, 8192
+
+
+def ifft_channels_device(x, num_neurons, scale=1.0, offset=0.0):
+  """`ifft_channels` of x * scale + offset on the GPU (csrc/ifft.hip,
+  cg_ifft_channels): a float32 device tensor (B, L, >= 2 num_neurons) with any
+  strides -- a channel-padded generator output or a permuted view is read in
+  place; channels [0, num_neurons) are the real parts, [num_neurons, 2
+  num_neurons) the imaginary parts -- -> float32 device (B, L, num_neurons),
+  contiguous.  The spectrum inverted is x * scale + offset with float32 product
+  and sum, i.e. utils.denormalize of the float32 array with scale = max - min,
+  offset = min.  No host sync.
+
+  The kernel takes L a power of two in 32 .. 8192.  Any other length (the tile
+  rule admits L = 2048 k with k not a power of two) is inverted by
+  `ifft_channels` on the host, silently: the batch goes down and the traces come
+  back up as a device tensor."""
+  import torch
+  from ... import _lib as hip
+  if not (torch.is_tensor(x) and x.is_cuda):
+    raise ValueError('ifft_channels_device needs a device tensor '
+                     '(ifft_channels is the host path)')
+  C = int(num_neurons)
+  if x.dtype != torch.float32 or x.dim() != 3 or C < 1 or x.shape[2] < 2 * C:
+    raise ValueError('float32 (B, L, >= 2 num_neurons) expected')
+  B, L = x.shape[0], x.shape[1]
+  if B == 0 or L == 0:
+    raise ValueError('empty input')
+  if (L & (L - 1)) or not IFFT_DEVICE_MIN_LENGTH <= L <= IFFT_DEVICE_MAX_LENGTH:
+    host = x[:, :, :2 * C].cpu().numpy()
+    host = host * np.float32(scale) + np.float32(offset)
+    return torch.from_numpy(ifft_channels(host)).to(x.device)
+  y = torch.empty((B, L, C), dtype=torch.float32, device=x.device)
+  hip.call('cg_ifft_channels', x, B, L, C, x.stride(0), x.stride(1),
+           x.stride(2), scale, offset, y, y.stride(0), y.stride(1), y.stride(2),
+           hip.stream())
+  return y
+
+
+def _reverse_fft(hparams, x):
+  """reverse_preprocessing of an FFT dataset (utils.py:49-63 with hparams.fft):
+  denormalise, then the inverse transform per (sample, neuron).  A device
+  tensor is denormalised and inverted on the device (`ifft_channels_device`)
+  and only the (N, L, num_neurons) traces come to the host."""
+  if hasattr(x, 'is_cuda') and x.is_cuda:
+    scale, offset = 1.0, 0.0
+    if hparams.normalize:
+      scale = hparams.signals_max - hparams.signals_min
+      offset = hparams.signals_min
+    x = ifft_channels_device(x.detach(), hparams.num_neurons, scale=scale,
+                             offset=offset)
+    return x.cpu().numpy()
+  x = _to_numpy(x)
+  if hparams.normalize:
+    x = denormalize(x, x_min=hparams.signals_min, x_max=hparams.signals_max)
+  return ifft_channels(x)
+
+
 def reverse_preprocessing(hparams, x):
-  """utils.py:49-63 (1-D, no fft: denormalise only)."""
+  """utils.py:49-63 (1-D): denormalise, and on an FFT dataset (hparams.fft)
+  invert the spectra to (N, L, num_neurons) traces."""
+  if getattr(hparams, 'fft', False):
+    return _reverse_fft(hparams, x)
   x = _to_numpy(x)
   if hparams.normalize:
     x = denormalize(x, x_min=hparams.signals_min, x_max=hparams.signals_max)

@@ -31,9 +31,12 @@ def main():
                  'shards instead of array files')
   p.add_argument('--num_per_shard', default=0, type=int,
                  help='segments per TFRecord shard (0: one shard per mode)')
+  p.add_argument('--fft', action='store_true',
+                 help="store each segment as its spectrum along time, channels "
+                 "[real | imag] (the reference's generate_tfrecords.py --fft)")
   a = p.parse_args()
   d = dg.make_dataset(a.num_neurons, a.sequence_length, a.num_segments, a.seed,
-                      a.stride)
+                      a.stride, fft=a.fft)
   info = {k: v for k, v in d['info'].items() if k != 'rates_hz'}
   full = dataset_helper.write_dataset(a.output_dir, d['signals'], d['spikes'],
                                       info, a.validation_size, a.tfrecords,

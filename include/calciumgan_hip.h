@@ -822,6 +822,35 @@ int cg_pair_histogram(const double* a, long long a_sp, long long a_si,
                       int* counts, int* valid, double* edges, int* status,
                       void* stream);
 
+/* ---------------------------------------------------------------------------
+ * FFT datasets (ifft.hip; the reference's generate_tfrecords.py --fft stores a
+ * trace as its spectrum along time, channels [real | imag], and inverts it on
+ * the host in utils.reverse_preprocessing, gan/utils/utils.py:35-63).  Added
+ * under ABI 20; the same float32 code in both precision builds.
+ * ------------------------------------------------------------------------- */
+/* Real part of the inverse DFT along time of every (sample, neuron) of a
+ * (B, T, >= 2 C) float32 batch (the numpy statement is utils.ifft_channels):
+ *   y[b][t][c] = Re((1/T) sum_k (xr_k + i xi_k) e^{+2 pi i k t / T})
+ *   xr_k = x[b * s_b + k * s_t + c * s_c] * scale + offset
+ *   xi_k = x[b * s_b + k * s_t + (C + c) * s_c] * scale + offset
+ * the product and the sum each rounded to float32 and not contracted (the
+ * denormalisation of a float32 array, as for cg_oasis_ar1_batched), y at
+ * y[b * y_sb + t * y_st + c * y_sc].  Strides in elements, any values: a
+ * channel-padded generator output and permuted views are read in place, and
+ * only the B T C elements of y are written.  x and y must not overlap.
+ * One launch on `stream`, one workgroup per (sample, group of min(16, 8192 / T)
+ * neurons) up to 1024 workgroups, grid-stride beyond; radix-4 (one radix-2
+ * stage when log2 T is odd) decimation in frequency in LDS, twiddles by float64
+ * sincospi rounded to float32, the 1/T scale exact.  No atomics, no workspace,
+ * the same bits every call.
+ * CG_EINVAL (nothing launched): a NULL x or y, B, T or C < 1, T not a power of
+ * two or outside 32 .. 8192. */
+int cg_ifft_channels(const float* x, int B, int T, int C,
+                     long long s_b, long long s_t, long long s_c,
+                     float scale, float offset,
+                     float* y, long long y_sb, long long y_st, long long y_sc,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
