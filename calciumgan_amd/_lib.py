@@ -44,8 +44,9 @@ class HipLibraryError(RuntimeError):
 
 
 class DataPtr(C.c_void_p):
-  """Argtype of a `[const] void|float|double|int *` parameter.  Takes a torch
-  tensor as its data_ptr() once its dtype matches the element type (`void*`
+  """Argtype of a `[const] void|float|double|int|long long *` parameter.  Takes
+  a torch tensor as its data_ptr() once its dtype matches the element type
+  (int64 for `long long*`; `void*`
   takes any; device and contiguity are the caller's business: several entry
   points take host buffers), None as NULL, and whatever c_void_p itself takes:
   ctypes arrays, byref(...), pointer instances, ints."""
@@ -64,7 +65,7 @@ def _data_ptr(ctype, dtype):
           ctype, dtype, obj.dtype))
     return address(obj.data_ptr())
 
-  return type('DataPtr_' + ctype[:-1], (DataPtr,), {
+  return type('DataPtr_' + ctype[:-1].replace(' ', '_'), (DataPtr,), {
       'ctype': ctype, 'dtype': dtype, 'from_param': classmethod(from_param)})
 
 
@@ -73,7 +74,8 @@ _SCALARS = {'int': C.c_int, 'long long': C.c_longlong, 'float': C.c_float,
 _DATA_PTRS = {'void': _data_ptr('void*', None),
               'float': _data_ptr('float*', torch.float32),
               'double': _data_ptr('double*', torch.float64),
-              'int': _data_ptr('int*', torch.int32)}
+              'int': _data_ptr('int*', torch.int32),
+              'long long': _data_ptr('long long*', torch.int64)}
 
 
 def _unknown(decl):

@@ -1,12 +1,22 @@
-"""Scalar logger with the reference's tags and directories
+"""Scalar and histogram logger with the reference's tags and directories
 (gan/utils/summary_helper.py: writers :32-40, Summary.scalar :98-101,
+Summary.histogram :104-106, variable_summary / plot_weights :523-557,
 Summary.log :559-588, profiler hooks :115-119).
 
-Scalars go to TensorBoard event files -- <output_dir>/events.out.tfevents.* for
-training, <output_dir>/validation/... for validation, the reference's two
-writer directories, written by tb_events.py without TensorFlow -- and, for
-grep-ability, to JSON lines next to them (scalars.jsonl).  Images, histograms
-and trace plots (matplotlib) are outside the hot path and not produced.
+Scalars and histograms go to TensorBoard event files --
+<output_dir>/events.out.tfevents.* for training, <output_dir>/validation/...
+for validation, the reference's two writer directories, written by tb_events.py
+without TensorFlow -- and, for grep-ability, to JSON lines next to them
+(scalars.jsonl, histograms.jsonl).  Images and trace plots (matplotlib) are
+outside the hot path and not produced.
+
+--plot_weights: once per training epoch, mean / stddev / min / max and a
+30-bucket histogram of every trainable variable of both models
+(Summary.plot_weights).  The figures of a whole model come from ONE
+cg_tensor_summary call over its flat parameter buffer (nets.FlatParams.summaries,
+csrc/summary.hip) and one device-to-host copy; histogram_buckets and
+variable_statistics below are the numpy statements of that kernel, and the path
+a host array takes.
 
 --profile: the reference traces batches 2-6 of the second epoch with the TF
 profiler (main.py:45-52).  Here profiler_trace() switches that window to eager
@@ -22,13 +32,93 @@ import json
 import os
 import sys
 
+import numpy as np
+
 from . import tb_events
+
+BUCKET_COUNT = 30  # tf.summary.histogram's default `buckets`
 
 
 def _to_float(v):
   if hasattr(v, 'item'):
     return float(v.item())
   return float(v)
+
+
+def _float64_vector(values):
+  d = np.asarray(values).astype(np.float64).reshape(-1)
+  if d.size == 0:
+    raise ValueError('an empty array has no statistics')
+  return d
+
+
+def histogram_buckets(values, bucket_count=BUCKET_COUNT):
+  """The (k, 3) float64 rows (left edge, right edge, count) of
+  tf.summary.histogram (TensorBoard's histogram summary v2, as shipped with TF
+  2.1-2.4): values cast to float64, bucket_count equal-width buckets over
+  [min, max], the maximum clamped into the last bucket; (1, 3), a bucket of
+  unit width, when all values are equal.  Operation by operation what
+  cg_tensor_summary computes (include/calciumgan_hip.h):
+
+    w = (mx - mn) / k,  idx(d) = min((long)floor((d - mn) / w), k - 1)
+    e[j] = mn + fl(j w) for j < k,  e[k] = mx   (a zero mx taken as +0)
+
+  Every value must be finite."""
+  d = _float64_vector(values)
+  k = int(bucket_count)
+  if k < 1:
+    raise ValueError('bucket_count must be positive')
+  if not np.isfinite(d).all():
+    raise ValueError('histogram_buckets: a NaN or an infinity among the values')
+  mn, mx = d.min(), d.max() + 0.0
+  span = mx - mn
+  if span == 0:
+    return np.array([[mn - 0.5, mn + 0.5, np.float64(d.size)]], np.float64)
+  w = span / np.float64(k)
+  idx = np.minimum(np.floor((d - mn) / w).astype(np.int64), k - 1)
+  counts = np.bincount(idx, minlength=k).astype(np.float64)
+  left = mn + np.arange(k, dtype=np.float64) * w
+  right = np.concatenate([left[1:], [mx]])
+  return np.stack([left, right, counts], axis=1)
+
+
+def variable_statistics(values):
+  """dict(mean, stddev, min, max) in float64 (summary_helper.py:526-540): sum
+  and centred squares of the values cast to float64, mean = sum / n, stddev =
+  sqrt(sum (d - mean)^2 / n).  All four are NaN when a value is NaN or
+  infinite, as cg_tensor_summary reports such a segment."""
+  d = _float64_vector(values)
+  if not np.isfinite(d).all():
+    return dict(mean=np.float64('nan'), stddev=np.float64('nan'),
+                min=np.float64('nan'), max=np.float64('nan'))
+  n = np.float64(d.size)
+  mean = d.sum() / n
+  c = d - mean
+  sq = (c * c).sum()
+  return dict(mean=mean, stddev=np.sqrt(sq / n), min=d.min(), max=d.max() + 0.0)
+
+
+def _device_summary(values, bucket_count=BUCKET_COUNT):
+  """(stats row, bucket rows) of a float32 device tensor as host arrays, or
+  None for anything else.  A contiguous tensor is read in place, whatever its
+  offset into its storage."""
+  import torch
+  if not (torch.is_tensor(values) and values.is_cuda and
+          values.dtype == torch.float32 and values.numel() > 0):
+    return None
+  from ... import nets
+  flat = values.detach().contiguous().view(-1)
+  plan = nets.TensorSummary([0], [flat.numel()], flat.device, bucket_count)
+  plan.run(flat)
+  return plan.host()
+
+
+def _rows(stats, buckets):
+  """A segment's bucket rows as they are written: None with a NaN or an
+  infinity in it, the single row when all its values are equal."""
+  if stats[7] > 0:
+    return None
+  return buckets[:1] if stats[1] == stats[2] else buckets
 
 
 class Summary(object):
@@ -48,6 +138,10 @@ class Summary(object):
         True: tb_events.EventFileWriter(self._train_dir),
         False: tb_events.EventFileWriter(self._validation_dir)
     }
+    self._histogram_files = {
+        True: os.path.join(self._train_dir, 'histograms.jsonl'),
+        False: os.path.join(self._validation_dir, 'histograms.jsonl')
+    }
     self._profile = None
 
   def scalar(self, tag, value, step=0, training=True):
@@ -55,6 +149,68 @@ class Summary(object):
     self._writers[bool(training)].scalar(tag, value, step=step)
     with open(self._files[bool(training)], 'a') as f:
       f.write(json.dumps({'tag': tag, 'value': value, 'step': int(step)}) + '\n')
+
+  # -- histograms and weight statistics (summary_helper.py:104-106, 523-557) ----
+  def _write_histogram(self, tag, buckets, step, training):
+    buckets = np.asarray(buckets, np.float64)
+    self._writers[bool(training)].histogram(tag, buckets, step=step)
+    with open(self._histogram_files[bool(training)], 'a') as f:
+      f.write(json.dumps({'tag': tag, 'step': int(step),
+                          'buckets': buckets.tolist()}) + '\n')
+
+  def histogram(self, tag, values, step=0, training=True):
+    """tf.summary.histogram(tag, values, step).  A float32 device tensor is
+    cut into its buckets on the device (cg_tensor_summary) and only the rows
+    come to the host; anything else goes through histogram_buckets.  Values
+    with a NaN or an infinity among them raise ValueError."""
+    got = _device_summary(values)
+    if got is None:
+      rows = histogram_buckets(values)
+    else:
+      rows = _rows(got[0][0], got[1][0])
+      if rows is None:
+        raise ValueError('histogram {}: a NaN or an infinity among the values'
+                         .format(tag))
+    self._write_histogram(tag, rows, step, training)
+
+  def _write_variable(self, name, stats, rows, step, training):
+    """Four scalars and the histogram of one variable; rows None (a NaN or an
+    infinity in it): the scalars, NaN, and no histogram."""
+    for suffix, key in (('0_mean', 'mean'), ('1_stddev', 'stddev'),
+                        ('2_min', 'min'), ('3_max', 'max')):
+      self.scalar('{}/{}'.format(name, suffix), stats[key], step=step,
+                  training=training)
+    if rows is not None:
+      self._write_histogram(name, rows, step, training)
+
+  def variable_summary(self, variable, name, step=0, training=True):
+    """summary_helper.py:523-541: `name`/0_mean, /1_stddev, /2_min, /3_max and a
+    histogram under `name` itself."""
+    got = _device_summary(variable)
+    if got is None:
+      stats = variable_statistics(variable)
+      rows = (histogram_buckets(variable)
+              if np.isfinite(stats['mean']) else None)
+    else:
+      s = got[0][0]
+      stats = dict(mean=s[4], stddev=s[6], min=s[1], max=s[2])
+      rows = _rows(s, got[1][0])
+    self._write_variable(name, stats, rows, step, training)
+
+  def plot_weights(self, gan, step=0, training=True):
+    """summary_helper.py:543-557: every trainable variable of the generator,
+    then of the discriminator, under plots_<model>/<i + 1>/<variable name>.
+    One cg_tensor_summary call and one device-to-host copy per model."""
+    for model, scope in ((gan.generator, 'plots_generator'),
+                         (gan.discriminator, 'plots_discriminator')):
+      params = model.net.params
+      stats, buckets = params.summaries_host(BUCKET_COUNT, trainable_only=True)
+      for i, index in enumerate(params.summary_indices(trainable_only=True)):
+        s = stats[i]
+        self._write_variable(
+            '{}/{:02d}/{}'.format(scope, i + 1, params.names[index]),
+            dict(mean=s[4], stddev=s[6], min=s[1], max=s[2]),
+            _rows(s, buckets[i]), step, training)
 
   # -- profiler window (main.py:45-52) ------------------------------------------
   def profiler_trace(self, gan=None, capacity=4096):
@@ -120,6 +276,9 @@ class Summary(object):
         self.scalar(tag, value, step=step, training=training)
     if elapse is not None:
       self.scalar('elapse', elapse, step=step, training=training)
+    if gan is not None and getattr(self._hparams, 'plot_weights', False):
+      # summary_helper.py:581-582 (main.py passes gan on the training call only)
+      self.plot_weights(gan, step=step, training=training)
     if training and gan is not None and getattr(
         gan.gen_optimizer, 'loss_scale', None) is not None:
       # summary_helper.py:77-78,586-588 logs the loss scale under mixed precision

@@ -112,6 +112,40 @@ def generator_layers(hp):
   return layers
 
 
+def _keras_name(base, i):
+  """Keras' automatic layer name: `base`, `base_1`, `base_2`, ..."""
+  return base if i == 0 else '{}_{}'.format(base, i)
+
+
+def generator_variable_names(layer_norm=False, batch_norm=False):
+  """Names of the generator's variables in get_weights() order, as Keras names
+  them when the generator is the first model built after clear_session()
+  (calciumgan.py:22-103; the reference's Conv1DTranspose layer wraps a
+  Conv2DTranspose).  Restated: TensorFlow is absent, the table is UNPINNED."""
+  names = ['dense/kernel:0', 'dense/bias:0']
+  for i in range(NUM_CONVS):
+    conv = '{}/{}'.format(_keras_name('conv1d_transpose', i),
+                          _keras_name('conv2d_transpose', i))
+    names += [conv + '/kernel:0', conv + '/bias:0']
+    if batch_norm:
+      names += ['{}/{}:0'.format(_keras_name('batch_normalization', i), v)
+                for v in ('gamma', 'beta', 'moving_mean', 'moving_variance')]
+    if layer_norm:
+      names += ['{}/{}:0'.format(_keras_name('layer_normalization', i), v)
+                for v in ('gamma', 'beta')]
+  return names + ['dense_1/kernel:0', 'dense_1/bias:0']
+
+
+def discriminator_variable_names():
+  """The same for the discriminator, built after the generator
+  (calciumgan.py:141-192): its Dense is the process's third."""
+  names = []
+  for i in range(NUM_CONVS):
+    names += ['{}/{}:0'.format(_keras_name('conv1d', i), v)
+              for v in ('kernel', 'bias')]
+  return names + ['dense_2/kernel:0', 'dense_2/bias:0']
+
+
 # activation_fn (gan/models/utils.py:6-8): 'leakyrelu' -> LeakyReLU() (Keras
 # default alpha 0.3), any other name -> layers.Activation(name).  The kernels
 # implement the PIECEWISE-LINEAR ones as x -> max(x, alpha x): the fused

@@ -61,16 +61,85 @@ def _require_gpu(hp=None):
         'compute path (no CPU fallback)')
 
 
+class TensorSummary(object):
+  """cg_tensor_summary (csrc/summary.hip) over fixed segments of a float32
+  device buffer: statistics and histogram buckets of every segment from one
+  call.  The segment tables are checked here -- the kernel cannot refuse what
+  sits in device memory -- and uploaded once; workspace and outputs are kept,
+  so run() allocates nothing and overwrites what the previous run() returned."""
+
+  def __init__(self, offsets, lengths, device, bucket_count=30, limit=None):
+    """Segment s is lengths[s] elements at offsets[s] of the buffer run() is
+    given; limit, the buffer's element count: no segment may reach past it."""
+    offsets, lengths = [int(o) for o in offsets], [int(n) for n in lengths]
+    if len(offsets) != len(lengths):
+      raise ValueError('as many offsets as lengths')
+    for o, n in zip(offsets, lengths):
+      if not 1 <= n <= 2**31 - 1:
+        raise ValueError('segment length {} outside 1 .. 2^31 - 1'.format(n))
+      if o < 0 or (limit is not None and o + n > limit):
+        raise ValueError('segment [{}, {}) outside the buffer'.format(o, o + n))
+    self.nseg, self.total = len(lengths), sum(lengths)
+    self.bucket_count = int(bucket_count)
+    self.limit = limit
+    nbytes = _lib.load().cg_tensor_summary_ws_bytes(self.nseg, self.total,
+                                                    self.bucket_count)
+    if nbytes < 0:
+      raise ValueError('cg_tensor_summary: {} segments, {} buckets (1 .. 65535 '
+                       'segments, 1 .. 512 buckets)'.format(self.nseg,
+                                                            self.bucket_count))
+    self.seg_off = torch.tensor(offsets, dtype=torch.int64, device=device)
+    self.seg_len = torch.tensor(lengths, dtype=torch.int64, device=device)
+    self.ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    # stats and buckets in one buffer: one copy brings both to the host
+    k = self.bucket_count
+    self.out = torch.empty(self.nseg * (8 + 3 * k), dtype=torch.float64,
+                           device=device)
+    self.stats = self.out[:self.nseg * 8].view(self.nseg, 8)
+    self.buckets = self.out[self.nseg * 8:].view(self.nseg, k, 3)
+
+  def run(self, data):
+    """-> device (stats (nseg, 8), buckets (nseg, k, 3)) float64, as
+    include/calciumgan_hip.h lays them out; five launches on the current
+    stream."""
+    if not (torch.is_tensor(data) and data.is_cuda and
+            data.dtype == torch.float32 and data.is_contiguous()):
+      raise ValueError('TensorSummary.run takes a contiguous float32 device '
+                       'tensor')
+    if self.limit is not None and data.numel() < self.limit:
+      raise ValueError('a buffer of {} elements, segments up to {}'.format(
+          data.numel(), self.limit))
+    _lib.call('cg_tensor_summary', data, self.seg_off, self.seg_len, self.nseg,
+              self.total, self.bucket_count, self.stats, self.buckets, self.ws,
+              self.ws.numel() * 8, _stream())
+    return self.stats, self.buckets
+
+  def host(self):
+    """(stats, buckets) of the last run() as numpy arrays: one device-to-host
+    copy."""
+    out = self.out.cpu().numpy()
+    k = self.bucket_count
+    return (out[:self.nseg * 8].reshape(self.nseg, 8),
+            out[self.nseg * 8:].reshape(self.nseg, k, 3))
+
+
 class FlatParams(object):
   """All parameters of one model in ONE flat f32 buffer (one Adam launch, one
   RCCL all-reduce), with per-tensor views in Keras get_weights() order."""
 
-  def __init__(self, shapes, device, frozen=()):
+  def __init__(self, shapes, device, frozen=(), names=None):
     """frozen: indices of non-trainable tensors (BatchNormalization's moving
     statistics): part of get_weights() / checkpoints, outside the parameter
     count, and never given a gradient (Adam leaves a zero-gradient entry
-    alone)."""
+    alone).  names: the variables' names in the same order (Keras' automatic
+    names: geometry.generator_variable_names / discriminator_variable_names)."""
     self.shapes = [tuple(s) for s in shapes]
+    self.names = (['variable_{}:0'.format(i) for i in range(len(self.shapes))]
+                  if names is None else [str(n) for n in names])
+    if len(self.names) != len(self.shapes):
+      raise ValueError('{} names for {} tensors'.format(len(self.names),
+                                                        len(self.shapes)))
+    self._summary_plans = {}
     self.frozen = frozenset(int(i) for i in frozen)
     sizes = [int(np.prod(s)) for s in self.shapes]
     # 16-byte align every tensor so vector loads stay aligned
@@ -106,6 +175,35 @@ class FlatParams(object):
       if tuple(w.shape) != tuple(v.shape):
         raise ValueError('shape mismatch {} vs {}'.format(w.shape, v.shape))
       v.copy_(torch.from_numpy(w))
+
+  # -- weight summaries (--plot_weights) -----------------------------------
+  def summary_indices(self, trainable_only=True):
+    """Indices (get_weights() order) of the variables summaries() covers."""
+    return [i for i in range(len(self.shapes))
+            if not (trainable_only and i in self.frozen)]
+
+  def _summary_plan(self, bucket_count, trainable_only):
+    key = (int(bucket_count), bool(trainable_only))
+    plan = self._summary_plans.get(key)
+    if plan is None:
+      idx = self.summary_indices(trainable_only)
+      plan = TensorSummary([self.offsets[i] for i in idx],
+                           [int(np.prod(self.shapes[i])) for i in idx],
+                           self.data.device, bucket_count, limit=self.numel)
+      self._summary_plans[key] = plan
+    return plan
+
+  def summaries(self, bucket_count=30, trainable_only=True):
+    """Device (stats (n, 8), buckets (n, bucket_count, 3)) float64 of every
+    variable (of summary_indices(trainable_only)) from ONE cg_tensor_summary
+    call over the flat buffer; the segment tables are uploaded on the first call
+    and the workspace is kept.  The next call overwrites the returned tensors."""
+    return self._summary_plan(bucket_count, trainable_only).run(self.data)
+
+  def summaries_host(self, bucket_count=30, trainable_only=True):
+    """summaries() as numpy arrays: one call, one device-to-host copy."""
+    self.summaries(bucket_count, trainable_only)
+    return self._summary_plan(bucket_count, trainable_only).host()
 
 
 # Ordered reductions (default).  Every sum that used to meet through f32 atomics
@@ -791,7 +889,8 @@ class DiscriminatorNet(object):
     last = self.layers[-1]
     self.flat = last.lout * last.cout
     shapes += [(self.flat, 1), (1,)]
-    self.params = FlatParams(shapes, device)
+    self.params = FlatParams(shapes, device,
+                             names=geo.discriminator_variable_names())
     init = []
     for lay in self.layers:
       init.append(
@@ -1190,7 +1289,9 @@ class GeneratorNet(object):
         glorot_uniform(rng, (self.C, self.C), self.C, self.C),
         np.zeros(self.C, np.float32)
     ]
-    self.params = FlatParams(shapes, device, frozen=frozen)
+    self.params = FlatParams(
+        shapes, device, frozen=frozen,
+        names=geo.generator_variable_names(self.layer_norm, self.batch_norm))
     self.params.set_weights(init)
     V = self.params.views
     # packed operands

@@ -851,6 +851,58 @@ int cg_ifft_channels(const float* x, int B, int T, int C,
                      float* y, long long y_sb, long long y_st, long long y_sc,
                      void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Weight summaries (summary.hip; --plot_weights: the reference's
+ * Summary.plot_weights, gan/utils/summary_helper.py:523-557, logs mean, stddev,
+ * min, max and a histogram of every trainable variable once per epoch).  Added
+ * under ABI 20; the same float32 / float64 code in both precision builds.
+ * ------------------------------------------------------------------------- */
+/* Statistics and equal-width histogram buckets of nseg segments of one float32
+ * buffer, in one call (the numpy statements are summary_helper.
+ * variable_statistics and summary_helper.histogram_buckets).  Segment s is the
+ * n = seg_len[s] values at data + seg_off[s]; seg_off and seg_len are DEVICE
+ * int64 tables [nseg] in elements.  Offsets are arbitrary (a 16-byte aligned
+ * segment is read as float4), segments may overlap or repeat, the input is
+ * only read, and no element outside a segment is read.  total_len is the sum of
+ * seg_len, from the caller (it sizes the workspace; the per-segment work is laid
+ * out on the device).  seg_len[s] must be in 1 .. 2^31 - 1: the tables are
+ * device memory, a violation is the caller's error.
+ * For a segment whose values are all finite, with d = (double)x and every
+ * operation rounded to float64 on its own (no fused multiply-add):
+ *   mn = min d, mx = max d (by value; a zero maximum is returned as +0)
+ *   sum = sum of d, mean = sum / n, sq = sum of (d - mean)^2,
+ *   stddev = sqrt(sq / n), range = mx - mn, k = num_buckets
+ *   range == 0:  one bucket (mn - 0.5, mn + 0.5, n)
+ *   otherwise:   w = range / k
+ *                idx(d) = min((long)floor((d - mn) / w), k - 1)
+ *                e[j] = mn + fl(j w) for j < k, e[k] = mx
+ *                bucket j = (e[j], e[j + 1], (double)#{d : idx(d) = j})
+ * which is what the TensorBoard histogram summary (v2) computes for buckets =
+ * 30.  (d - mn) / w is the correctly rounded float64 quotient.
+ * stats: float64 [nseg][8] = {n, mn, mx, sum, mean, sq, stddev, nonfinite},
+ * nonfinite the number of NaN or +-Inf values of the segment; buckets: float64
+ * [nseg][num_buckets][3] = (left, right, count).  range == 0: row 0 holds the
+ * single bucket, the other rows zeros.  nonfinite > 0: stats[1 .. 6] are NaN and
+ * every bucket row is zero; other segments are unaffected.
+ * Every element of stats and buckets is written (nothing has to be zeroed
+ * beforehand; what the workspace needs zeroed is zeroed by a kernel of the
+ * call).  Five launches on `stream` whatever nseg is: a segment is cut into
+ * chunks of 4096 elements, one workgroup per chunk, and the chunks' partial
+ * results are folded per segment in index order -- no floating-point atomics
+ * (the counts meet through integer atomics, which are exact), the same bits
+ * every call.
+ * cg_tensor_summary_ws_bytes: bytes of `ws` (8-byte aligned; contents do not
+ * matter), -1 for arguments cg_tensor_summary refuses.
+ * CG_EINVAL (nothing launched): a NULL pointer, nseg outside 1 .. 65535,
+ * num_buckets outside 1 .. 512, total_len < 1, ws_bytes too small or ws not
+ * 8-byte aligned. */
+long long cg_tensor_summary_ws_bytes(int nseg, long long total_len,
+                                     int num_buckets);
+int cg_tensor_summary(const float* data, const long long* seg_off,
+                      const long long* seg_len, int nseg, long long total_len,
+                      int num_buckets, double* stats, double* buckets, void* ws,
+                      long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

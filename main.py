@@ -11,8 +11,10 @@ of bryanlimy/CalciumGAN), driving the MI355X hot path.
 Differences, all documented: without --mixed_precision activations are bf16
 (f32 accumulation, f32 master weights) where the reference computes in f32;
 with it they are fp16 with the reference's dynamic loss scaling
-(mixed_float16).  Scalars go to TensorBoard event files (written without
-TensorFlow) and JSON lines; trace plots (main.py:142-154) are out of scope;
+(mixed_float16).  Scalars and, with --plot_weights, the weight statistics and
+histograms of every trainable variable (summarised on the device) go to
+TensorBoard event files (written without TensorFlow) and JSON lines; trace
+plots (main.py:142-154) are out of scope;
 the spike deconvolution the reference does there on the host is --spike_metrics
 here, on the device (csrc/spikes.hip); under torchrun every rank trains on its
 own shard of each batch and rank 0 writes the files.
