@@ -58,6 +58,17 @@ def segment(raw, sequence_length, stride=2, max_segments=None):
   return raw[idx]
 
 
+def make_recording(num_neurons=102, duration=20432, seed=1234, rho=0.05):
+  """One DG recording as the reference's pickles hold one: (signals, spikes,
+  rates_hz), signals and spikes (num_neurons, duration) float32 -- what
+  make_dataset segments, and what data/recording.py keeps whole."""
+  rng = np.random.RandomState(seed)  # generate_dg_data.py:9
+  rates, gamma, _ = dg_parameters(num_neurons, rng, rho)
+  spikes = sample_spikes(gamma, rho, duration, rng)
+  signals = spikes_to_signals(spikes, rng)
+  return signals, spikes, rates
+
+
 def make_dataset(num_neurons=102, sequence_length=2048, num_segments=9192,
                  seed=1234, stride=2, rho=0.05, fft=False):
   """Returns dict(signals (N,L,C) float32 in [0,1], spikes (N,L,C), info).
@@ -65,11 +76,8 @@ def make_dataset(num_neurons=102, sequence_length=2048, num_segments=9192,
   replaced by their spectra along time, channels [real | imag]
   (utils.fft_channels), before the global min/max normalisation; signals are
   then (N, L, 2C) and info carries fft=True, num_channels = 2C."""
-  rng = np.random.RandomState(seed)  # generate_dg_data.py:9
-  rates, gamma, _ = dg_parameters(num_neurons, rng, rho)
   duration = sequence_length + stride * num_segments
-  spikes = sample_spikes(gamma, rho, duration, rng)
-  signals = spikes_to_signals(spikes, rng)
+  signals, spikes, rates = make_recording(num_neurons, duration, seed, rho)
   sig = segment(signals.T, sequence_length, stride, num_segments)
   spk = segment(spikes.T, sequence_length, stride, num_segments)
   num_channels = num_neurons

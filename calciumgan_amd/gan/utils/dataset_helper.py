@@ -5,7 +5,10 @@ dataset directory here holds an ``info.pkl`` with the reference's keys
 (dataset/generate_tfrecords.py:229-248) next to EITHER the reference's
 ``train-*.record`` / ``validation-*.record`` files (decoded by
 ``tfrecord.py``, no TensorFlow) OR the same segments as ``train.npy`` /
-``validation.npy`` dicts (what dataset/generate_dg_dataset.py writes).  Batches
+``validation.npy`` dicts (what dataset/generate_dg_dataset.py writes) OR the
+recording itself as ``recording.npy`` (data/recording.py, what
+dataset/generate_dataset.py writes: every batch of windows is cut out of the
+resident recording, `RecordingDataset`).  Batches
 are float32 (B, L, C) in [0, 1]; the last batch of an epoch may be short
 (no drop_remainder, dataset_helper.py:173)."""
 import json
@@ -104,6 +107,165 @@ class ArrayDataset(object):
         yield self.signals[j], LazyRows(self.spikes, j)
 
 
+def _window_rows(starts, L, T):
+  """(B, L) row indices: clamp(starts[b] + t, 0, T - 1)."""
+  starts = np.asarray(starts, dtype=np.int64)
+  return np.clip(starts[:, None] + np.arange(L)[None, :], 0, T - 1)
+
+
+def window_batch(raw, starts, L, fft=False, sub=0.0, div=1.0):
+  """The numpy statement of cg_window_batch (csrc/windows.hip): windows of L
+  rows of the (T, C) float32 recording `raw` beginning at rows `starts`, a row
+  past either end repeating the edge row; with `fft` each window's spectrum
+  along time (utils.fft_channels: (B, L, 2C), [real | imag]); then
+  (x - float32(sub)) / float32(div).  Float32 (B, L, C) or (B, L, 2C)."""
+  raw = np.asarray(raw, dtype=np.float32)
+  assert raw.ndim == 2
+  x = raw[_window_rows(starts, L, raw.shape[0])]
+  if fft:
+    from . import utils
+    x = utils.fft_channels(x)
+  return (x - np.float32(sub)) / np.float32(div)
+
+
+WINDOW_FFT_DEVICE_MIN_LENGTH, WINDOW_FFT_DEVICE_MAX_LENGTH = 32, 8192
+
+
+def window_batch_device(raw, starts, L, fft=False, sub=0.0, div=1.0, out=None):
+  """`window_batch` on the GPU in one launch (cg_window_batch): `raw` a float32
+  device (T, C) tensor with any strides (a stored (C, T) array viewed transposed
+  is read in place), `starts` an int32 device (B,) tensor, `out` an optional
+  float32 device (B, L, C) -- (B, L, 2C) with `fft` -- tensor with any strides
+  (only its window elements are written); returns `out`, or a new contiguous
+  tensor.  No host sync.
+
+  With `fft` the kernel takes L a power of two in 32 .. 8192; any other length
+  goes through `window_batch` on the host, silently, as
+  utils.ifft_channels_device does."""
+  import torch
+  from ... import _lib as hip
+  if not (torch.is_tensor(raw) and raw.is_cuda and torch.is_tensor(starts) and
+          starts.is_cuda):
+    raise ValueError('window_batch_device needs device tensors (window_batch '
+                     'is the host path)')
+  if raw.dtype != torch.float32 or raw.dim() != 2 or raw.numel() == 0:
+    raise ValueError('raw: float32 (T, C) expected')
+  if starts.dtype != torch.int32 or starts.dim() != 1 or starts.numel() == 0:
+    raise ValueError('starts: int32 (B,) expected')
+  L = int(L)
+  if L < 1:
+    raise ValueError('L < 1')
+  starts = starts.contiguous()
+  T, C = raw.shape
+  B = starts.numel()
+  shape = (B, L, 2 * C if fft else C)
+  if out is None:
+    out = torch.empty(shape, dtype=torch.float32, device=raw.device)
+  elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32
+            and tuple(out.shape) == shape):
+    raise ValueError('out: float32 device {} expected'.format(shape))
+  if fft and ((L & (L - 1)) or not WINDOW_FFT_DEVICE_MIN_LENGTH <= L <=
+              WINDOW_FFT_DEVICE_MAX_LENGTH):
+    host = window_batch(raw.cpu().numpy(), starts.cpu().numpy(), L, True, sub,
+                        div)
+    out.copy_(torch.from_numpy(host))
+    return out
+  hip.call('cg_window_batch', raw, T, C, raw.stride(0), raw.stride(1), starts, B,
+           L, 1 if fft else 0, sub, div, out, out.stride(0), out.stride(1),
+           out.stride(2), hip.stream())
+  return out
+
+
+class LazyWindows(object):
+  """LazyRows' sibling for a recording: the float32 (B, L, C) windows of the
+  host (T, C) array `raw` at rows `starts`, cut when first looked at."""
+
+  def __init__(self, raw, starts, length):
+    self._raw, self.starts, self._length = raw, np.asarray(starts), length
+    self._rows = None
+
+  def _get(self):
+    if self._rows is None:
+      idx = _window_rows(self.starts, self._length, self._raw.shape[0])
+      self._rows = self._raw[idx].astype(np.float32)
+    return self._rows
+
+  def __array__(self, dtype=None, copy=None):
+    r = self._get()
+    return r if dtype is None else r.astype(dtype)
+
+  def __getitem__(self, k):
+    return self._get()[k]
+
+  def __len__(self):
+    return len(self.starts)
+
+  @property
+  def shape(self):
+    return (len(self.starts), self._length) + tuple(self._raw.shape[1:])
+
+  @property
+  def dtype(self):
+    return np.dtype(np.float32)
+
+
+class RecordingDataset(object):
+  """ArrayDataset's protocol over a recording that stays whole
+  (data/recording.py): window i begins at raw row starts[i], and a batch is cut
+  out of the (T, C) recording when it is asked for -- on the device by one
+  cg_window_batch launch into `gather_into(len)` (main.py: GAN.batch_buffer),
+  with the spectrum and the normalisation applied on the way; without
+  `to_device`, by the numpy statement.  Positions are shuffled and sorted per
+  batch exactly as ArrayDataset does, so a recording directory and the
+  materialised directory of the same recording yield the same batches in the
+  same order.  The `signal` tensors alias each other as ArrayDataset's do."""
+
+  def __init__(self, raw, spikes, starts, sequence_length, batch_size, shuffle,
+               fft=False, sub=0.0, div=1.0, seed=1234):
+    self.raw = np.ascontiguousarray(raw, dtype=np.float32)
+    self.raw_spikes = spikes
+    self.starts = np.asarray(starts, dtype=np.int64)
+    self.sequence_length = int(sequence_length)
+    self.batch_size, self.shuffle = batch_size, shuffle
+    self.fft, self.sub, self.div = bool(fft), float(sub), float(div)
+    self._rng = np.random.RandomState(seed)
+    self._dev_raw = None
+    self.gather_into = None
+
+  def to_device(self, device):
+    """Keep the recording resident (cfg2: 8.3 MB where the windows are 7.7 GB).
+    Spikes stay on the host.  A device that is no GPU leaves the host path."""
+    import torch
+    if torch.device(device).type == 'cuda':
+      self._dev_raw = torch.from_numpy(self.raw).to(device)
+    return self
+
+  def windows(self, starts):
+    """The host batch of the windows at `starts`."""
+    return window_batch(self.raw, starts, self.sequence_length, self.fft,
+                        self.sub, self.div)
+
+  def __len__(self):
+    return ceil(len(self.starts) / self.batch_size)
+
+  def __iter__(self):
+    idx = np.arange(len(self.starts))
+    if self.shuffle:
+      self._rng.shuffle(idx)
+    L = self.sequence_length
+    for i in range(0, len(idx), self.batch_size):
+      st = self.starts[np.sort(idx[i:i + self.batch_size])]
+      spikes = LazyWindows(self.raw_spikes, st, L)
+      if self._dev_raw is not None:
+        import torch
+        dev_st = torch.from_numpy(st.astype(np.int32)).to(self._dev_raw.device)
+        out = self.gather_into(len(st)) if self.gather_into is not None else None
+        yield window_batch_device(self._dev_raw, dev_st, L, self.fft, self.sub,
+                                  self.div, out=out), spikes
+      else:
+        yield self.windows(st), spikes
+
+
 def get_dataset_info(hparams):
   """dataset_helper.py:113-144."""
   with open(os.path.join(hparams.input_dir, 'info.pkl'), 'rb') as file:
@@ -154,7 +316,10 @@ def cache_validation_set(hparams, validation):
     os.remove(hparams.validation_cache)
   if len(keep) != len(sig):
     sig, spikes = sig[keep], spikes[keep]
-  if getattr(hparams, 'fft', False):
+  if 'traces' in validation:
+    # an FFT recording: the raw windows themselves, no inverse transform
+    sig = np.asarray(validation['traces'])[keep]
+  elif getattr(hparams, 'fft', False):
     # an FFT dataset: the cache holds (n, L, num_neurons) traces
     # (dataset_helper.py:25 goes through utils.reverse_preprocessing)
     from . import utils
@@ -237,6 +402,8 @@ def get_dataset(hparams, summary=None):
                                     hparams.batch_size)
     return train_ds, validation_ds
   get_dataset_info(hparams)
+  if os.path.exists(os.path.join(hparams.input_dir, 'recording.npy')):
+    return get_recording_dataset(hparams)
   if os.path.exists(os.path.join(hparams.input_dir, 'train.npy')):
     with open(os.path.join(hparams.input_dir, 'train.npy'), 'rb') as f:
       train = pickle.load(f)
@@ -258,6 +425,37 @@ def get_dataset(hparams, summary=None):
                           shuffle=True)
   validation_ds = ArrayDataset(validation['signals'], validation['spikes'],
                                hparams.batch_size, shuffle=False)
+  hparams.train_steps = ceil(hparams.train_size / hparams.batch_size)
+  hparams.validation_steps = ceil(hparams.validation_size / hparams.batch_size)
+  return train_ds, validation_ds
+
+
+def get_recording_dataset(hparams):
+  """A recording directory (data/recording.py: recording.npy beside info.pkl):
+  the (T, C) recording and the start rows of its train / validation windows.
+  The validation windows of generated/validation.h5 are cut on the host; for an
+  FFT recording the cache holds the raw windows themselves (exact: nothing is
+  transformed forth and back)."""
+  from ...data import recording
+  rec = recording.load(hparams.input_dir)
+  L, fft = hparams.sequence_length, bool(hparams.fft)
+  sub, div = recording.normalisation(rec['info'])
+  if hparams.save_generated and getattr(hparams, 'rank', 0) == 0:
+    vstarts = rec['validation_starts']
+    validation = {
+        'signals': window_batch(rec['raw'], vstarts, L, fft, sub, div),
+        'spikes': np.asarray(LazyWindows(rec['spikes'], vstarts, L))
+    }
+    if fft:
+      validation['traces'] = window_batch(rec['raw'], vstarts, L)
+    cache_validation_set(hparams, validation)
+  train_ds = RecordingDataset(rec['raw'], rec['spikes'], rec['train_starts'], L,
+                              hparams.batch_size, shuffle=True, fft=fft, sub=sub,
+                              div=div)
+  validation_ds = RecordingDataset(rec['raw'], rec['spikes'],
+                                   rec['validation_starts'], L,
+                                   hparams.batch_size, shuffle=False, fft=fft,
+                                   sub=sub, div=div)
   hparams.train_steps = ceil(hparams.train_size / hparams.batch_size)
   hparams.validation_steps = ceil(hparams.validation_size / hparams.batch_size)
   return train_ds, validation_ds

@@ -34,7 +34,23 @@ def main():
   p.add_argument('--fft', action='store_true',
                  help="store each segment as its spectrum along time, channels "
                  "[real | imag] (the reference's generate_tfrecords.py --fft)")
+  p.add_argument('--recording', action='store_true',
+                 help='write the recording itself (recording.npy) instead of '
+                 'its windows: every training step cuts its windows on the GPU '
+                 '(calciumgan_amd/data/recording.py)')
   a = p.parse_args()
+  if a.recording:
+    from calciumgan_amd.data import recording
+    signals, spikes, _ = dg.make_recording(
+        a.num_neurons, a.sequence_length + a.stride * a.num_segments, a.seed)
+    rec = recording.build(signals, spikes, a.sequence_length, stride=a.stride,
+                          fft=a.fft, validation_size=a.validation_size,
+                          max_segments=a.num_segments)
+    full = recording.write(a.output_dir, rec)
+    print('saved the recording of {} train + {} validation segments of shape {} '
+          'to {}'.format(full['train_size'], full['validation_size'],
+                         full['signal_shape'], a.output_dir))
+    return
   d = dg.make_dataset(a.num_neurons, a.sequence_length, a.num_segments, a.seed,
                       a.stride, fft=a.fft)
   info = {k: v for k, v in d['info'].items() if k != 'rates_hz'}

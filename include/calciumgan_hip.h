@@ -852,6 +852,42 @@ int cg_ifft_channels(const float* x, int B, int T, int C,
                      void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Recording datasets (windows.hip; the reference's generate_tfrecords.py cuts a
+ * (neurons, T) recording into overlapping stride-2 windows and writes each one
+ * out; here the recording stays resident and every step's windows are cut
+ * straight into the batch buffer).  Added under ABI 20; the same float32 code
+ * in both precision builds.
+ * ------------------------------------------------------------------------- */
+/* One batch of B windows of L rows of a float32 (T_raw, C) recording (the numpy
+ * statement is dataset_helper.window_batch).  Row t of window b is raw row
+ * clamp(starts[b] + t, 0, T_raw - 1): nothing outside raw is ever read,
+ * whatever starts holds, and a window past either end repeats the edge row.
+ * raw at raw[row * r_st + c * r_sc], strides in elements, any values (a stored
+ * (C, T) array viewed transposed is read in place); starts is a device int32[B].
+ *   fft == 0: y is (B, L, C), y[b * y_sb + t * y_st + c * y_sc] = (v - sub) / div
+ *             with v the raw value; 16-byte accesses where r_sc == y_sc == 1 and
+ *             the alignment allows, one element at a time otherwise
+ *   fft != 0: y is (B, L, 2 C); channel c is the real and channel C + c the
+ *             imaginary part of sum_t x_t e^{-2 pi i k t / L} (unscaled; the
+ *             layout of utils.fft_channels), each written as (v - sub) / div.
+ *             Shaped as cg_ifft_channels: one workgroup per (window, group of
+ *             min(16, 8192 / L) neurons) up to 1024, grid-stride beyond.  An
+ *             all-zero trace gives an all-zero spectrum.
+ * (v - sub) / div is the float32 difference, then the IEEE float32 quotient,
+ * not contracted, no reciprocal: v itself, bit for bit, with sub = 0, div = 1.
+ * One launch on `stream`; no atomics, no workspace, no host sync, the same bits
+ * every call; only the window elements of y are written.  raw and y must not
+ * overlap.
+ * CG_EINVAL (nothing launched): a NULL raw, starts or y, T_raw, C, B or L < 1,
+ * div == 0, with fft an L that is not a power of two in 32 .. 8192. */
+int cg_window_batch(const float* raw, long long T_raw, int C,
+                    long long r_st, long long r_sc,
+                    const int* starts, int B, int L,
+                    int fft, float sub, float div,
+                    float* y, long long y_sb, long long y_st, long long y_sc,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------
  * Weight summaries (summary.hip; --plot_weights: the reference's
  * Summary.plot_weights, gan/utils/summary_helper.py:523-557, logs mean, stddev,
  * min, max and a histogram of every trainable variable once per epoch).  Added
