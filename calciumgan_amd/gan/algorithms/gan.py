@@ -50,8 +50,18 @@ class GAN(object):
   _graph_under_dp = False
   # train() returns None in the penalty position
   _has_penalty = False
+  # whether the class's step drives an MLP pair (models/mlp.py): wgan_gp_mlp only
+  _mlp_step = False
 
   def __init__(self, hparams, generator, discriminator, summary=None):
+    for model in (generator, discriminator):
+      if getattr(model, 'is_mlp', False) != self._mlp_step:
+        raise ValueError(
+            'calciumgan_amd: the MLP step needs an MLP generator and '
+            'discriminator' if self._mlp_step else
+            'calciumgan_amd: --model mlp trains under --algorithm wgan-gp only '
+            '(the {} step is scheduled for the convolutional models)'.format(
+                type(self).__name__))
     self.generator = generator
     self.discriminator = discriminator
     self._summary = summary

@@ -55,6 +55,14 @@ class WGAN_GP(GAN):
   _has_penalty = True
   _graph_under_dp = True  # (as segments cut around the all-reduces)
 
+  def __new__(cls, hparams, generator, discriminator, summary=None):
+    """An MLP pair (--model mlp) goes to the MLP step (wgan_gp_mlp.py): the
+    schedule below is the convolutional models'."""
+    if cls is WGAN_GP and getattr(generator, 'is_mlp', False):
+      from .wgan_gp_mlp import MLP_WGAN_GP
+      return MLP_WGAN_GP(hparams, generator, discriminator, summary)
+    return super().__new__(cls)
+
   def __init__(self, hparams, generator, discriminator, summary=None):
     super().__init__(hparams, generator, discriminator, summary)
     self.penalty = float(hparams.gradient_penalty)

@@ -6,3 +6,4 @@ from .registry import get_models, register
 __all__ = ['get_models', 'register']
 
 from . import calciumgan  # noqa: E402,F401  (registers 'calciumgan')
+from . import mlp  # noqa: E402,F401  (registers 'mlp')

@@ -939,6 +939,84 @@ int cg_tensor_summary(const float* data, const long long* seg_off,
                       int num_buckets, double* stats, double* buckets, void* ws,
                       long long ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * The MLP model (gan/models/mlp.py:15-77): float32 Dense over rows with
+ * counter-based dropout (mlp.hip).  Everything in this section is float32 in
+ * both builds.  Operands are row-major; W is the Keras kernel (in, out); inputs
+ * are read through a row pitch (in floats) and outputs are written densely.
+ * act(z) = max(z, alpha z), alpha in {0.3, 0, 1}.
+ *
+ * Dropout.  The keep decision of element e of a layer's (rows x Cout) output is
+ * word e & 3 of the Philox4x32-10 block with counter words (lo(e >> 2),
+ * hi(e >> 2), lo(stream_id), hi(stream_id)) and key (lo(seed), hi(seed)):
+ * kept iff word >= floor(p 2^32).  Kept elements are multiplied by
+ * float32(1 / (1 - p)), the others are exactly 0.  p == 0 runs no generator.
+ * Nothing is stored between launches: the backward kernels read the decision
+ * back from the stored h (h > 0: slope 1, h < 0: slope alpha, h == 0: dropped).
+ *
+ * Limits: Cin, Cout >= 1, the smaller of the two <= CG_MLP_MAX_WIDTH (a layer
+ * width) and the larger <= CG_MLP_MAX_FLAT (the flattened time x width side of
+ * the generator's first Dense and of the critic's head); 0 <= p < 1.  Outside
+ * them, for rows <= 0 and for a NULL pointer where one is needed the functions
+ * return CG_EINVAL before anything touches HIP: nothing is written.
+ * ------------------------------------------------------------------------- */
+#define CG_MLP_MAX_WIDTH 1024
+#define CG_MLP_MAX_FLAT 65536
+/* cg_mlp_dense_fwd modes */
+#define CG_MLP_FWD_ACT 0      /* h = drop(act(x W + b)) */
+#define CG_MLP_FWD_TANGENT 1  /* h = m(h_mask) * (x W): no bias, no act; m = the
+                                 stored h's s * keep * act' (the tangent chain of
+                                 the penalty's second backward) */
+#define CG_MLP_FWD_SIGMOID 2  /* h = sigmoid(x W + b), no dropout */
+/* cg_mlp_dense_dgrad modes */
+#define CG_MLP_BWD_MASK 0     /* dz = dh * m(h) */
+#define CG_MLP_BWD_SIGMOID 1  /* dz = dh * h (1 - h), h the sigmoid's output */
+#define CG_MLP_BWD_NONE 2     /* dz = dh */
+
+/* keep[e] = 1 / 0 for e < n: the keep mask of (seed, stream_id, p), one byte
+ * per element (for tests; the Dense kernels store no mask) */
+int cg_mlp_dropout_mask(void* keep, long long n, long long seed,
+                        long long stream_id, double p, void* stream);
+/* h [rows][Cout] from x [rows][x_pitch >= Cin]; b may be NULL (no bias);
+ * h_mask [rows][Cout] is read by CG_MLP_FWD_TANGENT only. */
+int cg_mlp_dense_fwd(const float* x, long long x_pitch, const float* W,
+                     const float* b, const float* h_mask, float* h,
+                     long long rows, int Cin, int Cout, int mode, float alpha,
+                     double p, long long seed, long long stream_id,
+                     void* stream);
+/* dz [rows][Cout] = dh masked on the way in (mode; h [rows][Cout] the stored
+ * output of the layer), dx [rows][Cin] = dz W^T.  dx may be NULL (a first
+ * layer: dz only); dz must not alias dh. */
+int cg_mlp_dense_dgrad(const float* dh, const float* h, const float* W,
+                       float* dz, float* dx, long long rows, int Cin, int Cout,
+                       int mode, float alpha, double p, void* stream);
+/* dW [Cin][Cout] = sum_r c(r) x[r]^T dz[r], db [Cout] = sum_{r < bias_rows}
+ * c(r) dz[r] (db may be NULL), c(r) = c0 / c1 / c2 for row r in segment
+ * min(r / seg_rows, 2).  Rows >= tail_row0 read their x from x_tail (dense
+ * [rows - tail_row0][Cin]) when it is non-NULL: [h_real | h_fake | tangent].
+ * Ordered two-stage sums through ws (cg_mlp_wgrad_ws_elems floats, contents do
+ * not matter): no atomics, the same bits on every call; dW and db are stored.
+ * Each segment is summed on its own and the result is c0 S0 + c1 S1 + c2 S2
+ * with every product and sum rounded separately, so S0 == S1 under c0 == -c1
+ * (the head's bias gradient) gives exactly 0. */
+long long cg_mlp_wgrad_ws_elems(long long rows, int Cin, int Cout);
+int cg_mlp_dense_wgrad(const float* x, long long x_pitch, const float* x_tail,
+                       long long tail_row0, const float* dz, float* dW,
+                       float* db, long long rows, int Cin, int Cout,
+                       long long seg_rows, float c0, float c1, float c2,
+                       long long bias_rows, float* ws, void* stream);
+/* out [3][B][n] = [real | fake | alpha_b real + (1 - alpha_b) fake]
+ * (wgan_gp.py:38-41), all float32 [B][n] */
+int cg_mlp_interp(const float* real, const float* fake, const float* alpha,
+                  float* out, int B, long long n, void* stream);
+/* norm[b] = ||g[b]||, gp = mean((norm - 1)^2), coef[b] = penalty * 2 (norm - 1)
+ * / (B norm), v[b] = coef[b] g[b] (= penalty * dgp/dg; v may be NULL) and
+ * loss[0] / loss[1] as cg_critic_loss's out from d_out [3B]; g, v float32
+ * [B][n].  One launch, ordered sums. */
+int cg_mlp_gp_loss(const float* g, const float* d_out, float* norm, float* gp,
+                   float* coef, float* v, float* loss /*[2]*/, int B,
+                   long long n, float penalty, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -238,7 +238,8 @@ def main(hparams, return_metrics=False):
 
 def build_parser():
   """main.py:227-262 -- same flags and defaults (the reference's default
-  --model 'wavegan' is not registered there either; use --model calciumgan).
+  --model 'wavegan' is not registered there either; use --model calciumgan, or
+  --model mlp on a surrogate directory, where --dropout applies).
   --profile's meaning and --spike_metrics are this project's: the reference has
   no --spike_metrics flag (it deconvolves on the host inside its loop)."""
   parser = argparse.ArgumentParser()
