@@ -514,3 +514,126 @@ def pair_histograms_device(real, fake, num_bins=30, return_edges=True):
            real.stride(2), fake, fake.stride(0), fake.stride(1), fake.stride(2),
            P, C, num_bins, counts, valid, edges, status, hip.stream())
   return counts, valid, edges, status
+
+
+# -- pattern probabilities of the surrogate experiment ---------------------------
+# (compute_surrogate_metrics.py; csrc/patterns.hip)
+PATTERN_MAX_BITS = 24   # CG_PATTERN_HIST_MAX_BITS: 2^24 int64 counts are 128 MB
+PATTERN_SCORE_BITS = 16  # the marginal / pair figures of pattern_scores
+
+
+def pattern_codes(spikes):
+  """int64 (N,): the binary pattern of every sample of (N, T, C), any dtype and
+  any strides (a transposed view is walked in place): a frame is a spike when it
+  is != 0 (so a NaN is one and -0.0 is none), and
+    code[n] = sum_{t, c} [spikes[n, t, c] != 0] << (t C + c)."""
+  spikes = np.asarray(spikes)
+  if spikes.ndim != 3:
+    raise ValueError('(N, T, C) expected')
+  N, T, C = spikes.shape
+  if T * C > 62:
+    raise ValueError('T C = {} bits do not fit an int64 code'.format(T * C))
+  codes = np.zeros(N, np.int64)
+  for t in range(T):
+    for c in range(C):
+      codes |= (spikes[:, t, c] != 0).astype(np.int64) << (t * C + c)
+  return codes
+
+
+def pattern_histogram(spikes):
+  """int64 (2^K,), K = T C: the number of samples of (N, T, C) with each
+  `pattern_codes` code.  The statement cg_pattern_histogram (csrc/patterns.hip)
+  is tested against, for equality.  K > 24 is refused."""
+  spikes = np.asarray(spikes)
+  if spikes.ndim != 3:
+    raise ValueError('(N, T, C) expected')
+  K = spikes.shape[1] * spikes.shape[2]
+  if not 1 <= K <= PATTERN_MAX_BITS:
+    raise ValueError('T C = {} bits: 1 .. {} supported'.format(
+        K, PATTERN_MAX_BITS))
+  return np.bincount(pattern_codes(spikes), minlength=1 << K).astype(np.int64)
+
+
+def pattern_histogram_device(spikes):
+  """`pattern_histogram` on the GPU (cg_pattern_histogram): float32 device tensor
+  (N, T, C), any strides, -> device int64 (2^K,), the statement's counts.
+  Nothing is zeroed beforehand (the call's first launch does it), no host
+  synchronisation."""
+  import torch
+  from ... import _lib as hip
+  if not (torch.is_tensor(spikes) and spikes.is_cuda and
+          spikes.dtype == torch.float32 and spikes.dim() == 3):
+    raise ValueError('float32 device tensor (N, T, C) expected')
+  N, T, C = spikes.shape
+  nbytes = hip.load().cg_pattern_hist_ws_bytes(N, T, C)
+  if nbytes < 0:
+    raise ValueError('cg_pattern_histogram: unsupported shape {} (N >= 1, '
+                     '1 <= T C <= {})'.format((N, T, C), PATTERN_MAX_BITS))
+  ws = (torch.empty(nbytes, dtype=torch.uint8, device=spikes.device)
+        if nbytes else None)
+  counts = torch.empty(1 << (T * C), dtype=torch.int64, device=spikes.device)
+  hip.call('cg_pattern_histogram', spikes, N, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), counts, ws, nbytes, hip.stream())
+  return counts
+
+
+def _pattern_moments(q, K):
+  """(marginals (K,), covariances (K, K)) of the bits under the code
+  probabilities q (2^K,): E[b_i] and E[b_i b_j] - E[b_i] E[b_j]."""
+  bits = ((np.arange(1 << K)[:, None] >> np.arange(K)[None, :]) & 1).astype(
+      np.float64)
+  mean = q @ bits
+  second = bits.T @ (q[:, None] * bits)
+  return mean, second - mean[:, None] * mean[None, :]
+
+
+def pattern_scores(ref_counts, counts):
+  """How far the pattern probabilities q = counts / sum(counts) are from p =
+  ref_counts / sum(ref_counts); both integer (2^K,).  Host float64, whichever
+  device counted:
+    js_divergence_bits       1/2 sum p log2(p / m) + 1/2 sum q log2(q / m), m =
+                             (p + q) / 2; a term with a zero numerator is 0
+    log_prob_correlation     Pearson r of log10 p against log10 q over the codes
+                             present on both sides; NaN with fewer than two
+    unseen_mass              sum of q over the codes with ref_counts == 0
+    patterns_seen            [codes in ref_counts, codes in counts]
+    firing_probability_mae   mean |difference| of the K per-bit marginals
+    pair_covariance_mae      mean |difference| of the covariances of the bit
+                             pairs i < j (NaN for K = 1)
+  the last two formed from the counts, for K <= 16 only (None above)."""
+  ref = np.asarray(ref_counts)
+  cnt = np.asarray(counts)
+  if not (ref.ndim == 1 and ref.shape == cnt.shape and len(ref) >= 2 and
+          len(ref) & (len(ref) - 1) == 0):
+    raise ValueError('two count vectors (2^K,) expected')
+  if ref.sum() <= 0 or cnt.sum() <= 0 or (ref < 0).any() or (cnt < 0).any():
+    raise ValueError('counts must be non-negative and not all zero')
+  K = len(ref).bit_length() - 1
+  p = ref.astype(np.float64) / float(ref.sum())
+  q = cnt.astype(np.float64) / float(cnt.sum())
+  m = (p + q) / 2.0
+  js = 0.0
+  for side in (p, q):
+    on = side > 0
+    js += 0.5 * float(np.sum(side[on] * np.log2(side[on] / m[on])))
+  both = (ref > 0) & (cnt > 0)
+  r = float('nan')
+  if both.sum() >= 2:
+    with np.errstate(invalid='ignore', divide='ignore'):
+      r = float(np.corrcoef(np.log10(p[both]), np.log10(q[both]))[0, 1])
+  scores = {
+      'js_divergence_bits': js,
+      'log_prob_correlation': r,
+      'unseen_mass': float(q[ref == 0].sum()),
+      'patterns_seen': [int((ref > 0).sum()), int((cnt > 0).sum())],
+      'firing_probability_mae': None,
+      'pair_covariance_mae': None,
+  }
+  if K <= PATTERN_SCORE_BITS:
+    mean_p, cov_p = _pattern_moments(p, K)
+    mean_q, cov_q = _pattern_moments(q, K)
+    iu = np.triu_indices(K, k=1)
+    scores['firing_probability_mae'] = float(np.mean(np.abs(mean_p - mean_q)))
+    scores['pair_covariance_mae'] = (
+        float(np.mean(np.abs(cov_p[iu] - cov_q[iu]))) if K > 1 else float('nan'))
+  return scores

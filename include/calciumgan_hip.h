@@ -822,6 +822,39 @@ int cg_pair_histogram(const double* a, long long a_sp, long long a_si,
                       int* counts, int* valid, double* edges, int* status,
                       void* stream);
 
+/* Pattern counts of the surrogate experiment (patterns.hip; the numpy statement
+ * is spike_metrics.pattern_histogram).  Added under ABI 20.  A sample is T time
+ * steps x C neurons, K = T C bits:
+ *   bit(n, t, c) = spikes[n * s_n + t * s_t + c * s_c] != 0
+ *                  (the spike kernels' convention: a NaN is a spike, -0.0 is not)
+ *   code(n)      = sum_{t, c} bit(n, t, c) << (t * C + c)
+ *   counts[code] = number of samples n < N with that code, int64 [1 << K]
+ * Strides in elements, any sign: a (n, neurons, L) array is read in place as
+ * its (n, L, neurons) view.  Every element of counts is written by the call
+ * (its first launch zeroes them; no memset node), nothing has to be zeroed
+ * beforehand, and the same input gives the same bits every call: the additions
+ * are integer atomics.
+ * K <= CG_PATTERN_HIST_LDS_BITS: each workgroup counts into a private table in
+ * LDS and adds its non-zero entries to counts once.  Above: every count goes
+ * straight to global memory.  A workgroup takes CG_PATTERN_HIST_BLOCK_SAMPLES
+ * samples at a time and the grid has at most CG_PATTERN_HIST_MAX_BLOCKS
+ * workgroups, so one pass of the grid covers their product.
+ * ws: cg_pattern_hist_ws_bytes(N, T, C) bytes (0 for both present forms, which
+ * add into counts itself: ws may then be NULL; -1 for a shape the call refuses).
+ * CG_EINVAL (nothing launched, counts untouched): a NULL spikes or counts,
+ * N < 1 or N > 2^40 (a workgroup's table is 32-bit), T < 1, C < 1,
+ * K > CG_PATTERN_HIST_MAX_BITS, ws_bytes smaller than
+ * cg_pattern_hist_ws_bytes reports. */
+#define CG_PATTERN_HIST_MAX_BITS 24
+#define CG_PATTERN_HIST_LDS_BITS 13
+#define CG_PATTERN_HIST_BLOCK_SAMPLES 1024
+#define CG_PATTERN_HIST_MAX_BLOCKS 512
+long long cg_pattern_hist_ws_bytes(long long N, int T, int C);
+int cg_pattern_histogram(const float* spikes, long long N, int T, int C,
+                         long long s_n, long long s_t, long long s_c,
+                         long long* counts, void* ws, long long ws_bytes,
+                         void* stream);
+
 /* ---------------------------------------------------------------------------
  * FFT datasets (ifft.hip; the reference's generate_tfrecords.py --fft stores a
  * trace as its spectrum along time, channels [real | imag], and inverts it on
