@@ -12,6 +12,8 @@ Host-side numpy restatement of the reference's DG recipe:
 The recorded-data statistics the reference fits (generate_dg_data.py:16-39) are
 not available offline, so rates follow SURVEY 8(d): r_hz =
 clip(exp(N(-2.5, 1.2^2)), 0.005, 2.0) at 24 Hz, equicorrelation rho = 0.05.
+The DG twin of a recording that is at hand (fitted rates and correlations) is
+data/dg_fit.py with sample_spikes_corr below; dataset/generate_dg_data.py.
 """
 import numpy as np
 from scipy.stats import norm
@@ -36,6 +38,18 @@ def sample_spikes(gamma, rho, duration, rng):
   eps = rng.standard_normal((duration, n))
   eta = rng.standard_normal((duration, 1))
   z = np.sqrt(1.0 - rho) * eps + np.sqrt(rho) * eta
+  return (z + gamma[None, :] > 0).astype(np.float32).T
+
+
+def sample_spikes_corr(gamma, corr, duration, rng):
+  """(num_neurons, duration) float32 in {0,1} for any positive definite
+  correlation matrix: z = eps L^T with L L^T = corr, the law of the reference's
+  mnorm.rvs (dichot_gauss.py:173-179).  data/dg_fit.py fits gamma and corr to
+  a recording."""
+  gamma = np.asarray(gamma, dtype=np.float64).reshape(-1)
+  n = gamma.shape[0]
+  chol = np.linalg.cholesky(np.asarray(corr, dtype=np.float64))
+  z = rng.standard_normal((duration, n)) @ chol.T
   return (z + gamma[None, :] > 0).astype(np.float32).T
 
 

@@ -1050,6 +1050,43 @@ int cg_mlp_gp_loss(const float* g, const float* d_out, float* norm, float* gp,
                    float* coef, float* v, float* loss /*[2]*/, int B,
                    long long n, float penalty, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Added under ABI 20: latent correlations of the dichotomised-Gaussian model
+ * of a recording (dg_fit.hip; the numpy statement is data/dg_fit.py
+ * gauss_correlation, a restatement of the reference's
+ * DGOptimise.get_gauss_correlation).  Everything is float64 in both builds.
+ *
+ * For every pair i > j, with h = gamma[i], k = gamma[j], S = cov[i][j] (the
+ * lower triangle is the one that is read) and
+ *   f(l) = Phi_2(h, k; l) - fl32(fl32(rates[i]) fl32(rates[j])) - S
+ * (the reference's script multiplies float32 means in float32):
+ *   |S| <= 1e-10                      corr 0,        status 1
+ *   |f(-0.99999)| < tol               corr -0.99999, status 2
+ *   else |f(0.99999)| < tol           corr 0.99999,  status 3
+ *   else f(-0.99999) f(0.99999) > tol corr 0,        status 4
+ *   else bisection from [-0.99999, 0.99999]: l = (l0 + l1) / 2, f = f(l),
+ *     f > 0: l1 = l, f < 0: l0 = l, until |f| <= tol (status 0, iterations =
+ *     evaluations of the loop) or maxiters evaluations (status 5).  A midpoint
+ *     equal to an end of its bracket would be repeated by every later
+ *     iteration: the pair stops there with status 5 and iterations = maxiters.
+ * Phi_2 is Plackett's integral over 64 uniform panels of a 16-point
+ * Gauss-Legendre rule in asin(l) u, its 1024 terms added in a fixed order
+ * (sixteen runs of 64 consecutive nodes, then a tree over neighbouring runs);
+ * within 1e-11 of the exact value for |h|, |k| <= 3.8.
+ * corr float64, status and iterations int32, all dense [C][C]: every element is
+ * written, both triangles, the diagonal 1 / 0 / 0.  cov is read through its
+ * strides (in elements).  One launch: one 16-lane row per pair, a grid of at
+ * most CG_DG_FIT_MAX_BLOCKS workgroups of CG_DG_FIT_BLOCK_PAIRS pairs that
+ * walks the pairs.  No atomics, no workspace: the same bits every call.
+ * CG_EINVAL (nothing launched): a NULL pointer, C < 2 or C > 4096, tol <= 0 (or
+ * NaN), maxiters < 1. */
+#define CG_DG_FIT_MAX_BLOCKS 1024
+#define CG_DG_FIT_BLOCK_PAIRS 4
+int cg_dg_correlation(const double* rates, const double* gamma,
+                      const double* cov, long long cov_s0, long long cov_s1,
+                      int C, double tol, int maxiters, double* corr,
+                      int* status, int* iterations, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
