@@ -38,6 +38,9 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
     return (int)e__;                             \
   } while (0)
 
+// the C ABI's `void* stream`
+inline hipStream_t cg_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
 // Kernel-precise timing of the MFMA launches (cg_profile_enable /
 // cg_profile_collect in the C ABI): while enabled, a launch is issued through
 // hipExtLaunchKernelGGL with an event pair that carries the kernel's own begin /
@@ -164,15 +167,80 @@ __device__ __forceinline__ float group_max_n(float v, int n) {
   return v;
 }
 __device__ __forceinline__ float group_min_n(float v, int n) { return -group_max_n(-v, n); }
-__device__ __forceinline__ float wave_max(float v) {
+
+// Wave reduction with an operation: the DPP sum above for a float sum, for
+// every other type (double, int) an xor butterfly on __shfl_xor, offsets 32
+// down to 1.  (a + b == b + a: after every step both partners hold the same
+// bits, so every lane ends with the wave's value.)
+struct FoldSum {
+  template <class T>
+  static __device__ __forceinline__ T join(T a, T b) { return a + b; }
+};
+struct FoldMin {
+  static __device__ __forceinline__ double join(double a, double b) { return fmin(a, b); }
+};
+struct FoldMax {
+  static __device__ __forceinline__ double join(double a, double b) { return fmax(a, b); }
+};
+template <class Op = FoldSum, class T>
+__device__ __forceinline__ T wave_fold(T v) {
+  if constexpr (std::is_same_v<Op, FoldSum> && std::is_same_v<T, float>) {
+    return wave_sum(v);
+  } else {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
+    for (int o = 32; o > 0; o >>= 1) v = Op::join(v, __shfl_xor(v, o, 64));
+    return v;
+  }
 }
-__device__ __forceinline__ float wave_min(float v) {
+
+// The block fold, the one statement of the library's wave-then-index order:
+// every wave reduces its value and lane 0 leaves it in the wave's slot of the
+// caller's LDS (block_fold_put); after ONE barrier the NW slots are combined in
+// index order as a left fold, ((p0 + p1) + p2) + p3 (block_fold_get).  The
+// barrier is the caller's, and so is the choice of who gets the result (thread
+// 0, threads 0 .. K - 1, every thread).  K values go in one put -- the K wave
+// reductions interleave and lane 0 stores under one branch: `slot` is the
+// calling wave's slot of value 0, value k goes to slot[k * kstride], and v is
+// left holding the wave's values.  The bit-equality tests of the fused and
+// unfused chains rest on this order: a kernel that needs another one says why
+// next to it.  (The shapes -- v through a pointer, the K-value put handed the
+// wave's slot, the one-value put indexing the slots itself -- are those under
+// which hipcc emits the instruction streams the step's kernels had while each
+// wrote its fold out by hand; compare the device assembly before changing one.)
+template <int K, class Op = FoldSum, class T>
+__device__ __forceinline__ void block_fold_put(T* v, T* slot, int kstride) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
+  for (int k = 0; k < K; ++k) v[k] = wave_fold<Op>(v[k]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) slot[k * kstride] = v[k];
+  }
+}
+// one value: slots is wave 0's slot, the waves' slots are adjacent
+template <class Op = FoldSum, class T>
+__device__ __forceinline__ void block_fold_put(T& v, T* slots) {
+  v = wave_fold<Op>(v);
+  if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = v;
+}
+// slots: wave 0's slot of the value; wave w's is slots[w * wstride]
+template <int NW, class Op = FoldSum, class T>
+__device__ __forceinline__ T block_fold_get(const T* slots, int wstride = 1) {
+  T t = slots[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) t = Op::join(t, slots[w * wstride]);
+  return t;
+}
+// K values side by side (each still its own left fold): t[k] from the slots at
+// slots + k * kstride
+template <int NW, int K, class Op = FoldSum, class T>
+__device__ __forceinline__ void block_fold_get(T* t, const T* slots, int kstride) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) t[k] = slots[k * kstride];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) t[k] = Op::join(t[k], slots[k * kstride + w]);
+  }
 }
 
 // compile-time loop: f(integral_constant<int, 0>), ..., f(integral_constant<int, N - 1>)

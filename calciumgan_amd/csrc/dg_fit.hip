@@ -37,8 +37,6 @@
 
 namespace {
 
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kDgThreads = 64;
 constexpr int kDgRows = CG_DG_FIT_BLOCK_PAIRS;
 static_assert(kDgRows * 16 == kDgThreads, "one 16-lane row per pair");
@@ -228,7 +226,7 @@ extern "C" int cg_dg_correlation(const double* rates, const double* gamma,
   long long groups = (npairs + kDgRows - 1) / kDgRows;
   if (groups > CG_DG_FIT_MAX_BLOCKS) groups = CG_DG_FIT_MAX_BLOCKS;
   hipLaunchKernelGGL(dg_pairs_kernel, dim3((unsigned)groups), dim3(kDgThreads), 0,
-                     S_(stream), rates, gamma, cov, cov_s0, cov_s1, C, npairs, tol,
+                     cg_stream(stream), rates, gamma, cov, cov_s0, cov_s1, C, npairs, tol,
                      maxiters, corr, status, iterations);
   CG_LAUNCH_CHECK();
 }

@@ -35,8 +35,6 @@
 
 namespace {
 
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kIfftThreads = 512;
 constexpr int kIfftMinT = 32, kIfftMaxT = 8192;
 constexpr int kIfftMaxGrid = 1024;      // workgroups; beyond: grid-stride
@@ -222,6 +220,6 @@ extern "C" int cg_ifft_channels(const float* x, int B, int T, int C,
   const unsigned grid =
       (unsigned)(a.items < kIfftMaxGrid ? a.items : kIfftMaxGrid);
   hipLaunchKernelGGL(ifft_channels_kernel, dim3(grid), dim3(kIfftThreads),
-                     ifft_lds_bytes(T), S_(stream), a);
+                     ifft_lds_bytes(T), cg_stream(stream), a);
   CG_LAUNCH_CHECK();
 }

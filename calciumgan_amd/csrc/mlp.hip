@@ -343,6 +343,8 @@ __global__ void mlp_interp_kernel(const float* real, const float* fake,
   out[2 * total + e] = a * r + (1.f - a) * f;
 }
 
+// (an LDS tree, not cg_common.h's block fold: its order of additions differs
+// from wave-then-index, and moving it would change the MLP step's bits)
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
   const int t = threadIdx.x;
   red[t] = v;

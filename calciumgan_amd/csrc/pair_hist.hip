@@ -35,28 +35,10 @@
 
 namespace {
 
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kPhThreads = 512;
 constexpr int kPhWaves = kPhThreads / 64;
 constexpr int kPhMaxBins = 256;
 constexpr int kPhMaxC = 4096;
-
-__device__ __forceinline__ double ph_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double ph_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int ph_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(kPhThreads) void pair_hist_kernel(
     const double* __restrict__ a, long long a_sp, long long a_si, long long a_sj,
@@ -89,31 +71,23 @@ __global__ __launch_bounds__(kPhThreads) void pair_hist_kernel(
         }
       }
     }
-  mn = ph_wave_min(mn);
-  mx = ph_wave_max(mx);
-  cnt[0] = ph_wave_sum(cnt[0]);
-  cnt[1] = ph_wave_sum(cnt[1]);
+  // (the block fold in its two steps: the histograms are zeroed under the same
+  // barrier)
+  block_fold_put<FoldMin>(mn, sm_mn);
+  block_fold_put<FoldMax>(mx, sm_mx);
+  block_fold_put<2>(cnt, sm_cnt[wave], 1);
   inf = __any(inf);
-  if (lane == 0) {
-    sm_mn[wave] = mn;
-    sm_mx[wave] = mx;
-    sm_cnt[wave][0] = cnt[0];
-    sm_cnt[wave][1] = cnt[1];
-    sm_inf[wave] = inf;
-  }
+  if (lane == 0) sm_inf[wave] = inf;
   for (int k = lane; k < 2 * N; k += 64) sm_hist[wave][k / N][k % N] = 0;
   __syncthreads();
   // (every thread folds the waves' slots: the values are uniform from here on)
-  int n_a = 0, n_b = 0;
+  mn = block_fold_get<kPhWaves, FoldMin>(sm_mn);
+  mx = block_fold_get<kPhWaves, FoldMax>(sm_mx);
+  const int n_a = block_fold_get<kPhWaves>(&sm_cnt[0][0], 2);
+  const int n_b = block_fold_get<kPhWaves>(&sm_cnt[0][1], 2);
   inf = 0;
 #pragma unroll
-  for (int w = 0; w < kPhWaves; ++w) {
-    mn = w ? fmin(mn, sm_mn[w]) : sm_mn[0];
-    mx = w ? fmax(mx, sm_mx[w]) : sm_mx[0];
-    n_a += sm_cnt[w][0];
-    n_b += sm_cnt[w][1];
-    inf |= sm_inf[w];
-  }
+  for (int w = 0; w < kPhWaves; ++w) inf |= sm_inf[w];
   int st = ((n_a == 0 || n_b == 0) ? 1 : 0) | (inf ? 2 : 0);
   const bool have_edges = n_a + n_b > 0 && !inf;  // uniform
   if (have_edges) {
@@ -199,7 +173,7 @@ extern "C" int cg_pair_histogram(const double* a, long long a_sp, long long a_si
       num_bins < 1 || num_bins > kPhMaxBins)
     return CG_EINVAL;
   hipLaunchKernelGGL(pair_hist_kernel, dim3((unsigned)P), dim3(kPhThreads), 0,
-                     S_(stream), a, a_sp, a_si, a_sj, b, b_sp, b_si, b_sj, C,
+                     cg_stream(stream), a, a_sp, a_si, a_sj, b, b_sp, b_si, b_sj, C,
                      num_bins, counts, valid, edges, status);
   CG_LAUNCH_CHECK();
 }

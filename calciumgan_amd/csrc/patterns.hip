@@ -29,8 +29,6 @@
 
 namespace {
 
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kPtThreads = CG_PATTERN_HIST_BLOCK_SAMPLES;
 constexpr int kPtLdsSize = 1 << CG_PATTERN_HIST_LDS_BITS;
 constexpr int kPtZeroThreads = 256;
@@ -158,7 +156,7 @@ extern "C" int cg_pattern_histogram(const float* spikes, long long N, int T, int
   const long long zb = (size + kPtZeroThreads - 1) / kPtZeroThreads;
   hipLaunchKernelGGL(pattern_zero_kernel,
                      dim3((unsigned)(zb < kPtZeroMaxBlocks ? zb : kPtZeroMaxBlocks)),
-                     dim3(kPtZeroThreads), 0, S_(stream), counts, size);
+                     dim3(kPtZeroThreads), 0, cg_stream(stream), counts, size);
   const long long tiles = (N + kPtThreads - 1) / kPtThreads;
   const dim3 grid((unsigned)(tiles < CG_PATTERN_HIST_MAX_BLOCKS
                                  ? tiles
@@ -166,7 +164,7 @@ extern "C" int cg_pattern_histogram(const float* spikes, long long N, int T, int
   unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
 #define CG_PT_LAUNCH(LDS, PACKED)                                               \
   hipLaunchKernelGGL((pattern_count_kernel<LDS, PACKED>), grid,                 \
-                     dim3(kPtThreads), 0, S_(stream), spikes, N, s_n, off, K, out)
+                     dim3(kPtThreads), 0, cg_stream(stream), spikes, N, s_n, off, K, out)
   if (K <= CG_PATTERN_HIST_LDS_BITS) {
     if (packed) CG_PT_LAUNCH(true, true); else CG_PT_LAUNCH(true, false);
   } else {

@@ -1,8 +1,11 @@
 // HBM-bound kernels of the CalciumGAN hot path: LayerNorm(+LeakyReLU),
 // discriminator head, phase-unshuffle, WGAN-GP interpolation / penalty norm,
 // bias gradients, Keras Adam, signal metrics.  All loads/stores are 16-byte
-// (8 x bf16 or 4 x f32) per lane and row-contiguous; reductions use wavefront
-// shuffles (64 lanes) then one atomic per wave/block.
+// (8 x bf16 or 4 x f32) per lane and row-contiguous.  A reduction is a wave
+// sum (DPP / permlane swaps), the block fold of cg_common.h over the waves' LDS
+// slots, and then -- given a workspace, the default -- one partial row per block
+// that a finishing launch adds in a fixed order; without one, one atomic per
+// block.
 #include "cg_common.h"
 
 namespace {
@@ -41,7 +44,7 @@ struct FinishArgs {
 
 // block = 64 columns x 16 row classes: wave j adds rows j, j + 16, ... (fixed
 // order), the sixteen sums meet through LDS in order 0..15
-__global__ __launch_bounds__(1024) void finish_cols_kernel(FinishArgs f) {
+__device__ __forceinline__ void finish_cols(const FinishArgs& f) {
   __shared__ float sm[16][64];
   const int lane = threadIdx.x & 63;
   const int j = threadIdx.x >> 6;
@@ -63,12 +66,11 @@ __global__ __launch_bounds__(1024) void finish_cols_kernel(FinishArgs f) {
   }
   sm[j][lane] = s;
   __syncthreads();
-  if (j == 0 && c < f.cvalid[o]) {
-    float t = sm[0][lane];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) t += sm[k][lane];
-    f.out[o][c] = t * f.scale;
-  }
+  if (j == 0 && c < f.cvalid[o])
+    f.out[o][c] = block_fold_get<16>(&sm[0][lane], 64) * f.scale;
+}
+__global__ __launch_bounds__(1024) void finish_cols_kernel(FinishArgs f) {
+  finish_cols(f);
 }
 
 // Deferred finishing launches (round 5).  The finishing launch of a reduction
@@ -90,32 +92,7 @@ thread_local FinishBatch g_finish_batch;
 __global__ __launch_bounds__(1024) void finish_cols_batched_kernel(FinishBatch b) {
   const FinishArgs& f = b.f[blockIdx.z];
   if ((int)blockIdx.y >= f.nout || (int)blockIdx.x * 64 >= f.ncol) return;
-  __shared__ float sm[16][64];
-  const int lane = threadIdx.x & 63;
-  const int j = threadIdx.x >> 6;
-  const int o = blockIdx.y;
-  const int c = blockIdx.x * 64 + lane;
-  float s = 0.f;
-  if (c < f.ncol) {
-    const float* p = f.ws + (long long)o * f.cstride + c;
-    int r = j;
-    for (; r + 112 < f.nparts; r += 128) {
-      float a[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) a[k] = p[(long long)(r + 16 * k) * f.pstride];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s += a[k];
-    }
-    for (; r < f.nparts; r += 16) s += p[(long long)r * f.pstride];
-  }
-  sm[j][lane] = s;
-  __syncthreads();
-  if (j == 0 && c < f.cvalid[o]) {
-    float t = sm[0][lane];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) t += sm[k][lane];
-    f.out[o][c] = t * f.scale;
-  }
+  finish_cols(f);
 }
 
 inline void flush_finishes(hipStream_t s) {
@@ -767,15 +744,9 @@ __global__ __launch_bounds__(NT) void dense1_fwd_kernel(
       if (delta && i < F) store8(delta + (long long)b * F + i, o);
     }
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  block_fold_put(s, part);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = part[0];
-#pragma unroll
-    for (int k = 1; k < NT / 64; ++k) t += part[k];
-    out[b] = t + bias[0];
-  }
+  if (threadIdx.x == 0) out[b] = block_fold_get<NT / 64>(part) + bias[0];
 }
 
 // The seed with every product rounded to f32, THEN to the activation type -- what
@@ -971,14 +942,10 @@ __global__ __launch_bounds__(NT) void dense1_bce_kernel(
       if (kRow > 1 && i < F) row[i >> 3] = raw[k];
     }
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  block_fold_put(s, part);
   __syncthreads();
   if (threadIdx.x == 0) {
-    float t = part[0];
-#pragma unroll
-    for (int k = 1; k < NT / 64; ++k) t += part[k];
-    const float x = t + bias[0];
+    const float x = block_fold_get<NT / 64>(part) + bias[0];
     out[b] = x;
     const float inv_b = 1.f / (float)B;
     // s(x) - 1 as -s(-x): no cancellation for large positive x
@@ -1034,25 +1001,13 @@ __global__ __launch_bounds__(kThreads) void dense1_bce_finish(
     sr += terms[B + b];
     sg += terms[2 * B + b];
   }
-  sf = wave_sum(sf);
-  sr = wave_sum(sr);
-  sg = wave_sum(sg);
-  if ((threadIdx.x & 63) == 0) {
-    part[0][threadIdx.x >> 6] = sf;
-    part[1][threadIdx.x >> 6] = sr;
-    part[2][threadIdx.x >> 6] = sg;
-  }
+  float v[3] = {sf, sr, sg};
+  block_fold_put<3>(v, &part[0][threadIdx.x >> 6], kThreads / 64);
   __syncthreads();
   if (threadIdx.x == 0) {
-    float f = part[0][0], r = part[1][0], g = part[2][0];
-#pragma unroll
-    for (int k = 1; k < kThreads / 64; ++k) {
-      f += part[0][k];
-      r += part[1][k];
-      g += part[2][k];
-    }
-    loss[0] = g / (float)B;
-    loss[1] = r / (float)B + f / (float)B;
+    block_fold_get<kThreads / 64, 3>(v, &part[0][0], kThreads / 64);
+    loss[0] = v[2] / (float)B;
+    loss[1] = v[1] / (float)B + v[0] / (float)B;
   }
 }
 
@@ -1197,11 +1152,10 @@ __global__ __launch_bounds__(kThreads) void sumsq_kernel(
 #pragma unroll
     for (int e = 0; e < 8; ++e) s += v[e] * v[e];
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  block_fold_put(s, part);
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float t = ((part[0] + part[1]) + part[2]) + part[3];
+    const float t = block_fold_get<4>(part);
     if (ws) ws[(long long)b * gridDim.x + blockIdx.x] = t;
     else atomicAdd(sumsq + b, t);
   }
@@ -1230,26 +1184,66 @@ __global__ void sqrt_kernel(float* v, int n) {
   if (i < n) v[i] = sqrtf(v[i]);
 }
 
+// dgp/dnorm per sample (x coef_mul)
+__device__ __forceinline__ float gp_coef(float nv, int B, float scale, float coef_mul) {
+  const float d = nv - 1.f;
+  return scale * 2.f * d / (B * nv) * coef_mul;
+}
+// a sample's norm as cg_rownorm left it: the norm, or its square (then the
+// norm is written back)
+__device__ __forceinline__ float gp_load_norm(float* __restrict__ norm, int b,
+                                              int squared) {
+  float nv = norm[b];
+  if (squared) {
+    nv = sqrtf(nv);
+    norm[b] = nv;
+  }
+  return nv;
+}
+
+// The WGAN-GP penalty tail, one block of kThreads: with nv = norm_of(b) the
+// norm of sample b, coef[b] = gp_coef(nv), gp[0] = mean (nv - 1)^2 and, kLoss,
+// loss[0] = -mean d_out[0 .. B) + mean d_out[B .. 2B) + scale * gp[0],
+// loss[1] = -mean d_out[B .. 2B).  Its callers differ in where a norm comes from.
+template <bool kLoss, class NormOf>
+__device__ __forceinline__ void gp_tail(NormOf norm_of, float* __restrict__ gp,
+                                        float* __restrict__ coef,
+                                        const float* __restrict__ d_out,
+                                        float* __restrict__ loss, int B, float scale,
+                                        float coef_mul) {
+  __shared__ float part[kLoss ? 3 : 1][4];
+  float s = 0.f, sr = 0.f, sf = 0.f;
+  for (int b = threadIdx.x; b < B; b += kThreads) {
+    const float nv = norm_of(b);
+    const float d = nv - 1.f;
+    s += d * d;
+    coef[b] = gp_coef(nv, B, scale, coef_mul);
+    if constexpr (kLoss) {
+      sr += d_out[b];
+      sf += d_out[B + b];
+    }
+  }
+  float v[3] = {s, sr, sf};
+  block_fold_put<kLoss ? 3 : 1>(v, &part[0][threadIdx.x >> 6], 4);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float g = block_fold_get<4>(part[0]) / B;
+    gp[0] = g;
+    if constexpr (kLoss) {
+      const float mr = block_fold_get<4>(part[1]) / B;
+      const float mf = block_fold_get<4>(part[2]) / B;
+      loss[0] = -mr + mf + scale * g;
+      loss[1] = -mf;
+    }
+  }
+}
+
 __global__ void gp_finalize_kernel(float* __restrict__ norm,
                                    float* __restrict__ gp,
                                    float* __restrict__ coef, int B, float scale,
                                    int squared) {
-  __shared__ float part[4];
-  float s = 0.f;
-  for (int b = threadIdx.x; b < B; b += kThreads) {
-    float nv = norm[b];
-    if (squared) {
-      nv = sqrtf(nv);
-      norm[b] = nv;
-    }
-    const float d = nv - 1.f;
-    s += d * d;
-    coef[b] = scale * 2.f * d / (B * nv);
-  }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) gp[0] = (part[0] + part[1] + part[2] + part[3]) / B;
+  gp_tail<false>([=](int b) { return gp_load_norm(norm, b, squared); }, gp, coef,
+                 nullptr, nullptr, B, scale, 1.f);
 }
 
 __global__ __launch_bounds__(kThreads) void scale_rows_kernel(
@@ -1270,22 +1264,18 @@ __global__ __launch_bounds__(kThreads) void scale_rows_kernel(
 __global__ void critic_loss_kernel(const float* __restrict__ d_out,
                                    const float* __restrict__ gp, float penalty,
                                    float* __restrict__ out, int B) {
-  __shared__ float pr[4], pf[4];
+  __shared__ float part[2][4];
   float sr = 0.f, sf = 0.f;
   for (int b = threadIdx.x; b < B; b += kThreads) {
     sr += d_out[b];
     sf += d_out[B + b];
   }
-  sr = wave_sum(sr);
-  sf = wave_sum(sf);
-  if ((threadIdx.x & 63) == 0) {
-    pr[threadIdx.x >> 6] = sr;
-    pf[threadIdx.x >> 6] = sf;
-  }
+  float v[2] = {sr, sf};
+  block_fold_put<2>(v, &part[0][threadIdx.x >> 6], 4);
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float mr = (pr[0] + pr[1] + pr[2] + pr[3]) / B;
-    const float mf = (pf[0] + pf[1] + pf[2] + pf[3]) / B;
+    const float mr = block_fold_get<4>(part[0]) / B;
+    const float mf = block_fold_get<4>(part[1]) / B;
     out[0] = -mr + mf + penalty * gp[0];
     out[1] = -mf;
   }
@@ -1296,10 +1286,9 @@ __global__ void neg_mean_kernel(const float* __restrict__ d_out,
   __shared__ float pr[4];
   float s = 0.f;
   for (int b = threadIdx.x; b < B; b += kThreads) s += d_out[b];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) pr[threadIdx.x >> 6] = s;
+  block_fold_put(s, pr);
   __syncthreads();
-  if (threadIdx.x == 0) out[0] = -(pr[0] + pr[1] + pr[2] + pr[3]) / B;
+  if (threadIdx.x == 0) out[0] = -block_fold_get<4>(pr) / B;
 }
 
 // column sums: block handles `rows_per_block` rows of one slab of up to 2048
@@ -1572,6 +1561,7 @@ __global__ __launch_bounds__(kThreads) void signal_metrics_kernel(
             s += t;
           }
       }
+      // (rows wider than 512 channels: not on any step's path, left on shuffles)
       for (int o = lpr >> 1; o > 0; o >>= 1) {
         mn = fminf(mn, __shfl_xor(mn, o, 64));
         mx = fmaxf(mx, __shfl_xor(mx, o, 64));
@@ -1601,14 +1591,10 @@ __global__ __launch_bounds__(kThreads) void signal_metrics_kernel(
       }
     }
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) acc[k] = wave_sum(acc[k]);
-  if (lane == 0)
-    for (int k = 0; k < 4; ++k) part[wave][k] = acc[k];
+  block_fold_put<4>(acc, part[wave], 1);
   __syncthreads();
   if (threadIdx.x < 4) {
-    const float t = ((part[0][threadIdx.x] + part[1][threadIdx.x]) +
-                     part[2][threadIdx.x]) + part[3][threadIdx.x];
+    const float t = block_fold_get<4>(&part[0][threadIdx.x], 4);
     if (ws) ws[(long long)blockIdx.x * 4 + threadIdx.x] = t;
     else atomicAdd(out + threadIdx.x, t);
   }
@@ -1641,7 +1627,6 @@ inline int rows_per_slot_for(long long rows, int rpw, int lo, int hi) {
 
 }  // namespace
 
-#define S_(x) ((hipStream_t)(x))
 #define U16(x) (reinterpret_cast<const uint16_t*>(x))
 #define U16W(x) (reinterpret_cast<uint16_t*>(x))
 
@@ -1664,7 +1649,7 @@ extern "C" int cg_ln_lrelu_fwd(const void* y_pre, const float* gamma,
     const dim3 grid(grid1d(rows, 4 * 8 * rps, 1LL << 31));
 #define CG_LN8(G)                                                                 \
   case G:                                                                         \
-    hipLaunchKernelGGL(ln_fwd8_kernel<G>, grid, dim3(kThreads), 0, S_(stream),    \
+    hipLaunchKernelGGL(ln_fwd8_kernel<G>, grid, dim3(kThreads), 0, cg_stream(stream),    \
                        U16(y_pre), gamma, beta, U16W(h), mean, rstd, rows, C, Cp, \
                        eps, alpha, rps);                                          \
     break;
@@ -1679,7 +1664,7 @@ extern "C" int cg_ln_lrelu_fwd(const void* y_pre, const float* gamma,
   const int rows_per_slot = rows_per_slot_for(rows, rpw, kLnFwdRpsLo, kLnFwdRpsHi);
   hipLaunchKernelGGL(ln_fwd_kernel,
                      dim3(grid1d(rows, 4 * rpw * rows_per_slot, 1LL << 31)),
-                     dim3(kThreads), 0, S_(stream), U16(y_pre), gamma, beta,
+                     dim3(kThreads), 0, cg_stream(stream), U16(y_pre), gamma, beta,
                      U16W(h), mean, rstd, rows, C, Cp, eps, alpha, lpr, l2,
                      rows_per_slot);
   CG_LAUNCH_CHECK();
@@ -1695,7 +1680,7 @@ extern "C" int cg_finish_defer(int on) {
 }
 
 extern "C" int cg_finish_flush(void* stream) {
-  flush_finishes(S_(stream));
+  flush_finishes(cg_stream(stream));
   g_finish_defer = false;
   CG_LAUNCH_CHECK();
 }
@@ -1724,7 +1709,7 @@ extern "C" int cg_ln_lrelu_bwd(const void* dh, const void* h, const void* y_pre,
       rows_per_slot *= 2;
   }
   const unsigned blocks = grid1d(rows, 4 * rpw * rows_per_slot, 1LL << 31);
-  hipLaunchKernelGGL(ln_bwd_kernel, dim3(blocks), dim3(kThreads), 0, S_(stream),
+  hipLaunchKernelGGL(ln_bwd_kernel, dim3(blocks), dim3(kThreads), 0, cg_stream(stream),
                      U16(dh), U16(h), U16(y_pre), mean, rstd, gamma, U16W(dy),
                      dgamma, dbeta, dbias, rows, C, Cp, alpha, lpr, l2,
                      rows_per_slot, ws);
@@ -1734,7 +1719,7 @@ extern "C" int cg_ln_lrelu_bwd(const void* dh, const void* h, const void* y_pre,
     f.cstride = Cp; f.nout = dbias ? 3 : 2; f.scale = 1.f;
     f.out[0] = dgamma; f.out[1] = dbeta; f.out[2] = dbias;
     f.cvalid[0] = f.cvalid[1] = f.cvalid[2] = C;
-    launch_finish(f, S_(stream));
+    launch_finish(f, cg_stream(stream));
   }
   CG_LAUNCH_CHECK();
 }
@@ -1760,11 +1745,11 @@ extern "C" int cg_bn_stats(const void* y, long long rows, int C, int Cp,
   const int rpb = bn_rows_per_block(rows, Cp);
   const unsigned blocks = grid1d(rows, rpb, 1LL << 31);
   hipLaunchKernelGGL(bn_sums_kernel<0>, dim3(blocks), dim3(kThreads), 0,
-                     S_(stream), U16(y), (const uint16_t*)nullptr,
+                     cg_stream(stream), U16(y), (const uint16_t*)nullptr,
                      (const uint16_t*)nullptr, (const float*)nullptr,
                      (const float*)nullptr, rows, C, Cp, rpb, 0.f, 1.f, 0, ws);
   hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((Cp + 63) / 64), dim3(1024), 0,
-                     S_(stream), ws, (int)blocks, C, Cp, rows, rpb, mean, var,
+                     cg_stream(stream), ws, (int)blocks, C, Cp, rows, rpb, mean, var,
                      moving_mean, moving_var, momentum);
   CG_LAUNCH_CHECK();
 }
@@ -1778,7 +1763,7 @@ extern "C" int cg_bn_apply(const void* y, const float* mean, const float* var,
     return CG_EINVAL;
   const long long total8 = rows * Cp / 8;
   hipLaunchKernelGGL(bn_apply_kernel, dim3(grid1d(total8, kThreads, 1LL << 31)),
-                     dim3(kThreads), 0, S_(stream), U16(y), mean, var, gamma, beta,
+                     dim3(kThreads), 0, cg_stream(stream), U16(y), mean, var, gamma, beta,
                      U16W(out), C, Cp, eps, alpha, total8);
   CG_LAUNCH_CHECK();
 }
@@ -1794,18 +1779,18 @@ extern "C" int cg_bn_bwd(const void* dout, const void* h, const void* y,
   const int rpb = bn_rows_per_block(rows, Cp);
   const unsigned blocks = grid1d(rows, rpb, 1LL << 31);
   hipLaunchKernelGGL(bn_sums_kernel<1>, dim3(blocks), dim3(kThreads), 0,
-                     S_(stream), U16(y), U16(dout), U16(h), mean, var, rows, C, Cp,
+                     cg_stream(stream), U16(y), U16(dout), U16(h), mean, var, rows, C, Cp,
                      rpb, eps, alpha, act, ws);
   FinishArgs f;
   f.ws = ws; f.nparts = (int)blocks; f.ncol = Cp; f.pstride = 2ll * Cp;
   f.cstride = Cp; f.nout = 2; f.scale = 1.f;
   f.out[0] = dbeta; f.out[1] = dgamma; f.out[2] = nullptr;
   f.cvalid[0] = f.cvalid[1] = C; f.cvalid[2] = 0;
-  launch_finish(f, S_(stream));
+  launch_finish(f, cg_stream(stream));
   const long long total8 = rows * Cp / 8;
   hipLaunchKernelGGL(bn_bwd_apply_kernel,
                      dim3(grid1d(total8, kThreads, 1LL << 31)), dim3(kThreads), 0,
-                     S_(stream), U16(dout), U16(h), U16(y), mean, var, gamma,
+                     cg_stream(stream), U16(dout), U16(h), U16(y), mean, var, gamma,
                      dgamma, dbeta, U16W(dy), C, Cp, eps, alpha, act,
                      1.f / (float)rows, total8);
   CG_LAUNCH_CHECK();
@@ -1817,11 +1802,11 @@ extern "C" int cg_dense1_fwd(const void* h, const float* w, const float* bias,
   const int F = Lt * Cp;
   if (Cp % 8 || C > Cp || nB < 1) return CG_EINVAL;
   if (F >= 8192)
-    hipLaunchKernelGGL(dense1_fwd_kernel<1024>, dim3(nB), dim3(1024), 0, S_(stream),
-                       U16(h), w, bias, out, F, C, Cp, (const float*)nullptr,
-                       (uint16_t*)nullptr, 1, 1.f);
+    hipLaunchKernelGGL(dense1_fwd_kernel<1024>, dim3(nB), dim3(1024), 0,
+                       cg_stream(stream), U16(h), w, bias, out, F, C, Cp,
+                       (const float*)nullptr, (uint16_t*)nullptr, 1, 1.f);
   else
-    hipLaunchKernelGGL(dense1_fwd_kernel<256>, dim3(nB), dim3(256), 0, S_(stream),
+    hipLaunchKernelGGL(dense1_fwd_kernel<256>, dim3(nB), dim3(256), 0, cg_stream(stream),
                        U16(h), w, bias, out, F, C, Cp, (const float*)nullptr,
                        (uint16_t*)nullptr, 1, 1.f);
   CG_LAUNCH_CHECK();
@@ -1835,11 +1820,11 @@ extern "C" int cg_dense1_fwd_bwd(const void* h, const float* w, const float* bia
   if (Cp % 8 || C > Cp || nB < 1 || seg_size < 1 || !coef || !delta)
     return CG_EINVAL;
   if (F >= 8192)
-    hipLaunchKernelGGL(dense1_fwd_kernel<1024>, dim3(nB), dim3(1024), 0, S_(stream),
-                       U16(h), w, bias, out, F, C, Cp, coef, U16W(delta), seg_size,
-                       alpha);
+    hipLaunchKernelGGL(dense1_fwd_kernel<1024>, dim3(nB), dim3(1024), 0,
+                       cg_stream(stream), U16(h), w, bias, out, F, C, Cp, coef,
+                       U16W(delta), seg_size, alpha);
   else
-    hipLaunchKernelGGL(dense1_fwd_kernel<256>, dim3(nB), dim3(256), 0, S_(stream),
+    hipLaunchKernelGGL(dense1_fwd_kernel<256>, dim3(nB), dim3(256), 0, cg_stream(stream),
                        U16(h), w, bias, out, F, C, Cp, coef, U16W(delta), seg_size,
                        alpha);
   CG_LAUNCH_CHECK();
@@ -1852,37 +1837,8 @@ __global__ void gp_critic_loss_kernel(float* __restrict__ norm, float* __restric
                                       const float* __restrict__ d_out,
                                       float* __restrict__ loss, int B, float scale,
                                       int squared, float coef_mul) {
-  __shared__ float part[3][4];
-  float s = 0.f, sr = 0.f, sf = 0.f;
-  for (int b = threadIdx.x; b < B; b += kThreads) {
-    float nv = norm[b];
-    if (squared) {
-      nv = sqrtf(nv);
-      norm[b] = nv;
-    }
-    const float d = nv - 1.f;
-    s += d * d;
-    coef[b] = scale * 2.f * d / (B * nv) * coef_mul;
-    sr += d_out[b];
-    sf += d_out[B + b];
-  }
-  s = wave_sum(s);
-  sr = wave_sum(sr);
-  sf = wave_sum(sf);
-  if ((threadIdx.x & 63) == 0) {
-    part[0][threadIdx.x >> 6] = s;
-    part[1][threadIdx.x >> 6] = sr;
-    part[2][threadIdx.x >> 6] = sf;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float g = (part[0][0] + part[0][1] + part[0][2] + part[0][3]) / B;
-    const float mr = (part[1][0] + part[1][1] + part[1][2] + part[1][3]) / B;
-    const float mf = (part[2][0] + part[2][1] + part[2][2] + part[2][3]) / B;
-    gp[0] = g;
-    loss[0] = -mr + mf + scale * g;
-    loss[1] = -mf;
-  }
+  gp_tail<true>([=](int b) { return gp_load_norm(norm, b, squared); }, gp, coef,
+                d_out, loss, B, scale, coef_mul);
 }
 
 extern "C" int cg_gp_critic_loss(float* norm, float* gp, float* coef,
@@ -1890,17 +1846,11 @@ extern "C" int cg_gp_critic_loss(float* norm, float* gp, float* coef,
                                  float penalty, int squared, float coef_mul,
                                  void* stream) {
   if (!norm || !gp || !coef || !d_out || !loss || B < 1) return CG_EINVAL;
-  hipLaunchKernelGGL(gp_critic_loss_kernel, dim3(1), dim3(kThreads), 0, S_(stream),
+  hipLaunchKernelGGL(gp_critic_loss_kernel, dim3(1), dim3(kThreads), 0, cg_stream(stream),
                      norm, gp, coef, d_out, loss, B, penalty, squared, coef_mul);
   CG_LAUNCH_CHECK();
 }
 
-// dgp/dnorm per sample (x coef_mul), the one expression both halves of
-// gp_loss_scale_kernel use
-__device__ __forceinline__ float gp_coef(float nv, int B, float scale, float coef_mul) {
-  const float d = nv - 1.f;
-  return scale * 2.f * d / (B * nv) * coef_mul;
-}
 __device__ __forceinline__ float slot_sum(const float* __restrict__ ws, int P, int b) {
   float s = 0.f;
   for (int j = 0; j < P; ++j) s += ws[(long long)b * P + j];  // slot order
@@ -1918,34 +1868,13 @@ __global__ __launch_bounds__(kThreads) void gp_loss_scale_kernel(
     float coef_mul, const uint16_t* __restrict__ g, uint16_t* __restrict__ dst,
     long long n, long long total8) {
   if (blockIdx.x + 1 == gridDim.x) {
-    __shared__ float part[3][4];
-    float s = 0.f, sr = 0.f, sf = 0.f;
-    for (int b = threadIdx.x; b < B; b += kThreads) {
-      const float nv = sqrtf(slot_sum(ssq_ws, P, b));
-      norm[b] = nv;
-      const float d = nv - 1.f;
-      s += d * d;
-      coef[b] = gp_coef(nv, B, scale, coef_mul);
-      sr += d_out[b];
-      sf += d_out[B + b];
-    }
-    s = wave_sum(s);
-    sr = wave_sum(sr);
-    sf = wave_sum(sf);
-    if ((threadIdx.x & 63) == 0) {
-      part[0][threadIdx.x >> 6] = s;
-      part[1][threadIdx.x >> 6] = sr;
-      part[2][threadIdx.x >> 6] = sf;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float gm = (part[0][0] + part[0][1] + part[0][2] + part[0][3]) / B;
-      const float mr = (part[1][0] + part[1][1] + part[1][2] + part[1][3]) / B;
-      const float mf = (part[2][0] + part[2][1] + part[2][2] + part[2][3]) / B;
-      gp[0] = gm;
-      loss[0] = -mr + mf + scale * gm;
-      loss[1] = -mf;
-    }
+    gp_tail<true>(
+        [=](int b) {
+          const float nv = sqrtf(slot_sum(ssq_ws, P, b));
+          norm[b] = nv;
+          return nv;
+        },
+        gp, coef, d_out, loss, B, scale, coef_mul);
     return;
   }
   const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -1971,8 +1900,8 @@ extern "C" int cg_gp_loss_scale(const float* ssq_ws, int P, float* norm, float* 
   const long long total8 = g ? (long long)B * n / 8 : 0;
   const unsigned blocks = (unsigned)((total8 + kThreads - 1) / kThreads) + 1;
   hipLaunchKernelGGL(gp_loss_scale_kernel, dim3(blocks), dim3(kThreads), 0,
-                     S_(stream), ssq_ws, P, norm, gp, coef, d_out, loss, B, penalty,
-                     coef_mul, U16(g), U16W(dst), n, total8);
+                     cg_stream(stream), ssq_ws, P, norm, gp, coef, d_out, loss, B,
+                     penalty, coef_mul, U16(g), U16W(dst), n, total8);
   CG_LAUNCH_CHECK();
 }
 
@@ -1983,7 +1912,7 @@ extern "C" int cg_dense1_bwd(const float* w, const float* coef, const void* h,
   if (Cp % 8 || C > Cp || nB < 1 || seg_size < 1) return CG_EINVAL;
   const long long total8 = (long long)nB * F / 8;
   hipLaunchKernelGGL(dense1_bwd_kernel, dim3(grid1d(total8, kThreads, 1LL << 31)),
-                     dim3(kThreads), 0, S_(stream), w, coef, U16(h),
+                     dim3(kThreads), 0, cg_stream(stream), w, coef, U16(h),
                      U16W(delta), F, C, Cp, seg_size, alpha, total8);
   CG_LAUNCH_CHECK();
 }
@@ -2001,11 +1930,11 @@ extern "C" int cg_dense1_wgrad(const void* x, const float* coef,
   const int Fpad = gx * kThreads * 8;
   if (ws && (long long)gy * Fpad + gy > kReduceWsElems) return CG_EINVAL;
   hipLaunchKernelGGL(dense1_wgrad_kernel, dim3(gx, gy), dim3(kThreads), 0,
-                     S_(stream), U16(x), coef, bias_coef, dw, db, nB, F, C,
+                     cg_stream(stream), U16(x), coef, bias_coef, dw, db, nB, F, C,
                      Cp, seg_size, ws, Fpad);
   if (ws)
     hipLaunchKernelGGL(dense1_wgrad_finish, dim3((F + kThreads - 1) / kThreads),
-                       dim3(kThreads), 0, S_(stream), ws, dw, db, gy, F, Fpad, C,
+                       dim3(kThreads), 0, cg_stream(stream), ws, dw, db, gy, F, Fpad, C,
                        Cp, bias_coef ? 1 : 0);
   CG_LAUNCH_CHECK();
 }
@@ -2028,9 +1957,10 @@ extern "C" int cg_dense1_bce(const void* h, const float* w, const float* bias,
   const dim3 grid(2 * B);
   const bool lds = delta_d && F / 8 <= kBceLdsGroups;
 #define CG_BCE_LAUNCH(NT, ROW)                                                      \
-  hipLaunchKernelGGL((dense1_bce_kernel<NT, ROW>), grid, dim3(NT), 0, S_(stream),   \
-                     U16(h), w, bias, out, coef_d, coef_g, U16W(delta_d),           \
-                     U16W(delta_g), scale_d, scale_g, ws, loss, B, F, C, Cp, alpha)
+  hipLaunchKernelGGL((dense1_bce_kernel<NT, ROW>), grid, dim3(NT), 0,               \
+                     cg_stream(stream), U16(h), w, bias, out, coef_d, coef_g,       \
+                     U16W(delta_d), U16W(delta_g), scale_d, scale_g, ws, loss, B,   \
+                     F, C, Cp, alpha)
   if (F >= 8192) {
     if (lds) CG_BCE_LAUNCH(1024, kBceLdsGroups);
     else CG_BCE_LAUNCH(1024, 1);
@@ -2040,7 +1970,7 @@ extern "C" int cg_dense1_bce(const void* h, const float* w, const float* bias,
   }
 #undef CG_BCE_LAUNCH
   if (ws)
-    hipLaunchKernelGGL(dense1_bce_finish, dim3(1), dim3(kThreads), 0, S_(stream),
+    hipLaunchKernelGGL(dense1_bce_finish, dim3(1), dim3(kThreads), 0, cg_stream(stream),
                        ws, loss, B);
   CG_LAUNCH_CHECK();
 }
@@ -2052,7 +1982,7 @@ extern "C" int cg_unshuffle_mask(const void* e, const void* h, void* delta,
   const long long total8 = (long long)nB * w * Cp / 8;
   hipLaunchKernelGGL(unshuffle_mask_kernel,
                      dim3(grid1d(total8, kThreads, 1LL << 31)), dim3(kThreads),
-                     0, S_(stream), U16(e), U16(h), U16W(delta), shifts, w, Cp,
+                     0, cg_stream(stream), U16(e), U16(h), U16W(delta), shifts, w, Cp,
                      seg_size, alpha, total8);
   CG_LAUNCH_CHECK();
 }
@@ -2067,7 +1997,7 @@ extern "C" int cg_unshuffle_fixup(const void* side, const void* h, void* delta,
   const long long total8 = (long long)nB * side_rows * Cp / 8;
   hipLaunchKernelGGL(unshuffle_fixup_kernel,
                      dim3(grid1d(total8, kThreads, 1LL << 31)), dim3(kThreads),
-                     0, S_(stream), U16(side), U16(h), U16W(delta), shifts, w,
+                     0, cg_stream(stream), U16(side), U16(h), U16W(delta), shifts, w,
                      Cp, seg_size, side_rows, alpha, total8);
   CG_LAUNCH_CHECK();
 }
@@ -2080,7 +2010,7 @@ extern "C" int cg_interp_pack(const float* real, const float* fake,
   const long long total8 = (long long)B * L * Cp / 8;
   hipLaunchKernelGGL(interp_pack_kernel,
                      dim3(grid1d(total8, kThreads, 1LL << 31)), dim3(kThreads),
-                     0, S_(stream), real, fake, alpha, U16W(x0), B, L, C, Cr,
+                     0, cg_stream(stream), real, fake, alpha, U16W(x0), B, L, C, Cr,
                      Cf, Cp, total8, write_real);
   CG_LAUNCH_CHECK();
 }
@@ -2090,7 +2020,7 @@ extern "C" int cg_cast_pad(const float* src, void* dst, long long rows, int C,
   if (Cp % 8 || C > Cp || C > Cs) return CG_EINVAL;
   const long long total8 = rows * Cp / 8;
   hipLaunchKernelGGL(cast_pad_kernel, dim3(grid1d(total8, kThreads, 1LL << 31)),
-                     dim3(kThreads), 0, S_(stream), src, U16W(dst), C, Cs, Cp,
+                     dim3(kThreads), 0, cg_stream(stream), src, U16W(dst), C, Cs, Cp,
                      total8);
   CG_LAUNCH_CHECK();
 }
@@ -2103,23 +2033,23 @@ extern "C" int cg_rownorm(const void* g, float* norm, int B, long long n,
   if (ws) {
     if ((long long)B * chunks > kReduceWsElems) return CG_EINVAL;
     hipLaunchKernelGGL(sumsq_kernel, dim3(chunks, B), dim3(kThreads), 0,
-                       S_(stream), U16(g), norm, n, ws);
+                       cg_stream(stream), U16(g), norm, n, ws);
     hipLaunchKernelGGL(sqrt_sum_kernel, dim3((B + 255) / 256), dim3(256), 0,
-                       S_(stream), ws, norm, B, chunks);
+                       cg_stream(stream), ws, norm, B, chunks);
     CG_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(zero_f32_kernel, dim3((B + 255) / 256), dim3(256), 0,
-                     S_(stream), norm, B);
+                     cg_stream(stream), norm, B);
   hipLaunchKernelGGL(sumsq_kernel, dim3(chunks, B), dim3(kThreads), 0,
-                     S_(stream), U16(g), norm, n, (float*)nullptr);
+                     cg_stream(stream), U16(g), norm, n, (float*)nullptr);
   hipLaunchKernelGGL(sqrt_kernel, dim3((B + 255) / 256), dim3(256), 0,
-                     S_(stream), norm, B);
+                     cg_stream(stream), norm, B);
   CG_LAUNCH_CHECK();
 }
 
 extern "C" int cg_gp_finalize(float* norm, float* gp, float* coef, int B,
                               float scale, int squared, void* stream) {
-  hipLaunchKernelGGL(gp_finalize_kernel, dim3(1), dim3(kThreads), 0, S_(stream),
+  hipLaunchKernelGGL(gp_finalize_kernel, dim3(1), dim3(kThreads), 0, cg_stream(stream),
                      norm, gp, coef, B, scale, squared);
   CG_LAUNCH_CHECK();
 }
@@ -2129,20 +2059,20 @@ extern "C" int cg_scale_rows(const void* g, const float* coef, void* a0, int B,
   if (n % 8) return CG_EINVAL;
   const long long total8 = (long long)B * n / 8;
   hipLaunchKernelGGL(scale_rows_kernel, dim3(grid1d(total8, kThreads, 1LL << 31)),
-                     dim3(kThreads), 0, S_(stream), U16(g), coef, U16W(a0), n,
+                     dim3(kThreads), 0, cg_stream(stream), U16(g), coef, U16W(a0), n,
                      total8);
   CG_LAUNCH_CHECK();
 }
 
 extern "C" int cg_critic_loss(const float* d_out, const float* gp, float penalty,
                               float* out, int B, void* stream) {
-  hipLaunchKernelGGL(critic_loss_kernel, dim3(1), dim3(kThreads), 0, S_(stream),
+  hipLaunchKernelGGL(critic_loss_kernel, dim3(1), dim3(kThreads), 0, cg_stream(stream),
                      d_out, gp, penalty, out, B);
   CG_LAUNCH_CHECK();
 }
 
 extern "C" int cg_neg_mean(const float* d_out, float* out, int B, void* stream) {
-  hipLaunchKernelGGL(neg_mean_kernel, dim3(1), dim3(kThreads), 0, S_(stream),
+  hipLaunchKernelGGL(neg_mean_kernel, dim3(1), dim3(kThreads), 0, cg_stream(stream),
                      d_out, out, B);
   CG_LAUNCH_CHECK();
 }
@@ -2164,14 +2094,14 @@ extern "C" int cg_colsum(const void* x, float* out, long long rows, int C,
   const int slabs = (Cp + kThreads * 8 - 1) / (kThreads * 8);
   const unsigned blocks = grid1d(rows, rows_per_block, 1LL << 31);
   hipLaunchKernelGGL(colsum_kernel, dim3(blocks, slabs), dim3(kThreads), 0,
-                     S_(stream), U16(x), out, rows, C, Cp, rows_per_block, ws);
+                     cg_stream(stream), U16(x), out, rows, C, Cp, rows_per_block, ws);
   if (ws) {
     FinishArgs f;
     f.ws = ws; f.nparts = (int)blocks; f.ncol = Cp; f.pstride = Cp;
     f.cstride = 0; f.nout = 1; f.scale = 1.f;
     f.out[0] = out; f.out[1] = f.out[2] = nullptr;
     f.cvalid[0] = C; f.cvalid[1] = f.cvalid[2] = 0;
-    launch_finish(f, S_(stream));
+    launch_finish(f, cg_stream(stream));
   }
   CG_LAUNCH_CHECK();
 }
@@ -2183,7 +2113,7 @@ extern "C" int cg_sigmoid_bwd(const void* dfake, const float* fake, void* dz,
   const long long total8 = rows * Cp / 8;
   hipLaunchKernelGGL(sigmoid_bwd_kernel,
                      dim3(grid1d(total8, kThreads, 1LL << 31)), dim3(kThreads),
-                     0, S_(stream), U16(dfake), fake, U16W(dz), C, Cf, Cp,
+                     0, cg_stream(stream), U16(dfake), fake, U16W(dz), C, Cf, Cp,
                      total8);
   CG_LAUNCH_CHECK();
 }
@@ -2193,7 +2123,7 @@ extern "C" int cg_lrelu_bwd(const void* dh, const void* h, void* dpre,
   if (n % 8) return CG_EINVAL;
   const long long total8 = n / 8;
   hipLaunchKernelGGL(lrelu_bwd_kernel, dim3(grid1d(total8, kThreads, 1LL << 31)),
-                     dim3(kThreads), 0, S_(stream), U16(dh), U16(h), U16W(dpre),
+                     dim3(kThreads), 0, cg_stream(stream), U16(dh), U16(h), U16W(dpre),
                      alpha, total8);
   CG_LAUNCH_CHECK();
 }
@@ -2204,7 +2134,7 @@ extern "C" int cg_lrelu_mix(const void* h_a, const void* h_b, const float* mix,
   if (n_per_sample % 8 || B < 1 || !(alpha > 0.f && alpha <= 1.f)) return CG_EINVAL;
   const long long per8 = n_per_sample / 8, total8 = per8 * B;
   hipLaunchKernelGGL(lrelu_mix_kernel, dim3(grid1d(total8, kThreads, 1LL << 31)),
-                     dim3(kThreads), 0, S_(stream), U16(h_a), U16(h_b), mix,
+                     dim3(kThreads), 0, cg_stream(stream), U16(h_a), U16(h_b), mix,
                      U16W(out), per8, total8, alpha, 1.f / alpha);
   CG_LAUNCH_CHECK();
 }
@@ -2215,7 +2145,7 @@ extern "C" int cg_adam(float* p, const float* grad, float* m, float* v,
                        void* stream) {
   if (n < 1) return CG_EINVAL;
   hipLaunchKernelGGL(adam_kernel, dim3(grid1d(n, kThreads, 1LL << 31)),
-                     dim3(kThreads), 0, S_(stream), p, grad, m, v, n, lr_t,
+                     dim3(kThreads), 0, cg_stream(stream), p, grad, m, v, n, lr_t,
                      beta1, beta2, eps, grad_scale, lr_t_dev);
   CG_LAUNCH_CHECK();
 }
@@ -2224,7 +2154,7 @@ extern "C" int cg_grad_finite(const float* grad, long long n, float* ls,
                               void* stream) {
   if (n < 4 || (n & 3)) return CG_EINVAL;
   hipLaunchKernelGGL(grad_finite_kernel, dim3(grid1d(n / 4, kThreads, 2048)),
-                     dim3(kThreads), 0, S_(stream), grad, n / 4, ls);
+                     dim3(kThreads), 0, cg_stream(stream), grad, n / 4, ls);
   CG_LAUNCH_CHECK();
 }
 
@@ -2234,7 +2164,7 @@ extern "C" int cg_adam_scaled(float* p, const float* grad, float* m, float* v,
                               void* stream) {
   if (n < 1 || !ls) return CG_EINVAL;
   hipLaunchKernelGGL(adam_ls_kernel, dim3(grid1d(n, kThreads, 1LL << 31)),
-                     dim3(kThreads), 0, S_(stream), p, grad, m, v, n, lr, beta1,
+                     dim3(kThreads), 0, cg_stream(stream), p, grad, m, v, n, lr, beta1,
                      beta2, eps, grad_scale, ls);
   CG_LAUNCH_CHECK();
 }
@@ -2242,7 +2172,7 @@ extern "C" int cg_adam_scaled(float* p, const float* grad, float* m, float* v,
 extern "C" int cg_loss_scale_update(float* ls, int growth_interval,
                                     void* stream) {
   if (!ls || growth_interval < 1) return CG_EINVAL;
-  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, S_(stream),
+  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, cg_stream(stream),
                      ls, (float)growth_interval);
   CG_LAUNCH_CHECK();
 }
@@ -2267,7 +2197,7 @@ extern "C" int cg_signal_metrics(const float* real, const float* fake,
   }
   const unsigned blocks = grid1d(rows, 4 * rpw * rows_per_slot, 1LL << 31);
   hipLaunchKernelGGL(signal_metrics_kernel, dim3(blocks), dim3(kThreads), 0,
-                     S_(stream), real, fake, out, rows, C, Cr, Cf, smin,
+                     cg_stream(stream), real, fake, out, rows, C, Cr, Cf, smin,
                      smax - smin, lpr, l2, rows_per_slot, ws);
   if (ws) {
     FinishArgs f;
@@ -2275,7 +2205,7 @@ extern "C" int cg_signal_metrics(const float* real, const float* fake,
     f.cstride = 0; f.nout = 1; f.scale = 1.f / (float)rows;  // the means
     f.out[0] = out; f.out[1] = f.out[2] = nullptr;
     f.cvalid[0] = 4; f.cvalid[1] = f.cvalid[2] = 0;
-    launch_finish(f, S_(stream));
+    launch_finish(f, cg_stream(stream));
   }
   CG_LAUNCH_CHECK();
 }
@@ -2284,7 +2214,7 @@ extern "C" int cg_step_outputs(const float* gen_loss, const float* loss,
                                const float* gp, const float* metrics, int n,
                                float* out, void* stream) {
   if (!gen_loss || !loss || !gp || !metrics || !out || n < 0) return CG_EINVAL;
-  hipLaunchKernelGGL(step_outputs_kernel, dim3(1), dim3(64), 0, S_(stream),
+  hipLaunchKernelGGL(step_outputs_kernel, dim3(1), dim3(64), 0, cg_stream(stream),
                      gen_loss, loss, gp, metrics, n, out);
   CG_LAUNCH_CHECK();
 }

@@ -16,8 +16,6 @@
 
 namespace {
 
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kOasisThreads = 64;  // one wave per workgroup: 204 waves spread over the CUs
 // bytes of one stack entry: v, w (f64) and l (i32), struct of arrays
 constexpr long long kPoolBytes = 2 * sizeof(double) + sizeof(int);
@@ -178,24 +176,6 @@ __global__ __launch_bounds__(kStatsThreads) void spike_corrcoef_kernel(
 constexpr int kErrThreads = 256;
 constexpr int kErrMaxParts = 1024;
 
-__device__ __forceinline__ void block_sum4(float (&v)[4], float (*sm)[4]) {
-  // waves in order 0..3 after a wave sum of fixed pairing
-#pragma unroll
-  for (int q = 0; q < 4; ++q) v[q] = wave_sum(v[q]);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sm[wave][q] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    float t = sm[0][q];
-    for (int k = 1; k < kErrThreads / 64; ++k) t += sm[k][q];
-    v[q] = t;
-  }
-}
-
 __global__ __launch_bounds__(kErrThreads) void stats_error_kernel(
     const float* __restrict__ fr_a, const float* __restrict__ fr_b, long long n_fr,
     const float* __restrict__ cov_a, const float* __restrict__ cov_b,
@@ -214,8 +194,11 @@ __global__ __launch_bounds__(kErrThreads) void stats_error_kernel(
     v[2] += fabsf(d);
     v[3] += d * d;
   }
-  block_sum4(v, sm);
-  if (threadIdx.x < 4) ws[(long long)blockIdx.x * 4 + threadIdx.x] = v[threadIdx.x];
+  block_fold_put<4>(v, sm[threadIdx.x >> 6], 1);
+  __syncthreads();
+  if (threadIdx.x < 4)
+    ws[(long long)blockIdx.x * 4 + threadIdx.x] =
+        block_fold_get<kErrThreads / 64>(&sm[0][threadIdx.x], 4);
 }
 
 __global__ __launch_bounds__(64) void stats_error_finish_kernel(
@@ -285,7 +268,7 @@ extern "C" int cg_oasis_ar1_batched(
     const long long n = traces - t0 < group ? traces - t0 : group;
     hipLaunchKernelGGL(oasis_ar1_kernel,
                        dim3((unsigned)((n + kOasisThreads - 1) / kOasisThreads)),
-                       dim3(kOasisThreads), 0, S_(stream), a);
+                       dim3(kOasisThreads), 0, cg_stream(stream), a);
   }
   CG_LAUNCH_CHECK();
 }
@@ -304,7 +287,7 @@ extern "C" int cg_spike_stats(const float* spikes, int B, int T, int C,
   if (split > 8) split = 8;
   const float duration = (float)((double)T / 24.0);
   hipLaunchKernelGGL(spike_stats_kernel, dim3(B, split), dim3(kStatsThreads),
-                     (size_t)lds, S_(stream), spikes, s_b, s_t, s_c, T, C, nb,
+                     (size_t)lds, cg_stream(stream), spikes, s_b, s_t, s_c, T, C, nb,
                      duration, rates, cov);
   CG_LAUNCH_CHECK();
 }
@@ -322,7 +305,7 @@ extern "C" int cg_spike_corrcoef(const float* spikes, int B, int T, int C,
   if (split < 1) split = 1;
   if (split > 8) split = 8;
   hipLaunchKernelGGL(spike_corrcoef_kernel, dim3(B, split), dim3(kStatsThreads),
-                     (size_t)lds, S_(stream), spikes, s_b, s_t, s_c, C, nb, corr);
+                     (size_t)lds, cg_stream(stream), spikes, s_b, s_t, s_c, C, nb, corr);
   CG_LAUNCH_CHECK();
 }
 
@@ -341,8 +324,8 @@ extern "C" int cg_spike_stats_error(const float* fr_a, const float* fr_b,
     return CG_EINVAL;
   const int parts = err_parts(n_fr > n_cov ? n_fr : n_cov);
   hipLaunchKernelGGL(stats_error_kernel, dim3(parts), dim3(kErrThreads), 0,
-                     S_(stream), fr_a, fr_b, n_fr, cov_a, cov_b, n_cov, ws);
-  hipLaunchKernelGGL(stats_error_finish_kernel, dim3(1), dim3(64), 0, S_(stream),
+                     cg_stream(stream), fr_a, fr_b, n_fr, cov_a, cov_b, n_cov, ws);
+  hipLaunchKernelGGL(stats_error_finish_kernel, dim3(1), dim3(64), 0, cg_stream(stream),
                      ws, parts, out);
   CG_LAUNCH_CHECK();
 }

@@ -49,8 +49,6 @@
 
 namespace {
 
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kTsThreads = 256;
 constexpr int kTsWaves = kTsThreads / 64;
 constexpr int kTsChunk = 4096;       // elements of one tile
@@ -76,59 +74,27 @@ inline TsLayout ts_layout(int nseg, long long total_len, int k) {
   return l;
 }
 
-__device__ __forceinline__ double ts_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double ts_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// (a + b == b + a: after every step both partners hold the same bits)
-__device__ __forceinline__ double ts_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
-// minimum, maximum and the two sums over the workgroup, in every thread; the
-// waves' slots are folded in index order.  sm: [4][kTsWaves]
+// minimum, maximum and the two sums over the workgroup, in every thread.
+// sm: [4][kTsWaves]
 __device__ __forceinline__ void ts_block_fold(double& mn, double& mx, double& sum,
                                               double& nf, double (*sm)[kTsWaves]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  mn = ts_wave_min(mn);
-  mx = ts_wave_max(mx);
-  sum = ts_wave_sum(sum);
-  nf = ts_wave_sum(nf);
-  if (lane == 0) {
-    sm[0][wave] = mn;
-    sm[1][wave] = mx;
-    sm[2][wave] = sum;
-    sm[3][wave] = nf;
-  }
+  block_fold_put<FoldMin>(mn, sm[0]);
+  block_fold_put<FoldMax>(mx, sm[1]);
+  double v[2] = {sum, nf};
+  block_fold_put<2>(v, &sm[2][threadIdx.x >> 6], kTsWaves);
   __syncthreads();
-  mn = sm[0][0], mx = sm[1][0], sum = sm[2][0], nf = sm[3][0];
-#pragma unroll
-  for (int w = 1; w < kTsWaves; ++w) {
-    mn = fmin(mn, sm[0][w]);
-    mx = fmax(mx, sm[1][w]);
-    sum = sum + sm[2][w];
-    nf = nf + sm[3][w];
-  }
+  mn = block_fold_get<kTsWaves, FoldMin>(sm[0]);
+  mx = block_fold_get<kTsWaves, FoldMax>(sm[1]);
+  sum = block_fold_get<kTsWaves>(sm[2]);
+  nf = block_fold_get<kTsWaves>(sm[3]);
   __syncthreads();  // the slots are free again
 }
 
 __device__ __forceinline__ double ts_block_sum(double v, double* sm /*[kTsWaves]*/) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = ts_wave_sum(v);
-  if (lane == 0) sm[wave] = v;
+  block_fold_put(v, sm);
   __syncthreads();
-  v = sm[0];
-#pragma unroll
-  for (int w = 1; w < kTsWaves; ++w) v = v + sm[w];
-  __syncthreads();
+  v = block_fold_get<kTsWaves>(sm);
+  __syncthreads();  // the slots are free again
   return v;
 }
 
@@ -412,15 +378,15 @@ extern "C" int cg_tensor_summary(const float* data, const long long* seg_off,
   const int k = num_buckets;
   const dim3 tiles((unsigned)(l.tiles < kTsMaxGrid ? l.tiles : kTsMaxGrid));
   const dim3 segs((unsigned)(nseg < 1024 ? nseg : 1024));
-  hipLaunchKernelGGL(ts_plan_kernel, dim3(1), dim3(kTsPlanThreads), 0, S_(stream),
+  hipLaunchKernelGGL(ts_plan_kernel, dim3(1), dim3(kTsPlanThreads), 0, cg_stream(stream),
                      seg_len, nseg, l.tiles, tile_start);
-  hipLaunchKernelGGL(ts_pass1_kernel, tiles, dim3(kTsThreads), 0, S_(stream), data,
+  hipLaunchKernelGGL(ts_pass1_kernel, tiles, dim3(kTsThreads), 0, cg_stream(stream), data,
                      seg_off, seg_len, nseg, tile_start, part1);
-  hipLaunchKernelGGL(ts_finish1_kernel, segs, dim3(kTsThreads), 0, S_(stream),
+  hipLaunchKernelGGL(ts_finish1_kernel, segs, dim3(kTsThreads), 0, cg_stream(stream),
                      seg_len, nseg, k, tile_start, part1, counts, stats);
-  hipLaunchKernelGGL(ts_pass2_kernel, tiles, dim3(kTsThreads), 0, S_(stream), data,
+  hipLaunchKernelGGL(ts_pass2_kernel, tiles, dim3(kTsThreads), 0, cg_stream(stream), data,
                      seg_off, seg_len, nseg, k, tile_start, stats, part2, counts);
-  hipLaunchKernelGGL(ts_finish2_kernel, segs, dim3(kTsThreads), 0, S_(stream), nseg,
-                     k, tile_start, part2, counts, stats, buckets);
+  hipLaunchKernelGGL(ts_finish2_kernel, segs, dim3(kTsThreads), 0, cg_stream(stream),
+                     nseg, k, tile_start, part2, counts, stats, buckets);
   CG_LAUNCH_CHECK();
 }

@@ -23,8 +23,6 @@
 
 namespace {
 
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
 constexpr int kVrThreads = 512;
@@ -225,7 +223,7 @@ extern "C" int cg_van_rossum(const float* spikes, int B, int T, int C,
     return CG_EINVAL;
   const int NB = (C + kVrBlock - 1) / kVrBlock;
   hipLaunchKernelGGL(van_rossum_kernel, dim3(B, NB * (NB + 1) / 2),
-                     dim3(kVrThreads), 0, S_(stream), spikes, s_b, s_t, s_c, T, C,
+                     dim3(kVrThreads), 0, cg_stream(stream), spikes, s_b, s_t, s_c, T, C,
                      decay, gram, dist);
   CG_LAUNCH_CHECK();
 }

@@ -40,8 +40,6 @@
 
 namespace {
 
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kVpThreads = 256;
 constexpr int kVpRows = kVpThreads / 16;  // pairs in flight per workgroup
 // workgroups of the pair kernel at most: two per CU of an MI355X (8 waves a CU);
@@ -242,11 +240,11 @@ extern "C" int cg_victor_purpura(const float* spikes, int B, int T, int C,
   const long long trains = (long long)B * C;
   const int waves = kVpThreads / 64;
   hipLaunchKernelGGL(vp_compact_kernel, dim3((unsigned)((trains + waves - 1) / waves)),
-                     dim3(kVpThreads), 0, S_(stream), spikes, s_b, s_t, s_c, B, T, C,
-                     frames, counts, dist);
+                     dim3(kVpThreads), 0, cg_stream(stream), spikes, s_b, s_t, s_c, B, T,
+                     C, frames, counts, dist);
   if (L.pairs > 0)
     hipLaunchKernelGGL(vp_pairs_kernel, dim3((unsigned)L.groups), dim3(kVpThreads), 0,
-                       S_(stream), frames, counts, bnd, L.bnd_pitch, T, C,
+                       cg_stream(stream), frames, counts, bnd, L.bnd_pitch, T, C,
                        (long long)C * (C - 1) / 2, L.pairs, qf, dist);
   CG_LAUNCH_CHECK();
 }

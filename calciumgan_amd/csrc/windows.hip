@@ -37,8 +37,6 @@
 
 namespace {
 
-inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kWinThreads = 256;       // plain
 constexpr int kWinItemElems = 4 * kWinThreads;
 constexpr int kWinMaxGrid = 2048;      // workgroups; beyond: grid-stride
@@ -282,7 +280,7 @@ extern "C" int cg_window_batch(const float* raw, long long T_raw, int C,
     const unsigned grid =
         (unsigned)(a.items < kWinMaxGrid ? a.items : kWinMaxGrid);
     hipLaunchKernelGGL(window_gather_kernel, dim3(grid), dim3(kWinThreads), 0,
-                       S_(stream), a);
+                       cg_stream(stream), a);
     CG_LAUNCH_CHECK();
   }
   const int G = ifft_group(L);
@@ -302,6 +300,6 @@ extern "C" int cg_window_batch(const float* raw, long long T_raw, int C,
   const unsigned grid =
       (unsigned)(a.items < kWinFftMaxGrid ? a.items : kWinFftMaxGrid);
   hipLaunchKernelGGL(window_fft_kernel, dim3(grid), dim3(kWinFftThreads),
-                     win_fft_lds_bytes(L), S_(stream), a);
+                     win_fft_lds_bytes(L), cg_stream(stream), a);
   CG_LAUNCH_CHECK();
 }
