@@ -29,6 +29,7 @@
 
 #include "cg_common.h"
 #include "swconv_args.h"
+#include "swconv_epilogue.h"
 
 namespace {
 
@@ -518,15 +519,7 @@ swconv_kernel(ConvArgs a) {
               *reinterpret_cast<const f32x4*>(scr + row * kScrPitch + colB);
           float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
           float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const int n = (e < 4 ? nA : nB - 4) + e;
-            // statistics of the STORED (bf16) pre-activation, as the separate
-            // cg_ln_lrelu_fwd pass sees it
-            v[e] = n < a.N ? act2f(f2act(v[e] + bv[e])) : 0.f;
-            s1 += v[e];
-            s2 += v[e] * v[e];
-          }
+          ln_row_stats8(v, bv, nA, a.N, s1, s2);  // (nB == nA + 4: no f32 output)
 #pragma unroll
           for (int o = 1; o < 8; o <<= 1) {
             s1 += __shfl_xor(s1, o, 64);
@@ -538,10 +531,8 @@ swconv_kernel(ConvArgs a) {
           __syncthreads();
           const float2 o2 = *reinterpret_cast<const float2*>(
               part + ((wave ^ 1) * 16 + row) * 2);
-          const float invn = 1.f / (float)a.N;
-          const float mean = (s1 + o2.x) * invn;
-          const float var = fmaxf((s2 + o2.y) * invn - mean * mean, 0.f);
-          const float rstd = rsqrtf(var + a.ln_eps);
+          float mean, rstd;
+          ln_row_moments(s1 + o2.x, s2 + o2.y, 1.f / (float)a.N, a.ln_eps, mean, rstd);
           if (m < a.M && nA < a.Cy) {
             const int b = m / a.Lu;
             const int u = m - b * a.Lu;
@@ -554,25 +545,13 @@ swconv_kernel(ConvArgs a) {
             const f32x4 b0 = *reinterpret_cast<const f32x4*>(lnp + 128 + lc);
             const f32x4 b1 = *reinterpret_cast<const f32x4*>(lnp + 128 + lc + 4);
             float hv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const int n = (e < 4 ? nA : nB - 4) + e;  // (as in the statistics)
-              const float t = (v[e] - mean) * rstd * (e < 4 ? g0[e] : g1[e - 4]) +
-                              (e < 4 ? b0[e] : b1[e - 4]);
-              // (channel padding stays +0 whatever the row holds: with NaN / inf
-              // statistics the zero gamma / beta of a padding column give NaN)
-              hv[e] = n < a.N ? fmaxf(t, a.alpha * t) : 0.f;
-            }
+            ln_row_act8(v, hv, mean, rstd, g0, g1, b0, b1, nA, a.N, a.alpha);
             // (forward-only callers -- G(z) of a critic update -- pass no
             // statistics buffers: the pre-activation is then not stored either)
             if (a.ln_mean)
               *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(a.y) + rowoff +
-                                        nA) =
-                  make_uint4(pack2act(v[0], v[1]), pack2act(v[2], v[3]),
-                             pack2act(v[4], v[5]), pack2act(v[6], v[7]));
-            *reinterpret_cast<uint4*>(a.ln_h + rowoff + nA) =
-                make_uint4(pack2act(hv[0], hv[1]), pack2act(hv[2], hv[3]),
-                           pack2act(hv[4], hv[5]), pack2act(hv[6], hv[7]));
+                                        nA) = epi_pack8(v);
+            *reinterpret_cast<uint4*>(a.ln_h + rowoff + nA) = epi_pack8(hv);
             if (a.ln_mean && wn == 0 && cg8 == 0) {
               a.ln_mean[ridx] = mean;
               a.ln_rstd[ridx] = rstd;
@@ -585,16 +564,8 @@ swconv_kernel(ConvArgs a) {
         const int u = m - b * a.Lu;
         int t = a.y_stride * u + y_off;
         bool to_side = false;  // reflected-branch row of the unshuffle
-        if (a.out_shifts) {
-          const int s = a.out_shifts[b / a.out_seg];
-          if (s > 0) {
-            to_side = t >= a.Ly - s;
-            t = to_side ? t - (a.Ly - s) : t + s;
-          } else {
-            to_side = t < -s;
-            t = to_side ? t : t + s;
-          }
-        }
+        if (a.out_shifts)
+          t = out_shift_row(t, a.out_shifts[b / a.out_seg], a.Ly, to_side);
         const long long rowoff =
             ((long long)b * (to_side ? a.side_rows : a.Ly) + t) * a.Cy;
         const f32x4 v0 =
@@ -605,38 +576,14 @@ swconv_kernel(ConvArgs a) {
         const bool okB = nB < a.Cy;  // f32 out: second half past the pitch
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += bv[e];
-        if (a.epilogue == CG_EPI_LRELU) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], a.alpha * v[e]);
-        } else if (a.epilogue == CG_EPI_MASK && !to_side) {
-          if (a.out_shifts) {
-            // the unfused form stores this gradient in bf16 before masking
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = act2f(f2act(v[e]));
-          }
+        epi_apply8(v, a.epilogue, a.alpha, to_side, a.out_shifts, [&] {
           const uint2 ha = *reinterpret_cast<const uint2*>(a.mask + rowoff + nA);
           const uint2 hb = okB ? *reinterpret_cast<const uint2*>(a.mask + rowoff + nB)
                                : make_uint2(0u, 0u);
-          const uint32_t hw[4] = {ha.x, ha.y, hb.x, hb.y};
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const uint16_t hv = (uint16_t)(hw[e >> 1] >> ((e & 1) * 16));
-            v[e] *= (act2f(hv) > 0.f) ? 1.f : a.alpha;
-          }
-        } else if (a.epilogue == CG_EPI_SIGMOID) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = 1.f / (1.f + __expf(-v[e]));
-        }
-        // channel padding [N, Cy) stays exactly zero
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (nA + e >= a.N) v[e] = 0.f;
-          if (nB + e >= a.N) v[4 + e] = 0.f;
-        }
-        if (a.rowsumsq) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) ssq += v[e] * v[e];
-        }
+          return make_uint4(ha.x, ha.y, hb.x, hb.y);
+        });
+        epi_zero_pad8(v, nA, nB, a.N);
+        if (a.rowsumsq) epi_add_squares8(v, ssq);
         if (a.out_f32) {
           float* dst = reinterpret_cast<float*>(a.y) + rowoff;
           *reinterpret_cast<f32x4*>(dst + nA) = f32x4{v[0], v[1], v[2], v[3]};
@@ -645,9 +592,7 @@ swconv_kernel(ConvArgs a) {
         } else {
           uint16_t* dst =
               (to_side ? a.side : reinterpret_cast<uint16_t*>(a.y)) + rowoff + nA;
-          *reinterpret_cast<uint4*>(dst) =
-              make_uint4(pack2act(v[0], v[1]), pack2act(v[2], v[3]),
-                         pack2act(v[4], v[5]), pack2act(v[6], v[7]));
+          *reinterpret_cast<uint4*>(dst) = epi_pack8(v);
         }
       }
     }
@@ -656,10 +601,6 @@ swconv_kernel(ConvArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
   if (a.rowsumsq) {
-    // the whole tile belongs to one sample (nseg == 1, checked on the host):
-    // one f32 atomic per WORKGROUP -- the atomics of a sample all hit one
-    // address and serialise in the L2 (measured 24 us of an 88 us launch with
-    // one per wave)
     ssq = wave_sum(ssq);
     float* wsum = reinterpret_cast<float*>(smem) + kScratchBytes / 4;
     if (lane == 0) wsum[wave] = ssq;
@@ -667,12 +608,9 @@ swconv_kernel(ConvArgs a) {
     if (tid == 0 && m0 < a.M) {
       const float t = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
       const int b = m0 / a.Lu;
-      if (a.ssq_ws) {
-        const int rt = (m0 - b * a.Lu) / TM;
-        a.ssq_ws[(long long)b * a.ssq_P + (rt * a.gp + phase) * a.gn + bn] = t;
-      } else {
-        atomicAdd(a.rowsumsq + b, t);
-      }
+      const int rt = (m0 - b * a.Lu) / TM;
+      ssq_commit(t, a.ssq_ws, (long long)b * a.ssq_P + (rt * a.gp + phase) * a.gn + bn,
+                 a.rowsumsq, b);
     }
   }
 }
@@ -718,24 +656,11 @@ __global__ __launch_bounds__(256) void split_finish_kernel(SplitFinishArgs f) {
 #pragma unroll
   for (int e = 0; e < 8; ++e)
     if (f.bias && c + e < f.N) v[e] += f.bias[c + e];
-  if (f.epilogue == CG_EPI_LRELU) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], f.alpha * v[e]);
-  } else if (f.epilogue == CG_EPI_MASK) {
-    const uint4 h = *reinterpret_cast<const uint4*>(f.mask + e0);
-    const uint32_t hw[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const uint16_t hv = (uint16_t)(hw[e >> 1] >> ((e & 1) * 16));
-      v[e] *= (act2f(hv) > 0.f) ? 1.f : f.alpha;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e)
-    if (c + e >= f.N) v[e] = 0.f;
-  *reinterpret_cast<uint4*>(f.y + e0) =
-      make_uint4(pack2act(v[0], v[1]), pack2act(v[2], v[3]), pack2act(v[4], v[5]),
-                 pack2act(v[6], v[7]));
+  // (no sigmoid, no output shift: the host refuses both with split-K)
+  epi_apply8<false>(v, f.epilogue, f.alpha, false, nullptr,
+                    [&] { return *reinterpret_cast<const uint4*>(f.mask + e0); });
+  epi_zero_pad8(v, c, f.N);
+  *reinterpret_cast<uint4*>(f.y + e0) = epi_pack8(v);
 }
 
 // ---------------------------------------------------------------------------

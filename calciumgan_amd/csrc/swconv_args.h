@@ -1,6 +1,6 @@
 // Kernel-side argument block of the cg_swconv launches (filled on the host by
 // swconv_run in swconv.hip from a cg_conv_desc; shared by the tile kernels of
-// swconv.hip and the ping-pong kernels of swconv_pp.hip).
+// swconv.hip and the software-pipelined kernels of swconv_swp.hip).
 #pragma once
 #include "cg_common.h"
 

@@ -42,6 +42,7 @@
 #include <cstdlib>
 
 #include "swconv_args.h"
+#include "swconv_epilogue.h"
 
 namespace {
 
@@ -803,16 +804,7 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
         pair8(mt, 1, v[1]);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const int n = nl0 + p * 32 + e;
-            // statistics of the STORED pre-activation, as the separate
-            // cg_ln_lrelu_fwd pass sees it
-            v[p][e] = n < a.N ? act2f(f2act(v[p][e] + bv[p][e])) : 0.f;
-            s1 += v[p][e];
-            s2 += v[p][e] * v[p][e];
-          }
+        for (int p = 0; p < 2; ++p) ln_row_stats8(v[p], bv[p], nl0 + p * 32, a.N, s1, s2);
         s1 += __shfl_xor(s1, 16, 64);
         s2 += __shfl_xor(s2, 16, 64);
         s1 += __shfl_xor(s1, 32, 64);
@@ -823,9 +815,8 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
         __syncthreads();
         const float2 o2 =
             *reinterpret_cast<const float2*>(pt + ((wave ^ 1) * 16 + rM) * 2);
-        const float mean = (s1 + o2.x) * invn;
-        const float var = fmaxf((s2 + o2.y) * invn - mean * mean, 0.f);
-        const float rstd = rsqrtf(var + a.ln_eps);
+        float mean, rstd;
+        ln_row_moments(s1 + o2.x, s2 + o2.y, invn, a.ln_eps, mean, rstd);
         const int m = mw0 + mt * 16 + rM;
         if (m < a.M) {
           const int b = m / a.Lu;
@@ -843,25 +834,13 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
               const f32x4 b0v = *reinterpret_cast<const f32x4*>(lnp + 128 + lc);
               const f32x4 b1v = *reinterpret_cast<const f32x4*>(lnp + 128 + lc + 4);
               float hv[8];
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                const float t =
-                    (v[p][e] - mean) * rstd * (e < 4 ? g0[e] : g1[e - 4]) +
-                    (e < 4 ? b0v[e] : b1v[e - 4]);
-                // (channel padding stays +0 whatever the row holds: with NaN / inf
-                // statistics the zero gamma / beta of a padding column give NaN)
-                hv[e] = n + e < a.N ? fmaxf(t, a.alpha * t) : 0.f;
-              }
+              ln_row_act8(v[p], hv, mean, rstd, g0, g1, b0v, b1v, n, a.N, a.alpha);
               // (forward-only callers pass no statistics buffers: the
               // pre-activation is then not stored either)
               if (a.ln_mean)
                 *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(a.y) +
-                                          rowoff + n) =
-                    make_uint4(pack2act(v[p][0], v[p][1]), pack2act(v[p][2], v[p][3]),
-                               pack2act(v[p][4], v[p][5]), pack2act(v[p][6], v[p][7]));
-              *reinterpret_cast<uint4*>(a.ln_h + rowoff + n) =
-                  make_uint4(pack2act(hv[0], hv[1]), pack2act(hv[2], hv[3]),
-                             pack2act(hv[4], hv[5]), pack2act(hv[6], hv[7]));
+                                          rowoff + n) = epi_pack8(v[p]);
+              *reinterpret_cast<uint4*>(a.ln_h + rowoff + n) = epi_pack8(hv);
             }
           }
           if (a.ln_mean && wn == 0 && g == 0) {
@@ -886,15 +865,7 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
         const int u = uw0 + r;
         int t = a.y_stride * u + ey_off;
         to_side = false;
-        if (a.out_shifts) {
-          if (oshift > 0) {
-            to_side = t >= a.Ly - oshift;
-            t = to_side ? t - (a.Ly - oshift) : t + oshift;
-          } else {
-            to_side = t < -oshift;
-            t = to_side ? t : t + oshift;
-          }
-        }
+        if (a.out_shifts) t = out_shift_row(t, oshift, a.Ly, to_side);
         return ((long long)bw * (to_side ? a.side_rows : a.Ly) + t) * a.Cy;
       };
       // the LeakyReLU' mask words of every subtile are fetched up front (one
@@ -930,33 +901,16 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
           if (row_ok && n < a.Cy) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = (v[e] + bv[p][e]) * rs;
-            if (a.epilogue == CG_EPI_LRELU) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], a.alpha * v[e]);
-            } else if (a.epilogue == CG_EPI_MASK && !to_side) {
-              if (a.out_shifts) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = act2f(f2act(v[e]));
-              }
-              const uint4 h4 = mk[mt][p];
-              const uint32_t hw[4] = {h4.x, h4.y, h4.z, h4.w};
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                const uint16_t hv = (uint16_t)(hw[e >> 1] >> ((e & 1) * 16));
-                v[e] *= (act2f(hv) > 0.f) ? 1.f : a.alpha;
-              }
-            } else if (a.epilogue == CG_EPI_SIGMOID) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = 1.f / (1.f + __expf(-v[e]));
-            }
+            epi_apply8(v, a.epilogue, a.alpha, to_side, a.out_shifts,
+                       [&] { return mk[mt][p]; });
             // (columns past N are stored as zeros; only the last column tile of
             // an N that is no multiple of the tile has any: a scalar branch
             // instead of 16 compares and selects per store)
-            if (en0 + TN > a.N) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e)
-                if (n + e >= a.N) v[e] = 0.f;
-            }
+            if (en0 + TN > a.N) epi_zero_pad8(v, n, a.N);
+            // (epi_add_squares8, written out: through the helper hipcc contracts
+            // v0 v0 + v1 v1 of a wave's first eight values the other way round --
+            // fma(v1, v1, v0 v0) for fma(v0, v0, v1 v1) -- and the last bit of
+            // rowsumsq moves: tests/golden/reduce_bits.npz, rowsumsq/t13)
             if (a.rowsumsq) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) ssq += v[e] * v[e];
@@ -969,26 +923,18 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
             } else {
               uint16_t* dst =
                   (to_side ? a.side : reinterpret_cast<uint16_t*>(a.y)) + rowoff + n;
-              *reinterpret_cast<uint4*>(dst) =
-                  make_uint4(pack2act(v[0], v[1]), pack2act(v[2], v[3]),
-                             pack2act(v[4], v[5]), pack2act(v[6], v[7]));
+              *reinterpret_cast<uint4*>(dst) = epi_pack8(v);
             }
           }
         }
       }
       if (a.rowsumsq) {
-        // the whole tile belongs to one sample (nseg == 1, checked on the host):
-        // one f32 atomic per workgroup
         ssq = wave_sum(ssq);
         if (lane == 0) wsum[wave] = ssq;
         __syncthreads();
         if (tid == 0 && em0 < a.M) {
-          float t = 0.f;
-          for (int w = 0; w < NW; ++w) t += wsum[w];
-          // (ordered form: the workgroup's own slot, summed by the finishing
-          // launch; else one f32 atomic per workgroup)
-          if (a.ssq_ws) a.ssq_ws[(long long)eb0 * a.ssq_P + ess] = t;
-          else atomicAdd(a.rowsumsq + eb0, t);
+          ssq_commit(block_fold_get<NW>(wsum), a.ssq_ws, (long long)eb0 * a.ssq_P + ess,
+                     a.rowsumsq, eb0);
         }
       }
     }
@@ -1055,26 +1001,13 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
     // the wave stores, before rounding -- the x^ input gradient's launch)
     float ssq = 0.f;
     auto finish8 = [&](float (&v)[8], int n) {
-      if (zero_tail) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (n + e >= a.N) v[e] = 0.f;
-      }
-      if constexpr (EPI == kEpiLreluSsq) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) ssq += v[e] * v[e];
-      }
-      return u32x4{pack2act(v[0], v[1]), pack2act(v[2], v[3]), pack2act(v[4], v[5]),
-                   pack2act(v[6], v[7])};
+      if (zero_tail) epi_zero_pad8(v, n, a.N);
+      if constexpr (EPI == kEpiLreluSsq) epi_add_squares8(v, ssq);
+      const uint4 q = epi_pack8(v);
+      return u32x4{q.x, q.y, q.z, q.w};
     };
     auto masked8 = [&](float (&v)[8], const u32x4 h4, bool round_first) {
-      const uint32_t hw[4] = {h4.x, h4.y, h4.z, h4.w};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if (round_first) v[e] = act2f(f2act(v[e]));
-        const uint16_t hv = (uint16_t)(hw[e >> 1] >> ((e & 1) * 16));
-        v[e] *= (act2f(hv) > 0.f) ? 1.f : a.alpha;
-      }
+      epi_mask8(v, h4.x, h4.y, h4.z, h4.w, a.alpha, round_first);
     };
     // Subtile mt of a lane: + mt * mt_step bytes, added on the VECTOR side.  (As
     // the scalar offset of the store it corrupted data: with a register in the
@@ -1117,8 +1050,7 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += bv[p][e];
           if constexpr (EPI != kEpiMask) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], a.alpha * v[e]);
+            epi_lrelu8(v, a.alpha);
           } else {
             if (a.row_scale) {
 #pragma unroll
@@ -1129,17 +1061,13 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
           store_rows(finish8(v, nl0 + p * 32), ry, vo[p], mt);
         }
       if constexpr (EPI == kEpiLreluSsq) {
-        // the whole tile belongs to one sample (nseg == 1, checked on the host;
-        // every wave of the workgroup is here): the workgroup's own slot of the
-        // ordered sum, or one f32 atomic
+        // (every wave of the workgroup is here)
         ssq = wave_sum(ssq);
         if (lane == 0) wsum[wave] = ssq;
         __syncthreads();
         if (tid == 0) {
-          float t = 0.f;
-          for (int w = 0; w < NW; ++w) t += wsum[w];
-          if (a.ssq_ws) a.ssq_ws[(long long)bw * a.ssq_P + to_sgpr(ess)] = t;
-          else atomicAdd(a.rowsumsq + bw, t);
+          ssq_commit(block_fold_get<NW>(wsum), a.ssq_ws,
+                     (long long)bw * a.ssq_P + to_sgpr(ess), a.rowsumsq, bw);
         }
       }
     } else {
@@ -1148,7 +1076,8 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
       // (cg_unshuffle_fixup adds them in)
       int oshift = a.out_shifts[bw / a.out_seg];
       const int tlast = t0 + a.y_stride * (16 * MT - 1);
-      const bool any_side = oshift > 0 ? tlast >= a.Ly - oshift : t0 < -oshift;
+      const bool any_side = oshift > 0 ? out_shift_reflected(tlast, oshift, a.Ly)
+                                       : out_shift_reflected(t0, oshift, a.Ly);
       if (!any_side) {
         const long long base = (((long long)bw * a.Ly + t0 + oshift) * a.Cy) * 2;
         const __amdgpu_buffer_rsrc_t ry = rsrc_at(a.y, base);
@@ -1205,8 +1134,8 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
           const int t = t0 + 2 * i;
           const int ip = kmir - i;
           const int tp = t0 + 2 * ip;
-          const bool to_side = oshift > 0 ? t >= a.Ly - oshift : t < -oshift;
-          const bool p_side = oshift > 0 ? tp >= a.Ly - oshift : tp < -oshift;
+          const bool to_side = out_shift_reflected(t, oshift, a.Ly);
+          const bool p_side = out_shift_reflected(tp, oshift, a.Ly);
           direct[mt] = !to_side;
           fold[mt] = !to_side && ip >= 0 && ip < 16 * MT && p_side;
           phi[mt] = (ip & 16) != 0;
@@ -1302,15 +1231,9 @@ __device__ __forceinline__ void swconv_swp_body(const SwpArgs& pa) {
         u32x4 mk[MT][2];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          int t = t0 + a.y_stride * (mt * 16 + rM);
           bool to_side;
-          if (oshift > 0) {
-            to_side = t >= a.Ly - oshift;
-            t = to_side ? t - (a.Ly - oshift) : t + oshift;
-          } else {
-            to_side = t < -oshift;
-            t = to_side ? t : t + oshift;
-          }
+          const int t =
+              out_shift_row(t0 + a.y_stride * (mt * 16 + rM), oshift, a.Ly, to_side);
 #pragma unroll
           for (int p = 0; p < 2; ++p) {
             const bool ok = !(cols_open && nl0 + p * 32 >= a.Cy);

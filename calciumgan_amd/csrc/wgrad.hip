@@ -39,10 +39,22 @@ __device__ unsigned g_wgrad_trace[256 * 8 * kWTraceParts];
 #define CG_WTR(acc, t, part) do { unsigned long long n_; \
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(n_)::"memory"); \
     (acc)[part] += (unsigned)n_ - (t); (t) = (unsigned)n_; } while (0)
+// set-up and write-out of the batched kernels (multi and flex): a wave's parts
+// from its first stamp on; the first 256 workgroups are recorded
+#define CG_WTR_BEGIN unsigned wtr[kWTraceParts] = {}; unsigned wtt; \
+  do { unsigned long long n_; \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(n_)::"memory"); \
+    wtt = (unsigned)n_; } while (0)
+#define CG_WTR_END do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) \
+    for (int k = 0; k < kWTraceParts; ++k) \
+      g_wgrad_trace[((int)blockIdx.x * 8 + (int)(threadIdx.x >> 6)) * kWTraceParts + k] = \
+          wtr[k]; } while (0)
 #else
 #define CG_WTR(acc, t, part)
 #define CG_WTR_PARAMS
 #define CG_WTR_ARGS
+#define CG_WTR_BEGIN
+#define CG_WTR_END
 #endif
 
 struct WgradArgs {
@@ -965,6 +977,57 @@ struct ReduceArgs {
   ReduceItem it[6];
 };
 
+// A thread's share [z0, z1) of an element's splits, `stride` floats apart from p
+// on, with up to 8 loads in flight; then the element's zc threads (zi = 0 ..
+// zc - 1, epb elements apart in the block) meet in LDS and thread zi == 0 adds
+// their sums in chunk order.  Every thread of the block comes here (barriers).
+__device__ __forceinline__ f32x4 reduce_splits(const float* p, bool live, int z0, int z1,
+                                               long long stride, int zc, int zi, int el,
+                                               int epb, f32x4* red) {
+  f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+  for (int z = z0; z < z1; z += 8) {
+    f32x4 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (live && z + k < z1) v[k] = *reinterpret_cast<const f32x4*>(p + (z + k) * stride);
+    }
+    sum += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+  }
+  if (zc > 1) {
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    if (zi == 0)
+      for (int k = 1; k < zc; ++k) sum += red[k * epb + el];
+    __syncthreads();
+  }
+  return sum;
+}
+
+// Float4 `rem` of output tile (bx, by)'s accumulator image -- (slot, tid) of the
+// workgroup that wrote it: slot = (s, mt, nt), tid = (wave, lane) -- is
+// dw[tap = wave + 8 s][cx, cx + 1 .. + 3][cg]: stored, or added by its one owner.
+template <class Item>
+__device__ __forceinline__ void reduce_commit(const Item& it, const f32x4& sum, int rem,
+                                              int bx, int by) {
+  const int slot = rem >> 9;
+  const int tid = rem & 511;
+  const int s = slot >> 3, mt = (slot >> 2) & 1, nt = slot & 3;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int tap = wave + 8 * s;
+  const int cg = by * 64 + nt * 16 + (lane & 15);
+  if (tap < it.taps && cg < it.Cg_real) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int cx = bx * 32 + mt * 16 + 4 * (lane >> 4) + r;
+      if (cx < it.Cx_real) {
+        float* q = it.dw + ((long long)tap * it.Cx_real + cx) * it.Cg_real + cg;
+        *q = it.store ? sum[r] : *q + sum[r];
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(ReduceArgs ra) {
   const ReduceItem& it = ra.it[blockIdx.y];
   __shared__ f32x4 red[256];
@@ -994,44 +1057,11 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(ReduceArgs ra) {
     const long long e = base + el;
     const bool live = e < total;
     const float* p = it.part + (live ? e : 0) * 4;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-    for (int z = z0; z < z1; z += 8) {
-      f32x4 v[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (live && z + k < z1)
-          v[k] = *reinterpret_cast<const f32x4*>(p + (z + k) * blk_stride);
-      }
-      sum += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-    if (zc > 1) {
-      red[threadIdx.x] = sum;
-      __syncthreads();
-      if (zi == 0)
-        for (int k = 1; k < zc; ++k) sum += red[k * epb + el];
-      __syncthreads();
-    }
+    const f32x4 sum = reduce_splits(p, live, z0, z1, blk_stride, zc, zi, el, epb, red);
     if (!live || zi != 0) continue;
     const int tile = (int)(e / per_tile);
     const int rem = (int)(e - (long long)tile * per_tile);
-    const int slot = rem >> 9;
-    const int tid = rem & 511;
-    const int bx = tile % it.gx, by = tile / it.gx;
-    const int s = slot >> 3, mt = (slot >> 2) & 1, nt = slot & 3;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int tap = wave + 8 * s;
-    const int cg = by * 64 + nt * 16 + (lane & 15);
-    if (tap < it.taps && cg < it.Cg_real) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int cx = bx * 32 + mt * 16 + 4 * (lane >> 4) + r;
-        if (cx < it.Cx_real) {
-          float* q = it.dw + ((long long)tap * it.Cx_real + cx) * it.Cg_real + cg;
-          *q = it.store ? sum[r] : *q + sum[r];
-        }
-      }
-    }
+    reduce_commit(it, sum, rem, tile % it.gx, tile / it.gx);
   }
 }
 
@@ -1067,15 +1097,7 @@ __global__ __launch_bounds__(512) void wgrad_multi_kernel(WgradMulti m) {
 #else
   const int rot = ((int)blockIdx.x >> 6) % m.n;
 #endif
-#ifdef CG_WGRAD_TRACE
-  unsigned wtr[kWTraceParts] = {};
-  unsigned wtt;
-  {
-    unsigned long long n_;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(n_)::"memory");
-    wtt = (unsigned)n_;
-  }
-#endif
+  CG_WTR_BEGIN;
   for (int k = 0; k < m.n; ++k) {
     int li = k + rot;
     if (li >= m.n) li -= m.n;
@@ -1103,11 +1125,7 @@ __global__ __launch_bounds__(512) void wgrad_multi_kernel(WgradMulti m) {
     __syncthreads();  // LDS is reused by the next item
     CG_WTR(wtr, wtt, 4);  // barrier between items
   }
-#ifdef CG_WGRAD_TRACE
-  if ((threadIdx.x & 63) == 0 && blockIdx.x < 256)
-    for (int k = 0; k < kWTraceParts; ++k)
-      g_wgrad_trace[((int)blockIdx.x * 8 + (int)(threadIdx.x >> 6)) * kWTraceParts + k] = wtr[k];
-#endif
+  CG_WTR_END;
 }
 
 // ---------------------------------------------------------------------------
@@ -1140,15 +1158,7 @@ struct WgradFlex {
 
 template <int R, int TPW, int ALLT>
 __global__ __launch_bounds__(512) void wgrad_flex_kernel(WgradFlex m) {
-#ifdef CG_WGRAD_TRACE
-  unsigned wtr[kWTraceParts] = {};
-  unsigned wtt;
-  {
-    unsigned long long n_;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(n_)::"memory");
-    wtt = (unsigned)n_;
-  }
-#endif
+  CG_WTR_BEGIN;
   const int* it = m.table + (size_t)blockIdx.x * (kFlexMaxItems * kFlexItemInts);
   for (int k = 0; k < kFlexMaxItems; ++k, it += kFlexItemInts) {
     const int li = __builtin_amdgcn_readfirstlane(it[0]);
@@ -1166,11 +1176,7 @@ __global__ __launch_bounds__(512) void wgrad_flex_kernel(WgradFlex m) {
     __syncthreads();  // LDS is reused by the next item
     CG_WTR(wtr, wtt, 4);
   }
-#ifdef CG_WGRAD_TRACE
-  if ((threadIdx.x & 63) == 0 && blockIdx.x < 256)
-    for (int k = 0; k < kWTraceParts; ++k)
-      g_wgrad_trace[((int)blockIdx.x * 8 + (int)(threadIdx.x >> 6)) * kWTraceParts + k] = wtr[k];
-#endif
+  CG_WTR_END;
 }
 
 // Reducing launch of the flex form: output tile t of a layer owns the slots
@@ -1226,41 +1232,10 @@ __global__ __launch_bounds__(256) void wgrad_flex_reduce_kernel(FlexReduceArgs r
     const int z1 = z0 + chunk < cnt ? z0 + chunk : cnt;
     const float* p = it.part + ((long long)p0 * per_tile + rem) * 4;
     const long long stride = (long long)per_tile * 4;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-    for (int z = z0; z < z1; z += 8) {
-      f32x4 v[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (z + k < z1) v[k] = *reinterpret_cast<const f32x4*>(p + (z + k) * stride);
-      }
-      sum += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-    if (zc > 1) {
-      red[threadIdx.x] = sum;
-      __syncthreads();
-      if (zi == 0)
-        for (int k = 1; k < zc; ++k) sum += red[k * epb + el];
-      __syncthreads();
-    }
+    // (epb divides per_tile: every element of a round is live and in one tile)
+    const f32x4 sum = reduce_splits(p, true, z0, z1, stride, zc, zi, el, epb, red);
     if (zi != 0) continue;
-    const int slot = rem >> 9;
-    const int tid = rem & 511;
-    const int bx = tile % it.gx, by = tile / it.gx;
-    const int s = slot >> 3, mt = (slot >> 2) & 1, nt = slot & 3;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int tap = wave + 8 * s;
-    const int cg = by * 64 + nt * 16 + (lane & 15);
-    if (tap < it.taps && cg < it.Cg_real) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int cx = bx * 32 + mt * 16 + 4 * (lane >> 4) + r;
-        if (cx < it.Cx_real) {
-          float* q = it.dw + ((long long)tap * it.Cx_real + cx) * it.Cg_real + cg;
-          *q = it.store ? sum[r] : *q + sum[r];
-        }
-      }
-    }
+    reduce_commit(it, sum, rem, tile % it.gx, tile / it.gx);
   }
 }
 

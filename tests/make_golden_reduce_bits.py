@@ -3,7 +3,10 @@
 every entry point whose kernel ends in a wave reduction and a fold of the
 waves' LDS slots, recorded from the libraries of ONE commit (named inside the
 file) so that a later commit which restates those folds can be held to the same
-bits (tests/test_hip_reduce_bits.py).  Data only.
+bits (tests/test_hip_reduce_bits.py).  Data only.  The groups conv_tails and
+wgrad_tails hold, per launch, the SHA-256 words of all output buffers of the MFMA
+kernels' tails (cg_swconv in every dispatch target and epilogue form, cg_wgrad
+and cg_wgrad_batched with partials), built with the tests' own case builders.
 
 Only the C ABI (through calciumgan_amd._lib) and seeded numpy inputs are used,
 and only paths whose result does not depend on the arrival order of atomics: a
@@ -295,6 +298,150 @@ def pair_histogram(out):
         out['{}/{}'.format(tag, k)] = bits(t)
 
 
+# ---------------------------------------------------------------------------
+# the output tails of the MFMA kernels
+# ---------------------------------------------------------------------------
+def launch_bits(*tensors):
+  """One entry per launch: the SHA-256 words of all its output buffers, guards
+  and sentinels included (a store outside the owned rows changes it too)."""
+  h = hashlib.sha256()
+  for t in tensors:
+    if t is not None:
+      a = t.detach().contiguous().cpu()
+      h.update(a.view(VIEW[a.element_size()]).numpy().tobytes())
+  return np.frombuffer(h.digest(), np.int64).copy()
+
+
+def conv_tails(out, f16):
+  """cg_swconv with the case builders of tests/test_hip_swconv.py and
+  tests/test_unshuffle_folded.py (the inputs whose float64 parity those tests
+  establish), the `real` recipe, deterministic forms only: every dispatch
+  target at one stage depth, the lean epilogues, the test_epilogues grid, the
+  per-sample scale, the ordered and the deferred penalty norm, out_shifts with
+  a side buffer and folded, the forward-only LayerNorm."""
+  import swconv_ref as S
+  import test_hip_swconv as T
+  import test_unshuffle_folded as F
+  lib = _lib.load()
+  pre = '{}/conv_tails/'.format('f16' if f16 else 'bf16')
+
+  def run(name, G, sigmoid=False, **kw):
+    L = T.Launch(G, T.case(G, f16, 'real', sigmoid), f16, 'real', sigmoid, **kw)
+    assert L.run() == 0, name
+    assert pre + name not in out, name
+    out[pre + name] = launch_bits(L.y, L.h, L.mean, L.rstd, L.ws, L.ssq, L.ssq_ws,
+                                  L.side)
+
+  for p in T.dispatch_cases():
+    G, kw, _ = p.values
+    if kw.get('ks', 2) != 2:
+      continue  # (the stage depth does not reach the epilogue)
+    if kw['epi'] == S.EPI_LN:
+      run('dispatch/' + p.id, G, ln=T.ln_params(G) + (True,), **kw)
+    else:
+      run('dispatch/' + p.id, G, mask='inplace' if kw.get('ksplit') else None, **kw)
+  was = lib.cg_debug_lean_epilogue(1)
+  try:
+    for p in T.lean_cases():
+      form, G, kw = p.values
+      if form == 'maskshift':
+        run(p.id, G, out_shifts=((2, -1, 0), 1, 2), **kw)
+      else:
+        run(p.id, G, ssq='ordered' if form == 'lrelussq' else None, **kw)
+  finally:
+    lib.cg_debug_lean_epilogue(was)
+  for tile, tkw in T.FEATURE_TILES:
+    for epi in (S.EPI_NONE, S.EPI_LRELU, S.EPI_MASK, S.EPI_SIGMOID):
+      for out_f32 in (0, 1):
+        for bias in (True, False):
+          run('epilogues/t{}-epi{}-f32{}-bias{}'.format(tile, epi, out_f32, int(bias)),
+              S.EPI_GEOM, epi == S.EPI_SIGMOID, bias=bias, tile=tile, epi=epi,
+              out_f32=out_f32, **tkw)
+  for tile in (9, 12, 13):
+    for epi in (S.EPI_NONE, S.EPI_LRELU, S.EPI_MASK):
+      run('row_scale/t{}-epi{}'.format(tile, epi), S.SWP_DOWN,
+          row_scale=np.array([-1.5, 0.0, 2.0**-20]), tile=tile, pmajor=1, epi=epi)
+  for tile in (2, 6, 12, 13):
+    rows = _lib.tile_shape(tile)[0]
+    for Lu, out_f32 in ((rows, 1), (2 * rows, 0)):
+      for form in ('ordered', 'defer'):
+        run('rowsumsq/t{}-Lu{}-{}'.format(tile, Lu, form), S.SSQ_GEOMS[Lu], tile=tile,
+            out_f32=out_f32, ssq=form)
+  for tile, side_rows in ((1, 2), (6, 3), (12, 2), (13, 5)):
+    for epi in (S.EPI_NONE, S.EPI_MASK):
+      run('out_shifts/t{}-side{}-epi{}'.format(tile, side_rows, epi), S.SWP_UP,
+          out_shifts=((2, -2, 0), 1, side_rows), tile=tile, epi=epi)
+  # folded: |shift| = 1 .. 3 of both signs ('small'), the largest admitted, +-15
+  # ('m15'), and the zero tail of a second column tile ('n102')
+  for p in F.PARAMS:
+    if p.id.split('-')[0] in ('small', 'm15', 'n102'):
+      G, osh, oseg, side_rows, Cy, tile = p.values
+      pr = F.Pair(G, T.case(G, f16, 'real'), f16, 'real', osh, oseg, side_rows, Cy, tile,
+                  T.ALPHA)
+      out[pre + 'folded/' + p.id] = launch_bits(pr.launch(folded=True))
+  for tile in (6, 12):
+    G = S.LN_GEOMS[0]
+    run('ln_forward_only/t{}'.format(tile), G, ln=T.ln_params(G) + (False,), tile=tile,
+        epi=S.EPI_LN)
+
+
+def wgrad_tails(out, f16):
+  """cg_wgrad with partials and `store` (one split, a few, and enough that
+  several threads share an element's splits; real channel counts short of
+  their pitches; 12 and 20 taps) and cg_wgrad_batched in the split and the
+  flex form, with the case builders of tests/test_hip_wgrad.py."""
+  import test_hip_wgrad as T
+  import wgrad_ref as W
+  lib = _lib.load()
+  pre = '{}/wgrad_tails/'.format('f16' if f16 else 'bf16')
+
+  def make(G, **kw):
+    c = T.case(G, f16, 'real')
+    return T.Launch(G, c['x'], c['g'], f16, **kw)
+
+  def record(name, L):
+    assert pre + name not in out, name
+    out[pre + name] = launch_bits(L.dw, L.db, L.ws)
+
+  def run(name, G, **kw):
+    L = make(G, **kw)
+    assert L.run() == 0, name
+    record(name, L)
+
+  run('join/direct1', W.JOIN, join='direct', nsplit=1, bias_rows=576)
+  for nsplit in (2, 3, 9, 17):  # the reduce kernel's zc = 1, 1, 2, 4
+    run('join/store{}'.format(nsplit), W.JOIN, join='store', nsplit=nsplit, bias_rows=576)
+  for taps, gi in ((12, 1), (20, 0), (20, 1)):
+    G = W.instantiation_geoms(taps)[gi]
+    run('taps{}-g{}'.format(taps, gi), G, join='store', nsplit=2,
+        bias_rows=W.rows_of(G) // 2)
+  for Cx, Cxp, Cg, Cgp in W.CHANNELS[2:4]:
+    run('channels/{}x{}'.format(Cx, Cg), W.channel_geom(Cx, Cg), join='store', nsplit=3,
+        bias_rows=128, Cxp=Cxp, Cgp=Cgp)
+  run('bias_ring/rows100', W.BIAS_RING, join='store', nsplit=2, bias_rows=100)
+  for bias_rows in (20, 36):
+    run('bias_nseg/rows{}'.format(bias_rows), W.BIAS_NSEG, join='store', nsplit=2,
+        bias_rows=bias_rows)
+  batches = [
+      ('batch', lambda: [make(G, join='store', bias_rows=128) for G in W.BATCH]),
+      ('join', lambda: [make(W.JOIN, join='store', nsplit=n, bias_rows=576)
+                        for n in (9, 17)]),
+      ('bias_ring', lambda: [make(W.BIAS_RING, join='store', nsplit=2, bias_rows=r)
+                             for r in (128, 32)]),
+      ('bias_nseg', lambda: [make(W.BIAS_NSEG, join='store', nsplit=2, bias_rows=r)
+                             for r in (20, 36)])]
+  for mode, form in ((0, 'split'), (2, 'flex')):
+    was = lib.cg_debug_wgrad_flex(mode)
+    try:
+      for name, mk in batches:
+        Ls = mk()
+        assert T.run_batched(Ls) == 0, (form, name)
+        for i, L in enumerate(Ls):
+          record('batched-{}/{}/{}'.format(form, name, i), L)
+    finally:
+      lib.cg_debug_wgrad_flex(was)
+
+
 def compute():
   """name -> integer array, from the libraries _lib resolves."""
   out = {}
@@ -305,6 +452,8 @@ def compute():
     rownorm(out, f16)
     head(out, f16)
     colsum(out, f16)
+    conv_tails(out, f16)
+    wgrad_tails(out, f16)
   _lib.use('bf16')
   signal_metrics(out)
   spike_stats_error(out)

@@ -4,7 +4,10 @@ tests/golden/reduce_bits.npz holds the raw output bits of every entry point
 whose kernel ends in a wave reduction and a fold of the waves' LDS slots,
 recorded (tests/make_golden_reduce_bits.py) from the libraries of the commit
 before the folds were stated once in cg_common.h (block_fold_put /
-block_fold_get); its hash is in the file.  The same calls on the same seeded
+block_fold_get), and since the output tails of the MFMA kernels were given
+shared helpers also the bits of every cg_swconv tail and cg_wgrad reduction
+(groups conv_tails, wgrad_tails), recorded from that change's parent; the
+commit's hash is in the file.  The same calls on the same seeded
 inputs must give the same bits from this tree's libraries, in both precision
 builds: the order of every sum, minimum and maximum is unchanged."""
 import os
@@ -48,10 +51,11 @@ def test_the_same_cases(recorded, computed):
   for pre, family in [('bf16', f) for f in (
       'gp_finalize+critic_loss', 'gp_critic_loss', 'neg_mean', 'gp_loss_scale',
       'rownorm', 'dense1', 'dense1_bce', 'colsum', 'colsum_deferred',
-      'signal_metrics', 'spike_stats_error', 'tensor_summary', 'pair_histogram')
+      'signal_metrics', 'spike_stats_error', 'tensor_summary', 'pair_histogram',
+      'conv_tails', 'wgrad_tails')
                      ] + [('f16', f) for f in (
                          'gp_loss_scale', 'rownorm', 'dense1', 'dense1_bce', 'colsum',
-                         'colsum_deferred')]:
+                         'colsum_deferred', 'conv_tails', 'wgrad_tails')]:
     assert any(k.startswith('{}/{}/'.format(pre, family)) for k in computed), (
         pre, family)
 

@@ -232,6 +232,7 @@ class Launch(object):
     self.y = (P.sent32(n + GUARD) if d.out_f32 else P.sent_act((n + GUARD,), f16))
     d.y = self.y.data_ptr()
     self.bias = None
+    self.h = self.mean = self.rstd = self.ws = self.ssq_ws = None
     if bias:
       self.bias = P.dev32(np.r_[c['bias'], [np.nan] * 8])
       d.bias = self.bias.data_ptr()
