@@ -16,7 +16,8 @@ LIB_F16 = os.path.join(CSRC, 'libcalciumgan_hip_f16.so')
 SOURCES = ['swconv.hip', 'swconv_swp.hip', 'wgrad.hip', 'pointwise.hip',
            'dense_rows.hip', 'spikes.hip', 'van_rossum.hip',
            'victor_purpura.hip', 'pair_hist.hip', 'ifft.hip', 'summary.hip',
-           'windows.hip', 'mlp.hip', 'patterns.hip', 'dg_fit.hip']
+           'windows.hip', 'mlp.hip', 'patterns.hip', 'dg_fit.hip',
+           'spike_ccg.hip']
 HEADERS = ['cg_common.h', 'swconv_args.h', 'swconv_epilogue.h', 'oasis_flat.h',
            'fft_stages.h',
            os.path.join('..', '..', 'include', 'calciumgan_hip.h')]

@@ -587,6 +587,18 @@ def _pattern_moments(q, K):
   return mean, second - mean[:, None] * mean[None, :]
 
 
+def _js_divergence_bits(p, q):
+  """Jensen-Shannon divergence in bits of two float64 probability vectors: 1/2
+  sum p log2(p / m) + 1/2 sum q log2(q / m), m = (p + q) / 2; a term with a zero
+  numerator is 0."""
+  m = (p + q) / 2.0
+  js = 0.0
+  for side in (p, q):
+    on = side > 0
+    js += 0.5 * float(np.sum(side[on] * np.log2(side[on] / m[on])))
+  return js
+
+
 def pattern_scores(ref_counts, counts):
   """How far the pattern probabilities q = counts / sum(counts) are from p =
   ref_counts / sum(ref_counts); both integer (2^K,).  Host float64, whichever
@@ -611,11 +623,7 @@ def pattern_scores(ref_counts, counts):
   K = len(ref).bit_length() - 1
   p = ref.astype(np.float64) / float(ref.sum())
   q = cnt.astype(np.float64) / float(cnt.sum())
-  m = (p + q) / 2.0
-  js = 0.0
-  for side in (p, q):
-    on = side > 0
-    js += 0.5 * float(np.sum(side[on] * np.log2(side[on] / m[on])))
+  js = _js_divergence_bits(p, q)
   both = (ref > 0) & (cnt > 0)
   r = float('nan')
   if both.sum() >= 2:
@@ -637,3 +645,195 @@ def pattern_scores(ref_counts, counts):
     scores['pair_covariance_mae'] = (
         float(np.mean(np.abs(cov_p[iu] - cov_q[iu]))) if K > 1 else float('nan'))
   return scores
+
+
+# -- structure across time: cross-correlograms and population counts ------------
+# (compute_metrics.py --temporal_metrics; csrc/spike_ccg.hip)
+CCG_MAX_NEURONS = 1024  # CG_CCG_MAX_C
+CCG_MAX_LAG = 256       # CG_CCG_MAX_LAG
+
+
+def _binary_trials(spikes):
+  spikes = np.asarray(spikes)
+  if spikes.ndim != 3:
+    raise ValueError('(B, T, C) expected')
+  # != 0: a NaN is a spike, -0.0 is not
+  return (spikes != 0).astype(np.int64)
+
+
+def cross_correlogram(spikes, max_lag):
+  """int64 (B, max_lag + 1, C, C) of trials (B, T, C), a frame a spike when it is
+  != 0:
+    ccg[b][tau][i][j] = sum_{t = 0}^{T - 1 - tau} s_i(t) s_j(t + tau)
+  -- how often neuron j fires tau frames after neuron i.  ccg[b][0][i][i] is the
+  spike count n_i, ccg[b][tau][i][i] the autocorrelogram; a lag tau >= T gives
+  zeros.  One integer matrix product per lag; the statement cg_spike_ccg
+  (csrc/spike_ccg.hip) is tested against, for equality."""
+  s = _binary_trials(spikes)
+  max_lag = int(max_lag)
+  if max_lag < 0:
+    raise ValueError('max_lag < 0')
+  B, T, C = s.shape
+  out = np.zeros((B, max_lag + 1, C, C), np.int64)
+  for tau in range(min(max_lag, T - 1) + 1):
+    # (B, C, T - tau) @ (B, T - tau, C)
+    out[:, tau] = np.matmul(s[:, :T - tau].transpose(0, 2, 1), s[:, tau:])
+  return out
+
+
+def population_count_histogram(spikes):
+  """int64 (B, C + 1) of trials (B, T, C): hist[b][k] is the number of frames of
+  trial b in which exactly k neurons fire; every row sums to T.  The statement
+  cg_spike_population_hist is tested against."""
+  s = _binary_trials(spikes)
+  B, _, C = s.shape
+  out = np.zeros((B, C + 1), np.int64)
+  for b in range(B):
+    out[b] = np.bincount(s[b].sum(-1), minlength=C + 1)
+  return out
+
+
+def cross_correlogram_device(spikes, max_lag):
+  """`cross_correlogram` on the GPU (cg_spike_ccg): float32 device tensor
+  (B, T, C), any strides, -> int32 device (B, max_lag + 1, C, C), the
+  statement's integers (T <= 2^24, C <= 1024, max_lag <= 256).  One launch, no
+  workspace, nothing zeroed beforehand, no host synchronisation."""
+  import torch
+  from ... import _lib as hip
+  B, T, C = _trial_batch(spikes)
+  max_lag = int(max_lag)
+  if not 0 <= max_lag <= CCG_MAX_LAG:
+    raise ValueError('max_lag = {}: 0 .. {} supported'.format(max_lag,
+                                                              CCG_MAX_LAG))
+  ccg = torch.empty(B, max_lag + 1, C, C, dtype=torch.int32,
+                    device=spikes.device)
+  hip.call('cg_spike_ccg', spikes, B, T, C, spikes.stride(0), spikes.stride(1),
+           spikes.stride(2), max_lag, ccg, hip.stream())
+  return ccg
+
+
+def population_count_histogram_device(spikes):
+  """`population_count_histogram` on the GPU (cg_spike_population_hist): float32
+  device tensor (B, T, C), any strides, -> int32 device (B, C + 1).  One launch,
+  no host synchronisation."""
+  import torch
+  from ... import _lib as hip
+  B, T, C = _trial_batch(spikes)
+  hist = torch.empty(B, C + 1, dtype=torch.int32, device=spikes.device)
+  hip.call('cg_spike_population_hist', spikes, B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), hist, hip.stream())
+  return hist
+
+
+def temporal_totals(spikes, max_lag):
+  """(ccg (max_lag + 1, C, C), hist (C + 1,), trials): `cross_correlogram` and
+  `population_count_histogram` of trials (B, T, C) summed over the trials, int64,
+  and B."""
+  B, _, C = np.shape(spikes)
+  ccg = np.zeros((int(max_lag) + 1, C, C), np.int64)
+  hist = np.zeros((C + 1,), np.int64)
+  for i in range(0, B, 16):  # (the per-trial correlograms of 16 trials at a time)
+    ccg += cross_correlogram(spikes[i:i + 16], max_lag).sum(0)
+    hist += population_count_histogram(spikes[i:i + 16]).sum(0)
+  return ccg, hist, int(B)
+
+
+def temporal_totals_device(spikes, max_lag, group_bytes=256 << 20):
+  """`temporal_totals` on the GPU: float32 device tensor (B, T, C) -> (device
+  int64 ccg (max_lag + 1, C, C), device int64 hist (C + 1,), B).  The batch is
+  walked in groups of as many trials as have their int32 correlograms fit in
+  `group_bytes` (one at least); integer sums, so the grouping does not show.
+  No host synchronisation."""
+  import torch
+  B, T, C = _trial_batch(spikes)
+  max_lag = int(max_lag)
+  per_trial = (max_lag + 1) * C * C * 4
+  group = max(int(group_bytes) // per_trial, 1)
+  ccg = torch.zeros(max_lag + 1, C, C, dtype=torch.int64, device=spikes.device)
+  hist = torch.zeros(C + 1, dtype=torch.int64, device=spikes.device)
+  for i in range(0, B, group):
+    part = spikes[i:i + group]
+    ccg += cross_correlogram_device(part, max_lag).sum(0, dtype=torch.int64)
+    hist += population_count_histogram_device(part).sum(0, dtype=torch.int64)
+  return ccg, hist, int(B)
+
+
+def _pearson(a, b):
+  """Pearson r of two float64 vectors, NaN with fewer than two values or no
+  variance on a side.  sum(da db) / sqrt(sum(da^2) sum(db^2)): exactly 1 for
+  equal vectors (sqrt(fl(x x)) == x)."""
+  if len(a) < 2:
+    return float('nan')
+  da, db = a - np.mean(a), b - np.mean(b)
+  va, vb = float(da @ da), float(db @ db)
+  if va == 0 or vb == 0:
+    return float('nan')
+  return float(da @ db) / math.sqrt(va * vb)
+
+
+def _mean_abs_difference(a, b):
+  return float(np.mean(np.abs(a - b))) if np.size(a) else float('nan')
+
+
+def temporal_scores(ref, other, T):
+  """How far the structure across time of `other` is from that of `ref`; both
+  `temporal_totals` (or `temporal_totals_device`, brought to the host) of trials
+  of T frames with the same C and max_lag.  Host float64, whichever device
+  counted.  Per side, with N trials, n_i = ccg[0][i][i] and p_i = n_i / (N T):
+    autocorrelogram_mae        mean |difference| of A_i(tau) = ccg[tau][i][i] / n_i
+                               over tau = 1 .. max_lag and the neurons with n_i > 0
+                               on both sides; NaN when there is no such value
+    lag_covariance_mae         mean |difference| of cov_ij = ccg[1][i][j] / (N (T -
+    lag_covariance_correlation 1)) - p_i p_j over the ordered pairs i != j, and
+                               the Pearson r between the two sides' values (NaN
+                               with fewer than two pairs or no variance); both
+                               NaN when max_lag < 1 or T < 2
+    cross_correlogram_mae      mean |difference| of ccg[tau][i][j] / (N (T - tau))
+                               over tau = 0 .. max_lag, tau < T, and i != j
+    population_count_js_bits   Jensen-Shannon divergence in bits of the two
+                               hist / sum(hist)
+    population_count_mean      [ref, other] mean number of neurons firing in a
+                               frame
+    max_lag, num_trials        num_trials as [ref, other]"""
+  sides = []
+  for ccg, hist, n in (ref, other):
+    ccg, hist = (np.asarray(a.cpu() if hasattr(a, 'cpu') else a).astype(np.int64)
+                 for a in (ccg, hist))
+    if not (ccg.ndim == 3 and ccg.shape[1] == ccg.shape[2] and
+            hist.shape == (ccg.shape[1] + 1,) and int(n) >= 1 and
+            hist.sum() > 0):
+      raise ValueError('totals (ccg (L, C, C), hist (C + 1,), trials) expected')
+    sides.append((ccg, hist, int(n)))
+  T = int(T)
+  if T < 1 or sides[0][0].shape != sides[1][0].shape:
+    raise ValueError('the two sides differ in shape, or T < 1')
+  L, C = sides[0][0].shape[:2]
+  off = ~np.eye(C, dtype=bool)
+  auto, cov, cross, pop, mean = [], [], [], [], []
+  for ccg, hist, n in sides:
+    count = np.diagonal(ccg[0]).astype(np.float64)
+    p = count / (float(n) * T)
+    with np.errstate(invalid='ignore', divide='ignore'):
+      auto.append(np.stack([np.diagonal(ccg[tau]) for tau in range(1, L)]
+                           ).astype(np.float64) / count if L > 1 else
+                  np.zeros((0, C)))
+    cov.append(ccg[1][off].astype(np.float64) / (float(n) * (T - 1)) -
+               (p[:, None] * p[None, :])[off] if L > 1 and T > 1 else
+               np.zeros(0))
+    cross.append(np.concatenate(
+        [ccg[tau][off].astype(np.float64) / (float(n) * (T - tau))
+         for tau in range(min(L, T))]))
+    pop.append(hist.astype(np.float64) / float(hist.sum()))
+    mean.append(float(np.arange(C + 1) @ pop[-1]))
+  fires = (np.diagonal(sides[0][0][0]) > 0) & (np.diagonal(sides[1][0][0]) > 0)
+  return {
+      'autocorrelogram_mae': _mean_abs_difference(auto[0][:, fires],
+                                                  auto[1][:, fires]),
+      'lag_covariance_mae': _mean_abs_difference(cov[0], cov[1]),
+      'lag_covariance_correlation': _pearson(cov[0], cov[1]),
+      'cross_correlogram_mae': _mean_abs_difference(cross[0], cross[1]),
+      'population_count_js_bits': _js_divergence_bits(pop[0], pop[1]),
+      'population_count_mean': mean,
+      'max_lag': L - 1,
+      'num_trials': [sides[0][2], sides[1][2]],
+  }

@@ -14,6 +14,7 @@ the reference's compute_metrics.py (BASELINE configs[3]: recorded-data pipeline
 
   python compute_metrics.py --output_dir runs/001 [--all_epochs]
       [--device gpu [--batch_trials 128]] [--victor_purpura [--vp_q 1.0]]
+      [--temporal_metrics [--max_lag 24]]
 
 --device gpu (not a reference flag) takes the deconvolution, the firing rates,
 the per-trial correlations and the van Rossum matrices through the HIP kernels
@@ -36,6 +37,16 @@ of a trial: spike_metrics.victor_purpura_distance_frames on the host,
 cg_victor_purpura (csrc/victor_purpura.hip) on the device.  The two hold the
 same bits, so both devices report the same figure.  Without the flag nothing is
 computed or written beyond what was before.
+
+--temporal_metrics [--max_lag 24] (not reference flags, absent from the namespace
+unless given) adds `temporal`: spike_metrics.temporal_scores of the generated
+file against the validation cache over the first num_samples trials of each --
+autocorrelograms, lag-1 covariances, cross-correlograms up to --max_lag frames
+and the population-count histogram, the time-axis panels of Spike-GAN's figure
+3.  Both come from integer totals: spike_metrics.temporal_totals on the host,
+cg_spike_ccg and cg_spike_population_hist (csrc/spike_ccg.hip) on the device in
+batches of --batch_trials, the recorded side's kept across epochs; only the
+totals come to the host and both devices write the same dict.
 
 The KL is the reference's: both samples cut into 30 equal-width bins over their
 pooled range by pandas.cut, empty bins replaced by 1e-10 (:80-111) -- pandas is
@@ -214,6 +225,46 @@ def _map(hparams, fn, args):
   return [fn(*a) for a in args]
 
 
+TEMPORAL_MAX_LAG = 24  # --max_lag: one second of frames
+
+
+def _trial_spikes(hparams, filename):
+  """The first num_samples trials of `filename` as an NWC host array."""
+  spikes = utils.set_array_format(
+      np.asarray(h5_helper.get(filename, name='spikes')), 'NWC', hparams)
+  return spikes[:hparams.num_samples]
+
+
+def temporal_totals_host(hparams, filename):
+  """(spike_metrics.temporal_totals, T) of the trials of `filename`."""
+  spikes = _trial_spikes(hparams, filename)
+  return spike_metrics.temporal_totals(
+      spikes, getattr(hparams, 'max_lag', TEMPORAL_MAX_LAG)), spikes.shape[1]
+
+
+def temporal_report(hparams, filename, totals):
+  """--temporal_metrics: spike_metrics.temporal_scores of `filename` against
+  the validation cache; totals(hparams, filename) -> ((ccg, hist, trials), T),
+  the recorded side's kept across epochs."""
+  real = getattr(hparams, '_recorded_temporal_totals', None)
+  if real is None:  # the validation set is the same for every epoch
+    real = hparams._recorded_temporal_totals = totals(hparams,
+                                                      hparams.validation_cache)
+  fake = totals(hparams, filename)
+  if real[1] != fake[1]:
+    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
+                     .format(filename, fake[1], real[1]))
+  scores = spike_metrics.temporal_scores(real[0], fake[0], real[1])
+  if hparams.verbose:
+    for name, label in (('autocorrelogram_mae', 'autocorrelogram    MAE'),
+                        ('lag_covariance_mae', 'lag-1 covariance   MAE'),
+                        ('lag_covariance_correlation', 'lag-1 covariance     r'),
+                        ('cross_correlogram_mae', 'cross-correlogram  MAE'),
+                        ('population_count_js_bits', 'population count    JS')):
+      print('\t{}: {:.04g}'.format(label, scores[name]))
+  return scores
+
+
 def compute_epoch_spike_metrics(hparams, filename, epoch):
   """:483-497 without plot_signals / raster_plots: dict of the statistics."""
   if not h5_helper.contains(filename, 'spikes'):
@@ -245,6 +296,8 @@ def compute_epoch_spike_metrics(hparams, filename, epoch):
     out['victor_purpura_kl'] = dict(mean=float(np.mean(kl)))
     if hparams.verbose:
       print('\tVictor-Purpura     KL mean: {:.04f}'.format(np.mean(kl)))
+  if getattr(hparams, 'temporal_metrics', False):
+    out['temporal'] = temporal_report(hparams, filename, temporal_totals_host)
   return out
 
 
@@ -411,6 +464,19 @@ def device_kl(hparams, filename):
   return figures
 
 
+def temporal_totals_device(hparams, filename):
+  """`temporal_totals_host` through cg_spike_ccg and cg_spike_population_hist, a
+  batch of trials at a time; the int64 totals summed on the device and brought
+  to the host once."""
+  spikes = _trial_spikes(hparams, filename)
+  max_lag = getattr(hparams, 'max_lag', TEMPORAL_MAX_LAG)
+  ccg = hist = None
+  for batch in _batches(hparams, spikes):
+    c, h, _ = spike_metrics.temporal_totals_device(batch, max_lag)
+    ccg, hist = (c, h) if ccg is None else (ccg + c, hist + h)
+  return (ccg.cpu().numpy(), hist.cpu().numpy(), len(spikes)), spikes.shape[1]
+
+
 def compute_epoch_spike_metrics_device(hparams, filename, epoch):
   """`compute_epoch_spike_metrics` with the statistics from the device; the
   histograms behind the KL from cg_pair_histogram (`device_kl`) unless
@@ -447,6 +513,8 @@ def compute_epoch_spike_metrics_device(hparams, filename, epoch):
     out['victor_purpura_kl'] = dict(mean=float(np.mean(kl)))
     if hparams.verbose:
       print('\tVictor-Purpura     KL mean: {:.04f}'.format(np.mean(kl)))
+  if getattr(hparams, 'temporal_metrics', False):
+    out['temporal'] = temporal_report(hparams, filename, temporal_totals_device)
   return out
 
 
@@ -518,6 +586,15 @@ def build_parser():
   parser.add_argument('--vp_q', type=float, default=argparse.SUPPRESS,
                       help='--victor_purpura: cost per second of shifting a '
                       'spike (default 1.0)')
+  # (absent unless given, like --victor_purpura)
+  parser.add_argument('--temporal_metrics', action='store_true',
+                      default=argparse.SUPPRESS,
+                      help='also report `temporal`: autocorrelogram, lagged '
+                      'covariance, cross-correlogram and population-count '
+                      'figures of the generated against the recorded trials')
+  parser.add_argument('--max_lag', type=int, default=argparse.SUPPRESS,
+                      help='--temporal_metrics: largest lag in frames '
+                      '(default 24, at most 256)')
   return parser
 
 

@@ -821,6 +821,41 @@ int cg_pair_histogram(const double* a, long long a_sp, long long a_si,
                       long long b_si, long long b_sj, int P, int C, int num_bins,
                       int* counts, int* valid, double* edges, int* status,
                       void* stream);
+/* Cross-correlograms of the C trains of every sample (spike_ccg.hip; the numpy
+ * statement is spike_metrics.cross_correlogram).  Added under ABI 20.  With
+ * s_i(t) = [spikes[b * s_b + t * s_t + i * s_c] != 0] (a NaN is a spike, -0.0 is
+ * not),
+ *   ccg[b][tau][i][j] = sum_{t = 0}^{T - 1 - tau} s_i(t) s_j(t + tau),
+ *                       tau = 0 .. max_lag
+ * -- how often neuron j fires tau frames after neuron i; a lag tau >= T gives
+ * zeros, and frames of sample b never pair with frames of sample b + 1.  The
+ * diagonal of the plane tau = 0 holds the spike counts, the diagonals of the
+ * others the autocorrelograms.  ccg: int32 [B][max_lag + 1][C][C].
+ * The products run on v_mfma_f32_16x16x32_bf16 with time as the K dimension: 0
+ * and 1 are exact in bf16 and an f32 sum of at most 2^24 of their products is
+ * exact, hence T <= 2^24 and every count is the exact integer.  One launch; a
+ * workgroup owns a 64 x 64 block of neurons of one sample at 8 consecutive lags
+ * over the whole of T, so every element is written exactly once: nothing has
+ * to be zeroed beforehand, no global atomics, no workspace, the same bits every
+ * call.
+ * CG_EINVAL (nothing launched): a NULL spikes or ccg, B, T or C < 1, T > 2^24,
+ * C > CG_CCG_MAX_C, max_lag < 0 or max_lag > CG_CCG_MAX_LAG. */
+#define CG_CCG_MAX_C 1024
+#define CG_CCG_MAX_LAG 256
+int cg_spike_ccg(const float* spikes, int B, int T, int C, long long s_b,
+                 long long s_t, long long s_c, int max_lag, int* ccg,
+                 void* stream);
+/* Population counts (spike_ccg.hip; spike_metrics.population_count_histogram):
+ *   hist[b][k] = number of frames t < T of sample b in which exactly k of the C
+ *                neurons fire, k = 0 .. C
+ * hist: int32 [B][C + 1]; every row sums to T.  One workgroup per sample counts
+ * into a table in LDS and writes every element: nothing has to be zeroed
+ * beforehand, no global atomics, the same bits every call.
+ * CG_EINVAL (nothing launched): a NULL spikes or hist, B, T or C < 1, T > 2^24,
+ * C > CG_CCG_MAX_C. */
+int cg_spike_population_hist(const float* spikes, int B, int T, int C,
+                             long long s_b, long long s_t, long long s_c,
+                             int* hist, void* stream);
 
 /* Pattern counts of the surrogate experiment (patterns.hip; the numpy statement
  * is spike_metrics.pattern_histogram).  Added under ABI 20.  A sample is T time
