@@ -30,18 +30,16 @@ import torch
 from ... import _lib
 from ... import nets
 from ... import parallel
+from . import draws
 from . import replay
 from .optimizer import Optimizer
 from .registry import register
 
 # main.py:11-12 (CALCIUMGAN_SEED: another draw of the noise / interpolation /
 # shift streams, for seed-to-seed comparisons -- tools/e2e_seeds.sh)
-_SEED = int(__import__('os').environ.get('CALCIUMGAN_SEED', '1234'))
+_SEED = int(os.environ.get('CALCIUMGAN_SEED', '1234'))
 _METRIC_KEYS = ('signals_metrics/min', 'signals_metrics/max',
                 'signals_metrics/mean', 'signals_metrics/std')
-# staged words of a BCE step: [2B plan shifts int32 (4, 2) | fake-segment plan
-# shifts (4, 1) | Adam step sizes f32 (D, G)]
-_BCE_STAGE_WORDS = 14
 
 
 @register('gan')
@@ -98,9 +96,7 @@ class GAN(object):
 
   # -- helpers ---------------------------------------------------------------
   def _to_device(self, x):
-    if not torch.is_tensor(x):
-      x = torch.as_tensor(x)
-    return x.to(device=self.device, dtype=torch.float32).contiguous()
+    return draws.to_device(x, self.device)
 
   def get_noise(self, batch_size):
     """gan.py:29-30: N(0,1) of shape (batch,) + noise_shape."""
@@ -205,18 +201,18 @@ class GAN(object):
   def _build_state(self, B):
     dev = self.device
     dws = self.discriminator.net.workspace(2 * B)
-    stage = torch.zeros(_BCE_STAGE_WORDS, dtype=torch.int32, device=dev)
+    stage = torch.zeros(draws.BCE_STAGE_WORDS, dtype=torch.int32, device=dev)
+    _, dis_shifts, gen_shifts, _ = draws.bce_stage(stage)
     f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
     return dict(
         gws=self.generator.net.workspace(B),
         dws=dws,
         stage_dev=stage,
         # D chain over [fake | real]; segment 0 is the fake batch
-        dis=dws.plan(2 * B, B, None, want_norm=False,
-                     shifts=stage[0:8].view(4, 2)),
+        dis=dws.plan(2 * B, B, None, want_norm=False, shifts=dis_shifts),
         # G chain: the same workspace's first B samples (the fake segment's
         # activations of the 2B forward), input gradient down to layer 1
-        gen=dws.plan(B, B, 0, want_norm=False, shifts=stage[8:12].view(4, 1)),
+        gen=dws.plan(B, B, 0, want_norm=False, shifts=gen_shifts),
         coef_d=f32(2 * B),
         coef_g=f32(B),
         delta_g=torch.zeros_like(dws.delta[-1][:B]),
@@ -226,29 +222,18 @@ class GAN(object):
         # the last launches of train(); train() hands out a COPY
         out=f32(7))
 
-  def _bce_shifts(self, r):
-    """Host int32 (12,): the (4, 2) [fake | real] shifts of the 2B plan, then the
-    fake segment's 4 for the G chain's plan.  r None: ONE draw of the shared
-    stream, (4, 2) = [shifts_real | shifts_fake] (z is drawn before it)."""
-    if r is None:
-      sh = self._streams.shifts(2)
-      real_s, fake_s = sh[:, 0], sh[:, 1]
-    else:
-      real_s = torch.as_tensor(r['shifts_real'], dtype=torch.int32).reshape(4)
-      fake_s = torch.as_tensor(r['shifts_fake'], dtype=torch.int32).reshape(4)
-    return torch.cat([torch.stack([fake_s, real_s], 1).reshape(-1), fake_s])
-
   def _bce_forward(self, st, real, z, shifts, training=True, seeds=True):
     """Steps 1-4: G(z) -> X0 = [fake | real] -> D over 2B -> cg_dense1_bce.
-    shifts: host int32 (12,) (_bce_shifts) or None when already staged.
+    shifts: the 12 ints of draws.shifts(., ., 2), on the host or staged.
     seeds=False (validate): losses only, no seeds."""
     net_g, net_d = self.generator.net, self.discriminator.net
     B = real.shape[0]
     lay, last = net_d.layers[0], net_d.layers[-1]
     dws, pd = st['dws'], st['dis']
     s = _lib.stream()
-    if shifts is not None:
-      st['stage_dev'][:12].copy_(shifts)
+    staged = draws.bce_stage(st['stage_dev'])[0]
+    if shifts.data_ptr() != staged.data_ptr():  # (else staged in place)
+      staged.copy_(shifts)
     fake = st['gws'].forward(z, keep=training, training=training)
     x0 = pd.x0
     _lib.call('cg_cast_pad', fake, x0, B * lay.lin, lay.cin, net_g.Cf, lay.cinp,
@@ -270,18 +255,13 @@ class GAN(object):
 
   def _bce_compute(self, real, r=None):
     """Steps 1-6: leaves both models' gradients in params.grad and the losses
-    in the state's `loss`; updates nothing.  r: injected draws
-    (dict(z=, shifts_real=, shifts_fake=)), dict(shifts_dev=True) when the
-    shifts are staged on the device (graph replay), or None."""
+    in the state's `loss`; updates nothing.  r: the source of the draws
+    (draws.py; injected: dict(z=, shifts_real=, shifts_fake=))."""
     B = real.shape[0]
     st = self._get_state(B)
     net_g, net_d = self.generator.net, self.discriminator.net
-    if r is None or 'shifts_dev' in r:
-      z = self.get_noise(B)
-      shifts = None if r is not None else self._bce_shifts(None)
-    else:
-      z = self._to_device(r['z'])
-      shifts = self._bce_shifts(r)
+    z, _, shifts = draws.draw(self._streams, self.device, r, B,
+                              self.noise_shape[0], False, 2)
     self._bce_forward(st, real, z, shifts)
     dws, pd, pg = st['dws'], st['dis'], st['gen']
     # D chain over 2B: no layer-1 input gradient; every sample has a bias term
@@ -341,14 +321,14 @@ class GAN(object):
     and the Adam step sizes are read from the state's stage buffer."""
     lr_dev = None
     if staged:
-      rand = dict(shifts_dev=True)
       st = self._get_state(real.shape[0])
-      lr_dev = st['stage_dev'][12:].view(torch.float32)
+      shifts, _, _, lr_dev = draws.bce_stage(st['stage_dev'])
+      rand = draws.staged(shifts)
     return [(lambda: self._bce_step(real, rand, lr_dev), None, False)]
 
   def _fill_stage(self, host):
-    host[:12] = self._bce_shifts(None)
-    lr = host[12:].view(torch.float32)
+    shifts, _, _, lr = draws.bce_stage(host)
+    shifts.copy_(draws.shifts(self._streams, None, 2))
     lr[0] = self.dis_optimizer.lr_t(self.dis_optimizer.host_steps + 1)
     lr[1] = self.gen_optimizer.lr_t(self.gen_optimizer.host_steps + 1)
 
@@ -394,12 +374,8 @@ class GAN(object):
     real = self._to_device(inputs)
     B = real.shape[0]
     st = self._get_state(B)
-    if rand is None:
-      z = self.get_noise(B)
-      shifts = self._bce_shifts(None)
-    else:
-      z = self._to_device(rand['z'])
-      shifts = self._bce_shifts(rand)
+    z, _, shifts = draws.draw(self._streams, self.device, rand, B,
+                              self.noise_shape[0], False, 2)
     # (the staged shifts of a captured step are rewritten before each replay)
     fake = self._bce_forward(st, real, z, shifts, training=False, seeds=False)
     metrics = self.metrics(real, fake, fake_pitch=self.generator.net.Cf)

@@ -20,12 +20,15 @@ the discriminator as ONE batch of 3B samples (per-segment phase shifts):
 Generator step (reference :22-36): G forward (activations kept), D forward and
 input-gradient chain on fake, generator backward, Adam, signal metrics.
 """
+import collections
 import os
+import types
 
 import torch
 
 from ... import _lib
 from ... import nets
+from . import draws
 from .gan import GAN, _METRIC_KEYS
 from .registry import register
 
@@ -48,6 +51,11 @@ _FUSE_GP = os.environ.get('CALCIUMGAN_FUSE_GP', '1') != '0'
 # epilogue (cg_dense_rows_interp), one input buffer per update -- instead of an
 # f32 fake batch that n_critic cg_interp_pack launches read back (A/B: =0)
 _FUSE_INTERP = os.environ.get('CALCIUMGAN_FUSE_INTERP', '1') != '0'
+
+# what _generator_pass hands one critic update: the f32 fake batch, or (fake
+# None) the index of the input buffer its output Dense packed [real | fake | x^]
+# into; alpha: the update's interpolation factors when the pass drew them
+_Fed = collections.namedtuple('_Fed', 'fake alpha x0_index')
 
 
 @register('wgan-gp')
@@ -76,20 +84,18 @@ class WGAN_GP(GAN):
     dev = self.device
     dws = self.discriminator.net.workspace(3 * B)
     nc = self.n_critic
-    # host-drawn inputs of a step on the device: [shifts int32 x (12 n + 4) |
-    # Adam step sizes f32 x (n + 1)].  The plans read their PhaseShuffle draws
-    # straight from it (update k: 12 ints at 12 k, the generator update's 4
-    # behind them), so a graph replay needs ONE staged copy and no per-update
-    # copies into the plans
-    stage = torch.zeros(nc * 13 + 5, dtype=torch.int32, device=dev)
+    # host-drawn inputs of a step on the device; the plans read their
+    # PhaseShuffle draws straight from it (draws.critic_stage)
+    stage = torch.zeros(draws.critic_stage_words(nc), dtype=torch.int32,
+                        device=dev)
+    critic_shifts, gen_shifts, _ = draws.critic_stage(stage, nc)
     st = dict(
         gws=self.generator.net.workspace(B),
         dws=dws,
         stage_dev=stage,
         critic=dws.plan(3 * B, B, 2 * B,
-                        shifts=stage[:12].view(4, 3) if nc > 0 else None),
-        gen=dws.plan(B, B, 0, want_norm=False,
-                     shifts=stage[12 * nc:12 * nc + 4].view(4, 1)),
+                        shifts=critic_shifts[0] if nc > 0 else None),
+        gen=dws.plan(B, B, 0, want_norm=False, shifts=gen_shifts),
         norm=torch.zeros(B, dtype=torch.float32, device=dev),
         coef_gp=torch.zeros(B, dtype=torch.float32, device=dev),
         gp=torch.zeros(max(self.n_critic, 1), dtype=torch.float32, device=dev),
@@ -132,7 +138,7 @@ class WGAN_GP(GAN):
       B = st['coef_gp'].shape[0]
       pl = plans[k] = st['dws'].plan(
           3 * B, B, 2 * B, x0_index=k,
-          shifts=st['stage_dev'][12 * k:12 * k + 12].view(4, 3))
+          shifts=draws.critic_stage(st['stage_dev'], self.n_critic)[0][k])
       pl.coef.copy_(st['critic'].coef)
       pl.bias_coef.copy_(st['critic'].bias_coef)
       pl.build_jvp(2, st['coef_gp'])
@@ -235,59 +241,53 @@ class WGAN_GP(GAN):
     own forward): activations stay for GeneratorNet's backward."""
     B = real.shape[0]
     st = self._get_state(B)
-    if r is None or 'shifts_dev' in r:
-      z = self.get_noise(B)
-    else:
-      z = self._to_device(r['z'])
+    z = draws.latents(self._streams, self.device, [r], B, self.noise_shape[0],
+                      alpha=False).z
     return st['gws'].forward(z, keep=keep)
 
-  def _critic_generate_all(self, real, z, n, alphas=None):
-    """G(z) of ALL n critic updates of one train() as one forward-only pass
-    over n * B samples: the generator does not change between them
-    (wgan_gp.py:84-90 updates only the critic), and the small early layers run
-    far better at 5 B.  Returns one (B, L, Cf) view per update -- or, with
-    alphas (f32, n * B: the interpolation factors of all updates), a list of
-    None: the output Dense then writes [real | fake_k | x^_k] into update k's
-    input buffer itself (cg_dense_rows_interp; no f32 fake batch)."""
-    B = real.shape[0]
-    ws = self.generator.net.workspace(n * B, forward_only=True)
-    if alphas is not None:
-      st = self._get_state(B)
+  def _generator_pass(self, real, gws, rs):
+    """ONE forward-only pass of G on workspace `gws` for the k = len(rs)
+    consecutive critic updates whose draws come from `rs`; returns their _Fed
+    records.  k = 1 on st['gws'] is a critic update's own pass; k = n_critic on
+    the forward-only workspace is the batched pass of a single rank: the
+    generator does not change between the updates (wgan_gp.py:84-90), and the
+    small early layers run far better at 5 B.  Where cg_dense_rows_interp applies
+    the output Dense writes [real | fake_j | x^_j] into input buffer x0(j) itself:
+    no f32 fake batch, no cg_interp_pack (x0(0) is free for a per-update pass:
+    every launch of the previous update that read it is ahead on the stream)."""
+    B, k = real.shape[0], len(rs)
+    st = self._get_state(B)
+    fuse = self._can_fuse_interp(B, k, gws)
+    # one draw each for the noise and the interpolation factors of all updates
+    # (i.i.d.: four RNG launches fewer per step).  A per-update pass that does not
+    # fuse leaves alpha to its critic update, behind the all-reduce wait
+    z, alpha, _ = draws.latents(self._streams, self.device, rs, B,
+                                self.noise_shape[0], alpha=fuse or k > 1)
+    part = lambda t, j: None if t is None else t[j * B:(j + 1) * B]
+    if fuse:
       # (plans that form layer 1 of x^ from the other two segments' never read x^)
-      ws.forward(z, keep=False,
-                 interp=(real, None if st['critic'].mixes_layer1 else alphas,
-                         [st['dws'].x0(k) for k in range(n)]))
-      return [None] * n
-    fake = ws.forward(z, keep=False)
-    return [fake[i * B:(i + 1) * B] for i in range(n)]
-
-  def _injected_critic_draws(self, r):
-    """(alpha on the device, host int32 (4, 3) shifts [real | fake | x^]) of the
-    injected draws of one critic update."""
-    return self._to_device(r['alpha']), torch.stack([
-        torch.as_tensor(r[k], dtype=torch.int32)
-        for k in ('shifts_real', 'shifts_fake', 'shifts_inter')], dim=1)
+      gws.forward(z, keep=False,
+                  interp=(real, None if st['critic'].mixes_layer1 else alpha,
+                          [st['dws'].x0(j) for j in range(k)]))
+      return [_Fed(None, part(alpha, j), j) for j in range(k)]
+    fake = gws.forward(z, keep=False)
+    return [_Fed(part(fake, j), part(alpha, j), None) for j in range(k)]
 
   def _critic_compute(self, real, r=None, slot=0, real_cached=False,
                       fake=None, alpha=None, x0_index=None):
     """wgan_gp.py:64-80 up to (not including) the optimizer update: leaves the
-    critic gradients in discriminator.net.params.grad.  alpha: this update's
-    interpolation draws when the caller drew all updates' at once."""
+    critic gradients in discriminator.net.params.grad.  fake, alpha, x0_index:
+    the _Fed record of this update when a generator pass ran ahead of it."""
     B = real.shape[0]
     st = self._get_state(B)
     net_d = self.discriminator.net
     lay = net_d.layers[0]
-    packed = x0_index is not None  # (the step's generator pass packed X0_k)
+    packed = x0_index is not None  # (the generator pass packed X0 itself)
     if fake is None and not packed:
       fake = self._critic_generate(real, r)
-    if r is None:
-      alpha = self._streams.alpha(B) if alpha is None else alpha
-      shifts = self._streams.shifts(3)
-    elif 'shifts_dev' in r:  # graph replay: draws staged in device memory
-      alpha = self._streams.alpha(B) if alpha is None else alpha
-      shifts = r['shifts_dev']
-    else:
-      alpha, shifts = self._injected_critic_draws(r)
+    if alpha is None:
+      alpha = draws.latents(self._streams, self.device, [r], B).alpha
+    shifts = draws.shifts(self._streams, r, 3)
     plan = self._critic_plan(st, x0_index or 0)
     n = lay.lin * lay.cinp
     if plan.jvp_folds:
@@ -336,12 +336,7 @@ class WGAN_GP(GAN):
     plan = st['gen']
     if fake is None:
       fake = self._critic_generate(real, r, keep=True)  # same op: fake = G(z)
-    if r is None:
-      shifts = self._streams.shifts(1)
-    elif 'shifts_dev' in r:
-      shifts = r['shifts_dev']
-    else:
-      shifts = torch.as_tensor(r['shifts'], dtype=torch.int32).reshape(4, 1)
+    shifts = draws.shifts(self._streams, r, 1)
     s = _lib.stream()
     if shifts.data_ptr() != plan.shifts.data_ptr():
       plan.shifts.copy_(shifts, non_blocking=shifts.is_cuda)
@@ -392,127 +387,76 @@ class WGAN_GP(GAN):
     replay): update k reads its shifts from the state's stage buffer (where the
     plans' own shifts are views of it) and its Adam step size behind them."""
     n = self.n_critic
-    st = self._get_state(real.shape[0])
-    lr_dev = None
+    B = real.shape[0]
+    st = self._get_state(B)
+    lr = lambda i: None
     if staged:
-      sd = st['stage_dev']
-      rand = dict(
-          critic=[dict(shifts_dev=sd[12 * i:12 * i + 12].view(4, 3))
-                  for i in range(n)],
-          gen=dict(shifts_dev=sd[12 * n:12 * n + 4].view(4, 1)))
-      lr_dev = sd[12 * n + 4:].view(torch.float32)
-    lr = (lambda i: None) if lr_dev is None else (lambda i: lr_dev[i:])
-    rc = (lambda i: None) if rand is None else (lambda i: rand['critic'][i])
-    rg = None if rand is None else rand['gen']
+      critic_shifts, gen_shifts, lr_dev = draws.critic_stage(st['stage_dev'], n)
+      rand = dict(critic=[draws.staged(v) for v in critic_shifts],
+                  gen=draws.staged(gen_shifts))
+      lr = lambda i: lr_dev[i:]
+    rc, rg = draws.per_update(rand, n)
     d_grad = self.discriminator.net.params.grad
     g_grad = self.generator.net.params.grad
-    box = {}
+    # what the step's closures hand each other: the _Fed record of every critic
+    # update, the generator update's own fake batch, the signal metrics
+    step = types.SimpleNamespace(fed=[None] * n, fake=None, metrics=None)
+    chain = lambda *fns: lambda: [fn() for fn in fns]
 
-    def generate(key, r):
+    def generate(i0, k, gws):
       def run():
-        B = real.shape[0]
-        if key != 'g' and self._can_fuse_interp(B, 1, st['gws']):
-          # a critic update's own generator pass (data parallel, BatchNorm,
-          # CALCIUMGAN_BATCH_G=0): its output Dense writes [real | fake | x^]
-          # into X0 itself (cg_dense_rows_interp, n = 1) -- no f32 fake batch, no
-          # cg_interp_pack.  X0 is free: every launch of the previous update that
-          # read it is ahead of this one on the stream
-          drawn = r is None or 'shifts_dev' in r
-          z = self.get_noise(B) if drawn else self._to_device(r['z'])
-          a = (self._streams.alpha(B) if drawn
-               else self._to_device(r['alpha']).reshape(-1))
-          st['gws'].forward(
-              z, keep=False,
-              interp=(real, None if st['critic'].mixes_layer1 else a,
-                      [st['dws'].x0(0)]))
-          box[key] = None
-          box[('alpha', key)] = a
-          box[('packed', key)] = True
-          return
-        # only the generator update's own forward ('g') is followed by a
-        # backward through G
-        box[key] = self._critic_generate(real, r, keep=key == 'g')
+        step.fed[i0:i0 + k] = self._generator_pass(real, gws, rc[i0:i0 + k])
       return run
 
-    def critic_seg(i, own_g):
+    def critic_seg(i):
       def run():
         if i > 0:
           self._critic_apply(lr(i - 1))
         # the bf16 copy of `real` in X0[0:B] survives a critic step (only the
         # x^ segment is overwritten): converted once per train()
-        self._critic_compute(real, rc(i), slot=i, real_cached=i > 0,
-                             fake=None if own_g else box.pop(i),
-                             alpha=box.pop(('alpha', i), None),
-                             x0_index=(i if box.get('packed') else
-                                       0 if box.pop(('packed', i), False)
-                                       else None))
+        self._critic_compute(real, rc[i], slot=i, real_cached=i > 0,
+                             **step.fed[i]._asdict())
+        step.fed[i] = None
       return run
+
+    def generate_g():
+      # the only forward that is followed by a backward through G
+      step.fake = self._critic_generate(real, rg, keep=True)
 
     def gen_seg():
       if n > 0:
         self._critic_apply(lr(n - 1))
-      self._gen_compute(real, rg, fake=box.pop('g'))
+      self._gen_compute(real, rg, fake=step.fake)
 
     def metrics_seg():
-      box['metrics'] = self._gen_metrics(real)
+      step.metrics = self._gen_metrics(real)
 
     def last_seg():
-      metrics = self._gen_apply(real, lr(n), metrics=box.pop('metrics'))
+      metrics = self._gen_apply(real, lr(n), metrics=step.metrics)
       # (metrics are views of one 4-float buffer: GAN.metrics)
       _lib.call('cg_step_outputs', st['gen_loss'], st['loss'], st['gp'],
                 metrics[_METRIC_KEYS[0]], n, st['out'], _lib.stream())
 
     segs = []
-    def first_seg():
-      generate(0, rc(0))()
-      critic_seg(0, False)()
-
     for i in range(n):
-      if i == 0:
-        segs.append((first_seg, d_grad, False))
-      else:
-        segs.append((generate(i, rc(i)), None, False))
-        segs.append((critic_seg(i, False), d_grad, True))
-    segs.append((generate('g', rg), None, False))
-    segs.append((gen_seg, g_grad, True))
-    segs.append((metrics_seg, None, False))
-    segs.append((last_seg, None, True))
-    if self._sync.world == 1 and not _FORCE_SPLIT:
-      # no collective to cut around: the whole step is one segment (one graph)
-      fns = [fn for fn, _, _ in segs]
-      # (BatchNormalization: the batch statistics are those of ONE update's
-      # fake batch -- no batched pass)
-      if _BATCH_G and n > 1 and not self.generator.net.batch_norm:
-        # ... and no all-reduce for G(z_i) to hide behind: all critic updates'
-        # fake batches come from ONE generator pass at the start of the step
-        def generate_all():
-          B = real.shape[0]
-          rs = [rc(i) for i in range(n)]
-          drawn = rs[0] is None or 'shifts_dev' in rs[0]
-          fuse = self._can_fuse_interp(B, n)
-          # one draw each for the noise and (they are i.i.d. U[0, 1): four RNG
-          # launches fewer per step) the interpolation factors of all updates
-          if drawn:
-            z = self.get_noise(n * B)
-            a = self._streams.alpha(n * B)
-          else:  # injected draws (parity tests)
-            z = torch.cat([self._to_device(r['z']) for r in rs], 0)
-            a = (torch.cat([self._to_device(r['alpha']).reshape(-1) for r in rs])
-                 if fuse else None)
-          fakes = self._critic_generate_all(real, z, n, alphas=a if fuse else None)
-          box['packed'] = fuse
-          for i in range(n):
-            box[i] = fakes[i]
-            if a is not None:
-              box[('alpha', i)] = a[i * B:(i + 1) * B]
-        fns = ([generate_all] + [critic_seg(i, False) for i in range(n)] +
-               [generate('g', rg), gen_seg, metrics_seg, last_seg])
-
-      def run_all():
-        for fn in fns:
-          fn()
-      segs = [(run_all, None, False)]
-    return segs
+      segs += [(generate(i, 1, st['gws']), None, False),
+               (critic_seg(i), d_grad, True)]
+    if n > 0:  # [G(z0) D-step0]: no all-reduce is pending yet
+      segs[:2] = [(chain(segs[0][0], segs[1][0]), d_grad, False)]
+    tail = [(generate_g, None, False), (gen_seg, g_grad, True),
+            (metrics_seg, None, False), (last_seg, None, True)]
+    if self._sync.world > 1 or _FORCE_SPLIT:
+      return segs + tail
+    # no collective to cut around: the whole step is one segment (one graph)
+    # (BatchNormalization: the batch statistics are those of ONE update's
+    # fake batch -- no batched pass)
+    if _BATCH_G and n > 1 and not self.generator.net.batch_norm:
+      # ... and no all-reduce for G(z_i) to hide behind: all critic updates'
+      # fake batches come from ONE generator pass at the start of the step
+      segs = [(generate(0, n, self.generator.net.workspace(
+          n * B, forward_only=True)), None, False)]
+      segs += [(critic_seg(i), d_grad, True) for i in range(n)]
+    return [(chain(*[fn for fn, _, _ in segs + tail]), None, False)]
 
   @property
   def _adam_steps(self):
@@ -521,10 +465,10 @@ class WGAN_GP(GAN):
   def _fill_stage(self, host):
     """[shifts int32 x (12 n + 4) | lr_t f32 x (n + 1)] of the coming step."""
     n = self.n_critic
-    for i in range(n):
-      host[12 * i:12 * i + 12] = self._streams.shifts(3).reshape(-1)
-    host[12 * n:12 * n + 4] = self._streams.shifts(1).reshape(-1)
-    lr = host[12 * n + 4:].view(torch.float32)
+    critic_shifts, gen_shifts, lr = draws.critic_stage(host, n)
+    for view in critic_shifts:
+      view.copy_(self._streams.shifts(3))
+    gen_shifts.copy_(self._streams.shifts(1))
     for i in range(n):
       lr[i] = self.dis_optimizer.lr_t(self.dis_optimizer.host_steps + i + 1)
     lr[n] = self.gen_optimizer.lr_t(self.gen_optimizer.host_steps + 1)
@@ -536,13 +480,8 @@ class WGAN_GP(GAN):
     real = self._to_device(inputs)
     B = real.shape[0]
     st = self._get_state(B)
-    if rand is None:
-      z = self.get_noise(B)
-      alpha = self._streams.alpha(B)
-      shifts = self._streams.shifts(3)
-    else:
-      z = self._to_device(rand['z'])
-      alpha, shifts = self._injected_critic_draws(rand)
+    z, alpha, shifts = draws.draw(self._streams, self.device, rand, B,
+                                  self.noise_shape[0], True, 3)
     fake = self._critic_forward(st, real, z, alpha, shifts, 0, training=False)
     C = self.generator.net.C
     metrics = self.metrics(real, fake, fake_pitch=self.generator.net.Cf)

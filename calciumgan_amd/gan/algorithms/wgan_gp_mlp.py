@@ -27,6 +27,7 @@ penalty's inner gradient included, no dropout, no update.
 import torch
 
 from ... import _lib
+from . import draws
 from .gan import GAN, _METRIC_KEYS
 
 
@@ -83,10 +84,9 @@ class MLP_WGAN_GP(GAN):
     return fake
 
   def _draws(self, B, r, alpha=True):
-    if r is None:
-      return self.get_noise(B), self._streams.alpha(B) if alpha else None
-    return (self._to_device(r['z']),
-            self._to_device(r['alpha']) if alpha else None)
+    """(z, alpha) of one pass: no PhaseShuffle in an MLP pair, so no shifts."""
+    return draws.latents(self._streams, self.device, [r], B,
+                         self.noise_shape[0], alpha)[:2]
 
   def _critic_compute(self, real, r=None, slot=0):
     """wgan_gp.py:64-80 up to the optimizer update: the critic's gradients in
@@ -132,11 +132,11 @@ class MLP_WGAN_GP(GAN):
     st = self._get_state(real.shape[0])
     n = self.n_critic
     self.last_streams = []
+    rc, rg = draws.per_update(rand, n)
     for i in range(n):
-      self._critic_compute(real, None if rand is None else rand['critic'][i],
-                           slot=i)
+      self._critic_compute(real, rc[i], slot=i)
       self.dis_optimizer.update(self.discriminator)
-    fake = self._gen_compute(real, None if rand is None else rand['gen'])
+    fake = self._gen_compute(real, rg)
     self.gen_optimizer.update(self.generator)
     metrics = self._metrics_of(real, fake)
     _lib.call('cg_step_outputs', st['gen_loss'], st['loss'], st['gp'],

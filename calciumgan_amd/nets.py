@@ -952,7 +952,7 @@ class _DisWorkspace(object):
     """Input buffer X0 of critic update k of a step: update 0 uses act[0]; the
     others get their own buffer, so that ONE launch at the start of the step
     (cg_dense_rows_interp) can leave every update's [real | fake_k | x^_k] in
-    place (WGAN_GP._critic_generate_all).  201 MB each at cfg2."""
+    place (WGAN_GP._generator_pass).  201 MB each at cfg2."""
     if k == 0:
       return self.act[0]
     if k not in self._x0_alt:
