@@ -140,6 +140,23 @@ CG_IFFT_FN int ifft_time_of_row(int p, int T, int odd) {
   return u;
 }
 
+// The row that holds time (or bin) u after the last stage: the inverse of
+// ifft_time_of_row.
+CG_IFFT_FN int ifft_row_of_time(int u, int T, int odd) {
+  int p = 0, bits = __builtin_ctz((unsigned)T);
+  if (odd) {
+    bits -= 1;
+    p = (u & 1) << bits;
+    u >>= 1;
+  }
+  while (bits > 0) {
+    bits -= 2;
+    p |= (u & 3) << bits;
+    u >>= 2;
+  }
+  return p;
+}
+
 }  // namespace
 
 #endif  // CG_FFT_STAGES_H_

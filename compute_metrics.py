@@ -14,7 +14,7 @@ the reference's compute_metrics.py (BASELINE configs[3]: recorded-data pipeline
 
   python compute_metrics.py --output_dir runs/001 [--all_epochs]
       [--device gpu [--batch_trials 128]] [--victor_purpura [--vp_q 1.0]]
-      [--temporal_metrics [--max_lag 24]]
+      [--temporal_metrics [--max_lag 24]] [--spectral_metrics]
 
 --device gpu (not a reference flag) takes the deconvolution, the firing rates,
 the per-trial correlations and the van Rossum matrices through the HIP kernels
@@ -48,6 +48,20 @@ cg_spike_ccg and cg_spike_population_hist (csrc/spike_ccg.hip) on the device in
 batches of --batch_trials, the recorded side's kept across epochs; only the
 totals come to the host and both devices write the same dict.
 
+--spectral_metrics (not a reference flag, absent from the namespace unless
+given) adds `spectral`: signals_metrics.spectral_scores of the generated file's
+calcium traces against the validation cache's over the first num_samples trials
+of `signals` in each -- the per-neuron power spectrum (mean removed, Hann
+window) averaged over trials: log-spectral distance, power ratios in total and
+per octave band, the peaks at the periods T / 2, T / 4, ... that stride-2
+transposed convolutions leave, and the spectral centroid.  The only figures of
+the report that look at the traces before deconvolution.  Both come from
+float64 totals: signals_metrics.spectral_totals on the host (a float64
+transform), cg_trace_psd (csrc/trace_psd.hip) on the device in batches of
+--batch_trials (a float32 transform), the recorded side's kept across epochs.
+Unlike `temporal`, the two devices' dicts agree to the rounding of a float32
+transform (about 1e-6 dB), not bit for bit.
+
 The KL is the reference's: both samples cut into 30 equal-width bins over their
 pooled range by pandas.cut, empty bins replaced by 1e-10 (:80-111) -- pandas is
 the same library here, so that step is shared, not restated.  Elephant / Neo /
@@ -67,7 +81,8 @@ from time import time
 import numpy as np
 import pandas as pd
 
-from calciumgan_amd.gan.utils import h5_helper, spike_helper, spike_metrics, utils
+from calciumgan_amd.gan.utils import (h5_helper, signals_metrics, spike_helper,
+                                      spike_metrics, utils)
 
 NUM_BINS = 30  # compute_metrics.py:96
 
@@ -265,6 +280,41 @@ def temporal_report(hparams, filename, totals):
   return scores
 
 
+def _trial_signals(hparams, filename):
+  """The first num_samples trials of `signals` of `filename` as a float32 NWC
+  host array."""
+  signals = utils.set_array_format(
+      np.asarray(h5_helper.get(filename, name='signals')), 'NWC', hparams)
+  return np.asarray(signals[:hparams.num_samples], dtype=np.float32)
+
+
+def spectral_totals_host(hparams, filename):
+  """(signals_metrics.spectral_totals, T) of the trials of `filename`."""
+  signals = _trial_signals(hparams, filename)
+  return signals_metrics.spectral_totals(signals), signals.shape[1]
+
+
+def spectral_report(hparams, filename, totals):
+  """--spectral_metrics: signals_metrics.spectral_scores of `filename` against
+  the validation cache; totals(hparams, filename) -> ((totals, trials), T), the
+  recorded side's kept across epochs."""
+  real = getattr(hparams, '_recorded_spectral_totals', None)
+  if real is None:  # the validation set is the same for every epoch
+    real = hparams._recorded_spectral_totals = totals(hparams,
+                                                      hparams.validation_cache)
+  fake = totals(hparams, filename)
+  if real[1] != fake[1]:
+    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
+                     .format(filename, fake[1], real[1]))
+  scores = signals_metrics.spectral_scores(real[0], fake[0], real[1])
+  if hparams.verbose:
+    for name, label in (('log_spectral_distance_db', 'log-spectral dist.  dB'),
+                        ('log_spectral_rmse_db', 'log-spectral RMSE   dB'),
+                        ('total_power_ratio_db', 'total power ratio   dB')):
+      print('\t{}: {:.04g}'.format(label, scores[name]))
+  return scores
+
+
 def compute_epoch_spike_metrics(hparams, filename, epoch):
   """:483-497 without plot_signals / raster_plots: dict of the statistics."""
   if not h5_helper.contains(filename, 'spikes'):
@@ -298,6 +348,8 @@ def compute_epoch_spike_metrics(hparams, filename, epoch):
       print('\tVictor-Purpura     KL mean: {:.04f}'.format(np.mean(kl)))
   if getattr(hparams, 'temporal_metrics', False):
     out['temporal'] = temporal_report(hparams, filename, temporal_totals_host)
+  if getattr(hparams, 'spectral_metrics', False):
+    out['spectral'] = spectral_report(hparams, filename, spectral_totals_host)
   return out
 
 
@@ -477,6 +529,18 @@ def temporal_totals_device(hparams, filename):
   return (ccg.cpu().numpy(), hist.cpu().numpy(), len(spikes)), spikes.shape[1]
 
 
+def spectral_totals_device(hparams, filename):
+  """`spectral_totals_host` through cg_trace_psd, a batch of trials at a time;
+  the float64 totals summed on the device in batch order and brought to the
+  host once."""
+  signals = _trial_signals(hparams, filename)
+  totals = None
+  for batch in _batches(hparams, signals):
+    part, _ = signals_metrics.spectral_totals_device(batch)
+    totals = part if totals is None else totals + part
+  return (totals.cpu().numpy(), len(signals)), signals.shape[1]
+
+
 def compute_epoch_spike_metrics_device(hparams, filename, epoch):
   """`compute_epoch_spike_metrics` with the statistics from the device; the
   histograms behind the KL from cg_pair_histogram (`device_kl`) unless
@@ -515,6 +579,8 @@ def compute_epoch_spike_metrics_device(hparams, filename, epoch):
       print('\tVictor-Purpura     KL mean: {:.04f}'.format(np.mean(kl)))
   if getattr(hparams, 'temporal_metrics', False):
     out['temporal'] = temporal_report(hparams, filename, temporal_totals_device)
+  if getattr(hparams, 'spectral_metrics', False):
+    out['spectral'] = spectral_report(hparams, filename, spectral_totals_device)
   return out
 
 
@@ -595,6 +661,11 @@ def build_parser():
   parser.add_argument('--max_lag', type=int, default=argparse.SUPPRESS,
                       help='--temporal_metrics: largest lag in frames '
                       '(default 24, at most 256)')
+  # (absent unless given, like --victor_purpura)
+  parser.add_argument('--spectral_metrics', action='store_true',
+                      default=argparse.SUPPRESS,
+                      help='also report `spectral`: power-spectrum figures of '
+                      'the generated against the recorded calcium traces')
   return parser
 
 

@@ -920,6 +920,44 @@ int cg_ifft_channels(const float* x, int B, int T, int C,
                      void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Power spectra of calcium traces (trace_psd.hip; compute_metrics.py
+ * --spectral_metrics: not in the reference, whose reports look at the traces
+ * only after deconvolution).  Added under ABI 20; the same float32 / float64
+ * code in both precision builds.
+ * ------------------------------------------------------------------------- */
+/* Periodogram of every neuron of a (B, T, C) float32 batch, summed over the
+ * trials (the numpy statement is signals_metrics.trace_power_spectrum):
+ *   m = float32(sum_t float64(x_t) / T)
+ *   w_t = float32(0.5 - 0.5 cospi(2 t / T))            (periodic Hann)
+ *   y_t = (x_t - m) w_t, the difference and the product each rounded to float32
+ *   totals[k * C + c] = sum_b |sum_t y_t e^{-2 pi i k t / T}|^2,  k = 0 .. T / 2
+ * x_t = x[b * s_b + t * s_t + c * s_c], strides in elements, any values (a
+ * stored (B, C, T) array viewed (B, T, C) and a padded channel pitch are read in
+ * place), every element read once.  totals is float64 (T / 2 + 1, C),
+ * contiguous and un-normalised: divide by B sum_t w_t^2 = B 3 T / 8 for a
+ * spectrum in which white noise of variance s^2 has the level s^2.
+ * The transform is float32 (the stages of cg_ifft_channels, two neurons packed
+ * into one complex trace: a neuron's error is relative to the larger norm of
+ * its pair); |.|^2 and every sum over trials are float64.  A neuron with a
+ * non-finite sample in any trial has NaN in all its totals and changes no other
+ * neuron's bits: zeros are transformed in place of such a trace.  A constant
+ * trace gives exact zeros.
+ * Two launches on `stream`: one workgroup per (group of 2 min(16, 8192 / T)
+ * neurons, chunk of consecutive trials) up to 1024, grid-stride beyond, writes
+ * float64 partial sums [chunks][T / 2 + 1][C] to ws; the second adds the chunks
+ * in index order.  The chunking depends on (B, T, C) alone and every partial
+ * element is written: nothing has to be zeroed, no atomics, no host sync, the
+ * same bits every call.  Only the (T / 2 + 1) C elements of totals are written.
+ * cg_trace_psd_ws_bytes: bytes of `ws` (8-byte aligned; contents do not
+ * matter), -1 for arguments cg_trace_psd refuses.
+ * CG_EINVAL (nothing launched): a NULL x, totals or ws, ws not 8-byte aligned,
+ * B or C < 1, T not a power of two or outside 32 .. 8192. */
+long long cg_trace_psd_ws_bytes(int B, int T, int C);
+int cg_trace_psd(const float* x, int B, int T, int C,
+                 long long s_b, long long s_t, long long s_c,
+                 double* totals, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Recording datasets (windows.hip; the reference's generate_tfrecords.py cuts a
  * (neurons, T) recording into overlapping stride-2 windows and writes each one
  * out; here the recording stays resident and every step's windows are cut
