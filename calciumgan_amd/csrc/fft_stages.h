@@ -157,6 +157,10 @@ CG_IFFT_FN int ifft_row_of_time(int u, int T, int odd) {
   return p;
 }
 
+// the j-th row whose bin is below T / 2 (trace_psd.hip): bit 1 of the row is
+// the top bit of its bin (the last radix-4 digit)
+CG_IFFT_FN int psd_low_row(int j) { return ((j >> 1) << 2) | (j & 1); }
+
 }  // namespace
 
 #endif  // CG_FFT_STAGES_H_

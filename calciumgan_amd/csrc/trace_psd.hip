@@ -90,10 +90,6 @@ __device__ __forceinline__ float psd_window(float x, float m, float w) {
   return a;
 }
 
-// the j-th row whose bin is below T / 2: bit 1 of the row is the top bit of its
-// bin (the last radix-4 digit)
-CG_IFFT_FN int psd_low_row(int j) { return ((j >> 1) << 2) | (j & 1); }
-
 struct PsdArgs {
   const float* x;
   long long s_b, s_t, s_c;

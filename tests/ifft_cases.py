@@ -3,11 +3,14 @@ tests/test_hip_ifft.py): seeded (B, T, 2C) float32 spectra in the [real | imag]
 layout of utils.fft_channels, as numpy arrays, with the memory layout the device
 test gives them, and the two error figures every case is held to.
 
-Shapes are the smallest at which each mechanism of csrc/ifft.hip can break: T in
-{32, 64, 256, 2048, 8192} (fewest stages / the radix-2 stage of an odd log2 T,
-an even number of radix-4 stages, the cfg2 length, the LDS limit); C in {1, 3,
-G + 1, 102} for the kernel's neurons per workgroup G = min(16, 8192 / T) (ragged
-groups); B x groups past one pass of the 1024-workgroup grid."""
+Shapes are the smallest at which each mechanism of csrc/ifft.hip can break:
+every accepted T, 32 .. 8192 (fewest stages / the radix-2 stage of an odd log2
+T, an even number of radix-4 stages, the radix-2 stage on a quarter-full image
+at 128 and on the first full one at 512, the cfg2 length, the LDS limit), which
+is every geometry G = min(16, 8192 / T) in {16, 8, 4, 2, 1} with its row swizzle
+rows_mask = 32 / G - 1; C in {1, 3, G + 1, 102} (ragged groups); B x groups a
+multiple of 8 below the 1024-workgroup grid (the renumbered walk of the items),
+no multiple of 8, and past one pass of the grid."""
 import functools
 
 import numpy as np
@@ -68,6 +71,9 @@ _TABLE = {
                   'contig', 'contig'),
     't64_c5_permuted': (lambda: _normal(3, 64, 5, 4), 5, 1.0, 0.0, 'permuted',
                         'contig'),
+    't128_c17_normal': (lambda: _normal(2, 128, 17, 16), 17, 1.0, 0.0, 'contig',
+                        'contig'),
+    't128_bins': (lambda: _bins(128), 2, 1.0, 0.0, 'contig', 'contig'),
     't256_c8_dg': (lambda: _dg(2, 256, 8, 5), 8, 1.0, 0.0, 'contig', 'contig'),
     't256_c8_dg_affine': (lambda: _dg(2, 256, 8, 5), 8, 0.37, -1.25, 'contig',
                           'contig'),
@@ -80,11 +86,29 @@ _TABLE = {
                            'padded'),
     't256_c4_zero_trace': (lambda: _zero_trace(2, 256, 4, 9), 4, 1.0, 0.0,
                            'contig', 'contig'),
+    't512_c17_dg': (lambda: _dg(2, 512, 17, 17), 17, 1.0, 0.0, 'contig',
+                    'contig'),
+    't512_bins': (lambda: _bins(512), 2, 1.0, 0.0, 'contig', 'contig'),
+    # G = 8: C = G + 1
+    't1024_c9_normal': (lambda: _normal(2, 1024, 9, 18), 9, 1.0, 0.0, 'contig',
+                        'contig'),
+    't1024_bins': (lambda: _bins(1024), 2, 1.0, 0.0, 'contig', 'contig'),
+    # 3 samples x 8 groups = 24 items: a multiple of 8 below the grid cap
+    't1024_c64_renumbered': (lambda: _normal(3, 1024, 64, 19), 64, 1.0, 0.0,
+                             'contig', 'contig'),
+    't1024_c5_permuted': (lambda: _normal(3, 1024, 5, 20), 5, 1.0, 0.0,
+                          'permuted', 'padded'),
     't2048_c102_dg': (lambda: _dg(2, 2048, 102, 10), 102, 1.0, 0.0, 'contig',
                       'contig'),
     't2048_c5_normal': (lambda: _normal(2, 2048, 5, 11), 5, 1.0, 0.0, 'contig',
                         'contig'),
     't2048_bins': (lambda: _bins(2048), 2, 1.0, 0.0, 'contig', 'contig'),
+    # G = 2: C = G + 1
+    't4096_c3_dg': (lambda: _dg(2, 4096, 3, 21), 3, 1.0, 0.0, 'contig',
+                    'contig'),
+    't4096_bins': (lambda: _bins(4096), 2, 1.0, 0.0, 'contig', 'contig'),
+    't4096_c2_affine': (lambda: _dg(2, 4096, 2, 22), 2, 0.37, -1.25, 'contig',
+                        'contig'),
     't8192_c1_dg': (lambda: _dg(2, 8192, 1, 12), 1, 1.0, 0.0, 'contig',
                     'contig'),
     't8192_c2_normal': (lambda: _normal(2, 8192, 2, 13), 2, 1.0, 0.0, 'contig',
@@ -95,6 +119,12 @@ _TABLE = {
                             'contig', 'contig'),
 }
 CASES = tuple(_TABLE)
+
+
+def items(name):
+  """Workgroup items of csrc/ifft.hip for the case: samples x neuron groups."""
+  x, C = case(name)[:2]
+  return x.shape[0] * (-(-C // group(x.shape[1])))
 
 
 @functools.lru_cache(maxsize=None)

@@ -129,13 +129,28 @@ def test_the_case_table_meets_its_own_conditions_with_the_statement():
 def test_the_cases_cover_the_mechanisms():
   cases = {n: ifft_cases.case(n) for n in ifft_cases.CASES}
   Ts = {c[0].shape[1] for c in cases.values()}
-  assert Ts == {32, 64, 256, 2048, 8192}
+  assert Ts == {32, 64, 128, 256, 512, 1024, 2048, 4096, 8192}
+  assert {ifft_cases.group(T) for T in Ts} == {16, 8, 4, 2, 1}
   for T in Ts:
+    G = ifft_cases.group(T)
     Cs = {c[1] for c in cases.values() if c[0].shape[1] == T}
-    assert ifft_cases.group(T) + 1 in Cs, T      # a ragged second group
+    assert G + 1 in Cs, T      # a ragged second group
+    if T in (128, 512, 1024, 4096):
+      assert 't%d_bins' % T in cases
+  for G in (8, 4, 2):          # a last group that is not full
+    assert any(ifft_cases.group(c[0].shape[1]) == G and c[1] > G and c[1] % G
+               for c in cases.values()), G
   x, C = cases['t32_c17_grid_stride'][:2]
   groups = -(-C // ifft_cases.group(32))
   assert x.shape[0] * groups > ifft_cases.MAX_GRID
+  # the walk of the items: renumbered when the grid (the item count, below the
+  # cap) is a multiple of 8, as they come otherwise
+  items = {n: ifft_cases.items(n) for n in cases}
+  assert items['t1024_c64_renumbered'] == 24
+  assert any(i % 8 == 0 and i < ifft_cases.MAX_GRID for i in items.values())
+  assert any(i % 8 and i < ifft_cases.MAX_GRID for i in items.values())
+  assert cases['t1024_c5_permuted'][4:] == ('permuted', 'padded')
+  assert cases['t4096_c2_affine'][2:4] == (0.37, -1.25)
   assert cases['t2048_c102_dg'][0].shape == (2, 2048, 204)
   assert {c[4] for c in cases.values()} == {'contig', 'padded', 'permuted'}
   assert {c[5] for c in cases.values()} == {'contig', 'padded'}

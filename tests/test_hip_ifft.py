@@ -87,6 +87,22 @@ def test_against_the_float64_transform(name):
   assert dev.cpu().numpy().tobytes() == got.tobytes()
 
 
+@pytest.mark.parametrize('name', ['t128_c17_normal', 't512_c17_dg',
+                                  't1024_c64_renumbered', 't4096_c3_dg'])
+def test_the_f16_library_holds_the_same_kernel(name):
+  """The float32 kernel of the other precision build, at the lengths the case
+  table gained: under both conditions, and the bf16 build's bits."""
+  x = _input(name)
+  want = _launch(name, x)[0].cpu().numpy()
+  _lib.use('f16')
+  try:
+    got = _launch(name, x)[0].cpu().numpy()
+  finally:
+    _lib.use('bf16')
+  IC.check_accuracy(got, name)
+  assert got.tobytes() == want.tobytes()
+
+
 def test_other_lengths_take_the_host_statement():
   rng = np.random.RandomState(5)
   x = rng.standard_normal((2, 96, 6)).astype(np.float32)

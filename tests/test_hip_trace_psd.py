@@ -8,7 +8,11 @@ compute_metrics.py --spectral_metrics on both devices.
 
 Measured on one MI355X: profiles/trace_psd_parity.txt (the worst e1 of a case
 1.5e-8 .. 2.7e-7, 0.6 .. 1.2 times that of single-precision pocketfft; 3.9
-times on the pure tones at T = 2048, which pocketfft transforms to 3.9e-9)."""
+times on the pure tones at T = 2048, which pocketfft transforms to 3.9e-9) and,
+for the cases of T = 128, 512, 1024 and 4096, the tones up to 8192 and the chunk
+plan at its cap, profiles/fft_lengths_parity.txt (4.2e-8 .. 1.07e-7, 0.82 .. 1.04
+times pocketfft's; on the tones 1.00 times up to T = 1024, 1.70 at 4096 and 10.2
+at 8192, the one result held to bar (a) only)."""
 import os
 
 import numpy as np
@@ -94,6 +98,22 @@ def test_against_the_float64_statement(name):
   PC.check_accuracy(sm.trace_power_spectrum(x_host), name, what='numpy')
 
 
+@pytest.mark.parametrize('name', ['t128_c33_normal', 't512_c5_dg',
+                                  't1024_c17_normal', 't4096_c5_normal'])
+def test_the_f16_library_holds_the_same_kernel(name):
+  """The kernel of the other precision build, at the lengths the case table
+  gained: under both bars, and the bf16 build's bits."""
+  x = _view(*PC.case(name))
+  want = _launch(x)
+  _lib.use('f16')
+  try:
+    got = _launch(x)
+  finally:
+    _lib.use('bf16')
+  PC.check_accuracy(got, name, what='f16')
+  assert got.tobytes() == want.tobytes()
+
+
 def test_the_case_table_reaches_every_path():
   shapes = {n: PC.case(n)[0].shape for n in PC.CASES}
   assert PC.plan(*shapes['t64_c3_three_chunks'])[1:] == (4, 3)
@@ -101,9 +121,30 @@ def test_the_case_table_reaches_every_path():
   assert groups * chunks > PC.MAX_GRID
   assert shapes['t32_c33_normal'][2] == 2 * PC.group(32) + 1
   assert PC.group(8192) == 1 and PC.group(2048) == 4
+  # every accepted length, so every geometry, each with a ragged last group
+  assert {s[1] for s in shapes.values()} == {32 << i for i in range(9)}
+  assert {PC.group(s[1]) for s in shapes.values()} == {16, 8, 4, 2, 1}
+  for T in (32, 128, 1024, 2048, 4096, 8192):   # 2 G + 1 neurons
+    assert any(s[1] == T and s[2] == 2 * PC.group(T) + 1
+               for s in shapes.values()), T
+  assert shapes['t512_c5_dg'][1:] == (512, 5)
+  assert shapes['t4096_c1_dg'][2] == 1
+  # both walks of the items under the grid cap, and the grid-stride one
+  items = {n: PC.items(n) for n in PC.CASES}
+  assert items['t1024_c128_renumbered'] == 8
+  assert any(i % 8 for i in items.values())
+  assert any(i % 8 == 0 and i < PC.MAX_GRID for i in items.values())
+  # the chunk plan at its cap and past it, each with a last chunk of one trial
+  assert PC.plan(*shapes['t32_c3_64_chunks']) == (1, 4, PC.MAX_CHUNKS)
+  assert shapes['t32_c3_64_chunks'][0] == 63 * 4 + 1
+  assert PC.plan(*shapes['t32_c3_chunks_of_5']) == (1, 5, 61)
+  assert shapes['t32_c3_chunks_of_5'][0] == 60 * 5 + 1
+  # bar (b) is left out only where the case table's docstring says why
+  assert {n for n, w in PC.BAR_A_ONLY.items() if 'device' in w} == {
+      't8192_tones'}
 
 
-@pytest.mark.parametrize('T', [32, 64, 2048])
+@pytest.mark.parametrize('T', [32, 64, 128, 512, 1024, 2048, 4096, 8192])
 def test_tones_sit_at_their_own_bins(T):
   """Neuron 0 holds bins 1 and T / 2 - 1, its partner T / 4 + 1 and T / 2: each
   has its tones' power at its own bins and none at the partner's, the isolated
@@ -136,7 +177,8 @@ def test_a_constant_trace_gives_exact_zeros_beside_a_live_partner():
   PC.check_accuracy(got, 't256_c5_normal', x=x)
 
 
-@pytest.mark.parametrize('name', ['t64_c3_three_chunks', 't2048_c9_dg'])
+@pytest.mark.parametrize('name', ['t64_c3_three_chunks', 't2048_c9_dg',
+                                  't1024_c17_normal'])
 def test_a_nan_and_an_inf_stay_in_their_own_neuron(name):
   """Neuron 1 (partner: neuron 0) has a NaN in one trial and an Inf in another:
   it is all NaN, every neuron of another pair keeps its bits, and its partner
@@ -159,6 +201,33 @@ def test_a_nan_and_an_inf_stay_in_their_own_neuron(name):
   PC.check_accuracy(np.delete(got, 1, axis=1), name, x=np.delete(clean, 1, axis=2))
   want = sm.trace_power_spectrum(dirty)
   assert np.isnan(want[:, 1]).all() and np.isfinite(np.delete(want, 1, 1)).all()
+
+
+def test_a_nan_does_not_reach_the_next_item_of_its_workgroup():
+  """1025 items on 1024 workgroups: workgroup 0 takes item 0 (neurons 0 .. 31)
+  and then item 1024 (neuron 32768), and clears its bad[] flags in between.  A
+  NaN in neuron 0 makes neuron 0 all NaN and nothing else: neuron 32768 -- the
+  same flag slot of the same workgroup, one item later -- and every neuron of
+  another pair keep the bits of the run without the NaN.  Neuron 1, packed
+  into one transform with neuron 0, holds the bits it has beside a zero trace
+  (zeros are transformed in the NaN trace's place), as in the test above."""
+  name = 't32_c32769_grid_stride'
+  clean = np.array(PC.case(name)[0])
+  B, T, C = clean.shape
+  groups, _, chunks = PC.plan(B, T, C)
+  assert (B, chunks, groups) == (1, 1, PC.MAX_GRID + 1)
+  last = C - 1
+  assert last // (2 * PC.group(T)) == PC.MAX_GRID   # item 1024: workgroup 0 again
+  dirty = clean.copy()
+  dirty[0, 7, 0] = np.nan
+  blank = clean.copy()
+  blank[0, :, 0] = 0.0
+  got, base, ref = _totals(dirty), _totals(clean), _totals(blank)
+  assert np.isnan(got[:, 0]).all()
+  assert np.isfinite(got[:, last]).all()
+  assert np.isfinite(got[:, 1:]).all() and np.isfinite(base).all()
+  assert got[:, 2:].tobytes() == base[:, 2:].tobytes()
+  assert got[:, 1].tobytes() == ref[:, 1].tobytes()
 
 
 def test_totals_in_groups_equal_the_single_call():

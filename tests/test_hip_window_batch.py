@@ -124,6 +124,22 @@ def test_the_spectra_against_the_float64_transform(name):
         norm.tobytes()
 
 
+@pytest.mark.parametrize('name', ['l128_c17_normal', 'l512_c17_dg',
+                                  'l1024_c17_dg', 'l4096_c3_dg'])
+def test_the_f16_library_holds_the_same_kernel(name):
+  """The float32 FFT kernel of the other precision build, at the lengths the
+  case table gained: under both conditions, and the bf16 build's bits."""
+  raw = _raw(name)
+  want = _launch(name, raw, True, sub=0.0, div=1.0)[0].cpu().numpy()
+  _lib.use('f16')
+  try:
+    got = _launch(name, raw, True, sub=0.0, div=1.0)[0].cpu().numpy()
+  finally:
+    _lib.use('bf16')
+  WC.check_accuracy(got, name)
+  assert got.tobytes() == want.tobytes()
+
+
 def test_invalid_arguments_are_refused_and_nothing_is_written():
   raw = torch.zeros((200, 3), device=DEV)
   starts = torch.zeros(2, dtype=torch.int32, device=DEV)

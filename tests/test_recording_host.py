@@ -71,9 +71,23 @@ def test_the_cases_cover_the_mechanisms():
   cases = {n: WC.case(n) for n in WC.CASES}
   fft = {n: cases[n] for n in WC.FFT_CASES}
   Ls = {c['L'] for c in fft.values()}
-  assert Ls == {32, 64, 256, 2048, 8192}
+  assert Ls == {32, 64, 128, 256, 512, 1024, 2048, 4096, 8192}
+  assert {WC.group(L) for L in Ls} == {16, 8, 4, 2, 1}
   for L in Ls:
     assert WC.group(L) + 1 in {c['C'] for c in fft.values() if c['L'] == L}, L
+    if L in (128, 512, 1024, 4096):
+      assert 'l%d_impulses' % L in fft
+  for G in (8, 4, 2):          # a last group that is not full
+    assert any(WC.group(c['L']) == G and c['C'] > G and c['C'] % G
+               for c in fft.values()), G
+  # the walk of the FFT kernel's items: renumbered when the grid (the item
+  # count, below the cap) is a multiple of 8, as they come otherwise
+  items = {n: WC.fft_items(n) for n in fft}
+  assert items['l1024_c17_dg'] == 24
+  assert any(i % 8 == 0 and i < WC.FFT_MAX_GRID for i in items.values())
+  assert any(i % 8 and i < WC.FFT_MAX_GRID for i in items.values())
+  assert cases['l1024_c5_transposed']['lin'] == 'transposed'
+  assert cases['l4096_c2_normal']['lout'] == 'padded'
   assert {1, 3, 102} <= {c['C'] for c in fft.values()}
   c = cases['l32_c17_grid_stride']
   assert len(c['starts']) * -(-17 // WC.group(32)) > WC.FFT_MAX_GRID

@@ -12,6 +12,7 @@ y_t is within 3 u |y_t| of the exact one, so every X_k is within 3 u T of its
 exact value -- 9 u^2 T^2 = 3.2e-14 T^2 where the exact bin is empty (measured:
 5e-17 T^2), 25 u relative at the peak (|X| = T / 4) and 50 u beside it."""
 import json
+import os
 import re
 
 import numpy as np
@@ -22,6 +23,7 @@ import trace_psd_cases as PC
 from calciumgan_amd import _lib
 from calciumgan_amd.gan.utils import signals_metrics as sm
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24
 PLAIN_KEYS = {'firing_rate_kl', 'correlation_kl', 'van_rossum_kl',
               'van_rossum_heatmap_min', 'elapse'}
@@ -121,6 +123,50 @@ def test_the_case_table_reaches_every_path():
   groups, _, chunks = PC.plan(*shapes['t32_c32769_grid_stride'])
   assert groups * chunks > PC.MAX_GRID
   assert PC.plan(128, 2048, 102) == (13, 4, 32)
+  # every accepted length: every G, and for each a ragged last group (2 G + 1
+  # neurons: a second group of one neuron whose partner is absent)
+  Ts = {s[1] for s in shapes.values()}
+  assert Ts == {32, 64, 128, 256, 512, 1024, 2048, 4096, 8192}
+  assert {PC.group(T) for T in Ts} == {16, 8, 4, 2, 1}
+  for G in (16, 8, 4, 2, 1):
+    assert any(PC.group(s[1]) == G and s[2] == 2 * G + 1
+               for s in shapes.values()), G
+  for T in (128, 512, 1024, 4096):
+    assert any(s[1] == T and s[2] % (2 * PC.group(T)) for s in shapes.values()), T
+    assert 't%d_tones' % T in shapes
+  assert shapes['t4096_c1_dg'][1:] == (4096, 1)
+  # the walk of the items: renumbered when the grid (the item count, below the
+  # cap) is a multiple of 8, as they come otherwise, grid-stride past the cap
+  items = {n: PC.items(n) for n in PC.CASES}
+  assert items['t1024_c128_renumbered'] == 8
+  assert any(i % 8 == 0 and i < PC.MAX_GRID for i in items.values())
+  assert any(i % 8 and i < PC.MAX_GRID for i in items.values())
+  # the chunk plan at its cap of 64 chunks and past it (chunks of 5), each with
+  # a last chunk of one trial
+  assert PC.plan(*shapes['t32_c3_64_chunks']) == (1, 4, 64)
+  assert shapes['t32_c3_64_chunks'][0] - 63 * 4 == 1
+  assert PC.plan(*shapes['t32_c3_chunks_of_5']) == (1, 5, 61)
+  assert shapes['t32_c3_chunks_of_5'][0] - 60 * 5 == 1
+  assert PC.MAX_CHUNKS == 64
+  src = open(os.path.join(ROOT, 'calciumgan_amd', 'csrc', 'trace_psd.hip')).read()
+  for text in ('kPsdMaxGrid = %d;' % PC.MAX_GRID, 'kPsdMaxChunks = %d;' %
+               PC.MAX_CHUNKS, 'kPsdMinChunk = %d;' % PC.MIN_CHUNK,
+               'kPsdTargetItems = %d;' % PC.TARGET_ITEMS):
+    assert text in src, text
+  # bar (b) is left out only where trace_psd_cases' docstring says why: of the
+  # device's totals on the tones at 8192, of the numpy statement's at 512 and
+  # 1024
+  assert PC.BAR_A_ONLY == {'t512_tones': {'numpy'}, 't1024_tones': {'numpy'},
+                           't8192_tones': {'device'}}
+
+
+def test_the_statement_on_every_tones_case():
+  """The module's numpy statement (float32 y, float64 transform) under bar (a)
+  on every tones case, and under bar (b) wherever the table holds it to both."""
+  for name in PC.CASES:
+    if name.endswith('_tones'):
+      PC.check_accuracy(sm.trace_power_spectrum(PC.case(name)[0]), name,
+                        what='numpy')
 
 
 # -- spectral_scores -----------------------------------------------------------

@@ -4,13 +4,19 @@ arrays, the start rows of a batch of windows, the memory layouts the device test
 gives the recording and the output, and the error figures an FFT case is held to.
 
 Shapes are the smallest at which each mechanism of csrc/windows.hip can break:
-  L and G       L in {32, 64, 256, 2048, 8192} (fewest stages / the radix-2 stage
-                of an odd log2 L, an even number of radix-4 stages, the cfg2
-                length, the LDS limit); C in {1, 3, G + 1, 102} for the FFT
-                kernel's neurons per workgroup G = min(16, 8192 / L) (ragged
-                groups); the 8192-point cases have B = 2 or 3
+  L and G       every accepted L, 32 .. 8192 (fewest stages / the radix-2 stage
+                of an odd log2 L, an even number of radix-4 stages, the radix-2
+                stage on a quarter-full image at 128 and on the first full one
+                at 512, the cfg2 length, the LDS limit): every geometry of the
+                FFT kernel, G = min(16, 8192 / L) in {16, 8, 4, 2, 1} neurons
+                per workgroup with its swizzle rows_mask = 32 / G - 1; C in {1,
+                3, G + 1, 102} (ragged groups); the 8192-point cases have B = 2
+                or 3
   grid stride   FFT: L 32, C 17, B 600: 1200 workgroups' worth > 1024; plain:
                 L 64, C 65, B 600: 3000 items of 1024 elements > 2048 workgroups
+  renumbering   FFT items = B x groups: the 8 edge starts make it a multiple of
+                8 below the grid (the renumbered walk; 24 items at L 1024, C
+                17), the 3 impulse starts do not
   starts        0; odd starts; overlapping windows; the same start twice; the
                 last valid start T - L; one start beyond it and one negative
                 (edge rows repeat)
@@ -104,6 +110,9 @@ _TABLE = {
     'l64_c65_plain_grid_stride': _case(
         64, 65, lambda: _normal(300, 65, 10),
         lambda T, L: _many_starts(T, L, 600, 11), fft=False),
+    'l128_c17_normal': _case(128, 17, lambda: _normal(200, 17, 23)),
+    'l128_impulses': _case(128, 2, lambda: _impulses(128),
+                           lambda T, L: np.array([0, L, 2 * L], np.int32)),
     'l256_c8_dg': _case(256, 8, lambda: _dg(300, 8, 12)),
     'l256_c8_dg_affine': _case(256, 8, lambda: _dg(300, 8, 12), sub=-1.25,
                                div=3.7),
@@ -117,10 +126,26 @@ _TABLE = {
     'l256_c8_padded4_out': _case(256, 8, lambda: _normal(300, 8, 17),
                                  lout='padded4'),
     'l256_c4_zero_trace': _case(256, 4, lambda: _zero_trace(300, 4, 18)),
+    'l512_c17_dg': _case(512, 17, lambda: _dg(580, 17, 24)),
+    'l512_impulses': _case(512, 2, lambda: _impulses(512),
+                           lambda T, L: np.array([0, L, 2 * L], np.int32)),
+    # G = 8: C = G + 1; 8 starts x 3 groups = 24 items at C = 17
+    'l1024_c9_normal': _case(1024, 9, lambda: _normal(1094, 9, 25)),
+    'l1024_c17_dg': _case(1024, 17, lambda: _dg(1094, 17, 26)),
+    'l1024_impulses': _case(1024, 2, lambda: _impulses(1024),
+                            lambda T, L: np.array([0, L, 2 * L], np.int32)),
+    'l1024_c5_transposed': _case(1024, 5, lambda: _normal(1094, 5, 27),
+                                 lin='transposed'),
     'l2048_c102_dg': _case(2048, 102, lambda: _dg(2100, 102, 19)),
     'l2048_c5_normal': _case(2048, 5, lambda: _normal(2100, 5, 20)),
     'l2048_impulses': _case(2048, 2, lambda: _impulses(2048),
                             lambda T, L: np.array([0, L, 2 * L], np.int32)),
+    # G = 2: C = G + 1
+    'l4096_c3_dg': _case(4096, 3, lambda: _dg(4166, 3, 28)),
+    'l4096_impulses': _case(4096, 2, lambda: _impulses(4096),
+                            lambda T, L: np.array([0, L, 2 * L], np.int32)),
+    'l4096_c2_normal': _case(4096, 2, lambda: _normal(4166, 2, 29),
+                             lout='padded'),
     'l8192_c1_dg': _case(8192, 1, lambda: _dg(8260, 1, 21),
                          lambda T, L: np.array([1, T - L + 5], np.int32)),
     'l8192_c2_normal': _case(8192, 2, lambda: _normal(8260, 2, 22),
@@ -130,6 +155,12 @@ _TABLE = {
 }
 CASES = tuple(_TABLE)
 FFT_CASES = tuple(n for n in CASES if _TABLE[n]['fft'])
+
+
+def fft_items(name):
+  """Workgroup items of the FFT kernel for the case: windows x neuron groups."""
+  c = case(name)
+  return len(c['starts']) * (-(-c['C'] // group(c['L'])))
 
 
 @functools.lru_cache(maxsize=None)
