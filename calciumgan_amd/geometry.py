@@ -71,6 +71,47 @@ def lds_bytes(CK, stride, taps, Lu, TM, TN=64, mfma_rows=16,
   return round_up(a, 16) + _LDS_B * (TN // 64)
 
 
+CK_TARGET = {1: 32, 2: 32}  # preferred channel chunk per source stride
+
+
+def channel_chunk(Cx, stride, taps, Lu):
+  """Channel chunk of a packed operand: a divisor of the pitch, multiple of 8,
+  >= 32, valid for both row tiles the launcher may pick.  Preference: the chunk
+  that keeps one workgroup's LDS under half the CU (two resident workgroups
+  hide each other's staging): 32.  ValueError where no chunk's windows fit LDS
+  even on the 64-row tile."""
+  cands = [d for d in range(32, Cx + 1, 8) if Cx % d == 0]
+  tgt = CK_TARGET[stride]
+  pref = sorted(cands, key=lambda d: (d > tgt, abs(d - tgt)))
+  tms = [tm for tm in (256, 64)
+         if ((Lu % tm == 0) if Lu >= tm else (tm % Lu == 0))]
+  if not tms:
+    raise ValueError('unsupported per-sample length {}'.format(Lu))
+  for d in pref:
+    if all(lds_bytes(d, stride, taps, Lu, tm) <= LDS_BYTES for tm in tms):
+      return d
+  # fall back to the small tile only
+  for d in pref:
+    if lds_bytes(d, stride, taps, Lu, 64) <= LDS_BYTES:
+      return d
+  raise ValueError('no channel chunk fits LDS (Cx={}, taps={})'.format(Cx, taps))
+
+
+def stride2_launches(hp):
+  """(network, layer number, Cx, stride, taps, Lu) of the stride-2 'down' launch
+  and the two-phase 'up' launch of every layer of both networks: what
+  nets.Stride2Layer asks channel_chunk for."""
+  k = hp.kernel_size
+  out = []
+  for i, lay in enumerate(discriminator_layers(hp)):
+    out.append(('discriminator', i + 1, lay.cinp, 2, k, lay.lin // 2))
+    out.append(('discriminator', i + 1, lay.coutp, 1, k // 2, lay.lin // 2))
+  for i, lay in enumerate(generator_layers(hp)):
+    out.append(('generator', i + 1, lay.coutp, 2, k, lay.lout // 2))
+    out.append(('generator', i + 1, lay.cinp, 1, k // 2, lay.lout // 2))
+  return out
+
+
 def dense_streams(cp):
   """Channel pitches whose per-timestep Dense runs on the streaming kernels
   (cg_dense_rows / cg_dense_rows_act) instead of an LDS-staged cg_swconv
@@ -174,8 +215,14 @@ def validate_hparams(hp):
     raise ValueError('calciumgan_amd: only strides=2 is implemented in HIP')
   if hp.kernel_size % 2 or hp.kernel_size > 24 or hp.kernel_size < 2:
     raise ValueError('calciumgan_amd: kernel_size must be even and <= 24')
-  if hp.noise_dim % 8 or hp.noise_dim < 32:
-    raise ValueError('calciumgan_amd: noise_dim must be a multiple of 8, >= 32')
+  # the input Dense stores h[0] as rows of noise_dim channels and the first
+  # transposed convolution reads (and its input gradient writes) them at the
+  # channel pitch of every activation, a multiple of 32: the two must agree
+  if hp.noise_dim < 32 or pitch(hp.noise_dim) != hp.noise_dim:
+    raise ValueError(
+        'calciumgan_amd: noise_dim must be a multiple of 32 (got {}): the '
+        'generator reshapes its input Dense to rows of noise_dim channels, '
+        'and activations have a channel pitch of 32'.format(hp.noise_dim))
   # (batch_norm: single rank only -- GeneratorNet raises under data parallelism,
   # where the batch statistics would need a cross-rank reduction)
   activation_alpha(hp)  # raises for activations the kernels do not cover
@@ -192,4 +239,15 @@ def validate_hparams(hp):
   if hp.m >= hp.signal_shape[0] // 16:
     raise ValueError('phase shuffle m={} too large for sequence length'.format(
         hp.m))
+  # the staged windows of every layer's launches must fit LDS with some channel
+  # chunk (kernel_size 24 at sequence_length 32: 64 one-row samples per tile,
+  # each with a 12-row window in both parities)
+  for net, i, cx, stride, taps, lu in stride2_launches(hp):
+    try:
+      channel_chunk(cx, stride, taps, lu)
+    except ValueError as e:
+      raise ValueError(
+          'calciumgan_amd: kernel_size {} at sequence_length {} unsupported: '
+          '{} layer {}, stride {}, rows of {}: {}'.format(
+              hp.kernel_size, hp.signal_shape[0], net, i, stride, lu, e))
   return w

@@ -339,29 +339,9 @@ def _transpose_phases(k, pad_left):
   return out
 
 
-CK_TARGET = {1: 32, 2: 32}  # preferred channel chunk per source stride
-
-
-def _ck_for(Cx, stride, taps, Lu):
-  """Channel chunk of a packed operand: a divisor of the pitch, multiple of 8,
-  >= 32, valid for both row tiles the launcher may pick.  Preference: the chunk
-  that keeps one workgroup's LDS under half the CU (two resident workgroups
-  hide each other's staging): 32."""
-  cands = [d for d in range(32, Cx + 1, 8) if Cx % d == 0]
-  tgt = CK_TARGET[stride]
-  pref = sorted(cands, key=lambda d: (d > tgt, abs(d - tgt)))
-  tms = [tm for tm in (256, 64)
-         if ((Lu % tm == 0) if Lu >= tm else (tm % Lu == 0))]
-  if not tms:
-    raise ValueError('unsupported per-sample length {}'.format(Lu))
-  for d in pref:
-    if all(geo.lds_bytes(d, stride, taps, Lu, tm) <= geo.LDS_BYTES for tm in tms):
-      return d
-  # fall back to the small tile only
-  for d in pref:
-    if geo.lds_bytes(d, stride, taps, Lu, 64) <= geo.LDS_BYTES:
-      return d
-  raise ValueError('no channel chunk fits LDS (Cx={}, taps={})'.format(Cx, taps))
+# channel chunk of a packed operand (geometry.channel_chunk:
+# geometry.validate_hparams refuses by the same rule)
+_ck_for = geo.channel_chunk
 
 
 def _conv_desc(x, w, y, nB, Lx, Cx, taps, stride, off, Lu, N, Ly, Cy, CK,
@@ -536,9 +516,12 @@ _FUSE_LN = _flag('FUSE_LN')
 
 def _ln_fusable(lay, CK, taps):
   """Conv1DTranspose + LayerNorm in one launch: rows of at most 128 channels
-  (one 128-column tile) on the 32x32x16 tiles (uniform 32-channel K walk)."""
-  return (_FUSE_LN and lay.cout <= 128 and CK % 32 == 0 and geo.lds_bytes(
-      CK, 1, taps, lay.lin, 128, 128, 32) <= geo.LDS_BYTES)
+  (one 128-column tile) on the 32x32x16 tiles (uniform 32-channel K walk),
+  samples whose rows fill or divide the 128 rows of the narrowest such tile
+  (192 rows -- sequence_length 6144 -- fit none: LayerNorm stays its own pass)."""
+  rows_fit = (lay.lin % 128 == 0) if lay.lin >= 128 else (128 % lay.lin == 0)
+  return (_FUSE_LN and lay.cout <= 128 and CK % 32 == 0 and rows_fit and
+          geo.lds_bytes(CK, 1, taps, lay.lin, 128, 128, 32) <= geo.LDS_BYTES)
 
 
 # Tile / weight-stage choice by measurement: the best of the CG_TILE_* shapes x

@@ -47,7 +47,9 @@ F16_SCALE_TINY = 2.0**14
 # the same way: the gradient buffers hold normal numbers under them
 F16_GEN_SCALE = {'tiny': 2.0**18, 'tiny_noln': 2.0**18, 'mid': 2.0**21, 'odd_c': 2.0**19,
                  'tiny_bn': 2.0**18, 'tiny_bn_ln': 2.0**18, 'tiny_linear': 2.0**18,
-                 'tiny-no_fuse_ln': 2.0**18, 'tiny-no_defer_finish': 2.0**18}
+                 'tiny-no_fuse_ln': 2.0**18, 'tiny-no_defer_finish': 2.0**18,
+                 'k6_c40': 2.0**18, 'k14_c102': 2.0**18, 'k22_u24': 2.0**19,
+                 'l6144': 2.0**19}
 
 
 class StageError(AssertionError):

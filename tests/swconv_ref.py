@@ -524,8 +524,37 @@ SPECIAL_GEOMS = {(shifted, split): down(3, 64, 24, 64 if split else 32, 38,
 # the classic tiles' further shapes: 1 / 2 / 8 taps, Lu = 4 and 16, Cx = 64 / 96, N = 6 /
 # 64 / 102 / 130, the two phases' rows the other way round
 CLASSIC_MORE = DENSE + CLASSIC_DOWN[1:3] + CLASSIC_UP[1:]
+# every admitted kernel size next to 24, 8 and 2 (all of them on the classic tiles:
+# the software-pipelined ones take 12 taps per pass only).  With CK = 32 a chunk is
+# walked in ceil16(4 taps) K groups: taps = 6, 10, 14, 18, 22 at stride 2 and k / 2 = 2, 3,
+# 5, 6, 7, 9, 10, 11 per phase end in padded groups (the tap clamped, the operand zero);
+# the narrow last chunk clamps to half_taps - 1 = 2 .. 10; k = 6, 10, 14, 18, 22 give both
+# phases one window offset (off_step 0) and start phase 0 on an even tap
+TAP_SWEEP = (4, 6, 10, 12, 14, 16, 18, 20, 22)
+K_DOWN = {k: down(3, 64, k, 32, 40, MIXED3, 1) for k in TAP_SWEEP}
+K_DOWN_NARROW = {k: down(3, 64, k, 38, 40, MIXED3, 1) for k in TAP_SWEEP if k >= 6}
+K_UP = {k: up(3, 64, k, 32, 40) for k in TAP_SWEEP}
+K_UP_LN = {k: up(3, 64, k, 32, 102) for k in (6, 22)}
+# three chunks, several samples per tile, segments of two: the padded groups of a
+# middle chunk
+K_DOWN_MULTI = {k: down(5, 16, k, 96, 102, (1, -1, 0), 2) for k in TAP_SWEEP}
+# out_shifts + fix-up and the shift edges away from 24 taps: an odd half_taps and a
+# multiple of 4
+FIXUP_K = (6, 12)
+SHIFT_GEOMS_K = [down(5, 8, 6, 32, 40, (15, -15, 0, 1, -1), 1),
+                 down(3, 64, 12, 32, 40, (127, -127, 0), 1)]
+
+
+def sweep_geoms():
+  return (list(K_DOWN.values()) + list(K_DOWN_NARROW.values()) + list(K_UP.values()) +
+          list(K_UP_LN.values()) + list(K_DOWN_MULTI.values()))
+
+
 # shapes where one dropped K-step is below 20 bars too often (K = 24 x 128)
-EXACT_ONLY = [SPLIT_SWP4]
+# ... and the three-chunk sweep geometries from K = 14 x 96 on (16 x 96 holds under the
+# linear epilogue of sweep_epi)
+K_MULTI_EXACT_ONLY = [K_DOWN_MULTI[k] for k in (14, 18, 20, 22)]
+EXACT_ONLY = [SPLIT_SWP4] + K_MULTI_EXACT_ONLY
 
 
 def sweep_epi(G):
@@ -539,7 +568,8 @@ def sweep_epi(G):
 def real_geoms():
   out = ([SWP_DOWN, SWP_DOWN_NARROW, SWP_UP, SWP_UP_LN, NON_UNI] + CLASSIC_DOWN +
          CLASSIC_UP + DENSE + LN_GEOMS + [NON_UNI_UP, SPLIT_CLASSIC, SPLIT_SWP2, EPI_GEOM] + list(SPECIAL_GEOMS.values()) +
-         list(FULL_TILE.values()) + list(TWO_TILES.values()) + list(SSQ_GEOMS.values()))
+         list(FULL_TILE.values()) + list(TWO_TILES.values()) + list(SSQ_GEOMS.values()) +
+         sweep_geoms())
   seen, uniq = set(), []
   for G in out:
     if G not in seen and G not in EXACT_ONLY:

@@ -206,9 +206,78 @@ def test_validate_hparams_errors():
   with pytest.raises(ValueError):
     geo.validate_hparams(O.make_hparams(64, 4, 8, m=4))  # reflect pad >= len
   assert geo.validate_hparams(O.make_hparams(2048, 102, 64, m=10)) == 64
+  # kernel_size 24 at sequence_length 32: the deepest layers' one-row samples, 64 per
+  # tile with a 12-row window each in both parities, need 172 032 B of LDS
+  with pytest.raises(ValueError, match='kernel_size 24 at sequence_length 32.*LDS'):
+    geo.validate_hparams(O.make_hparams(32, 6, 8, kernel_size=24, m=1))
+  assert geo.validate_hparams(O.make_hparams(32, 6, 8, kernel_size=22, m=1)) == 1
+  # noise_dim off the channel pitch: the input Dense would store rows of 40 channels
+  # where the first transposed convolution reads, and its input gradient writes, 64
+  for nd in (40, 48, 8):
+    with pytest.raises(ValueError, match='noise_dim must be a multiple of 32'):
+      geo.validate_hparams(O.make_hparams(64, 6, 8, noise_dim=nd))
+  assert geo.validate_hparams(O.make_hparams(64, 6, 8, noise_dim=64)) == 2
 
 
-@pytest.mark.parametrize('k', [24, 8, 2])
+GRID_K = list(range(2, 25, 2))
+
+
+def _placeholder_launches(hp, nB=6):
+  """(what, descriptor) of the down and the up launch of every Stride2Layer of both
+  networks, built by nets._conv_desc itself (its static tile rule included) over
+  placeholder tensors: cg_swconv_check dereferences nothing."""
+  x = torch.zeros(8, dtype=torch.bfloat16)
+  f = torch.zeros(8)
+  k = hp.kernel_size
+  out = []
+  nets_layers = [
+      ('D', [nets.Stride2Layer(k, l.cin, l.cout, l.lin) for l in geo.discriminator_layers(hp)],
+       geo.discriminator_layers(hp)),
+      ('G', [nets.Stride2Layer(k, l.cout, l.cin, l.lout) for l in geo.generator_layers(hp)],
+       geo.generator_layers(hp))]
+  for net, convs, lays in nets_layers:
+    for i, (conv, lay) in enumerate(zip(convs, lays)):
+      W = torch.zeros(k * conv.A * conv.B)
+      down, up = conv.pack_down(W), conv.pack_up(W)
+      out.append(('{}{} down'.format(net, i + 1), conv.down(x, down, x, nB)))
+      out.append(('{}{} up'.format(net, i + 1), conv.up(x, up, x, nB)))
+      if net == 'G' and nets._ln_fusable(lay, up.CK, k // 2):
+        out.append(('G{} up, LayerNorm'.format(i + 1),
+                    conv.up(x, up, x, nB, bias=f, ln=(f, f, x, f, f))))
+  return out
+
+
+@pytest.mark.parametrize('k', GRID_K)
+def test_every_admitted_hparams_point_builds_and_passes_the_launch_check(k, fixed_tiles):
+  """kernel_size x sequence_length x num_units x num_channels: wherever
+  validate_hparams admits a point, every Stride2Layer of both networks builds (a
+  channel chunk fits LDS) and cg_swconv_check admits each layer's stride-2 and
+  two-phase launch with the tile nets._conv_desc picks; a refused point is refused
+  by validate_hparams, with a reason, not later."""
+  import ctypes
+  lib = _lib.load()
+  admitted = 0
+  for L in (32, 64, 128, 2048, 6144):
+    for U in (8, 24, 40):
+      for C in (6, 40, 102):
+        hp = O.make_hparams(L, C, U, kernel_size=k, m=min(2, L // 16 - 1))
+        try:
+          geo.validate_hparams(hp)
+        except ValueError as e:
+          assert (L, k) == (32, 24) and 'LDS' in str(e), (L, C, U, k, str(e))
+          continue
+        admitted += 1
+        for what, d in _placeholder_launches(hp):
+          assert lib.cg_swconv_check(ctypes.byref(d)) == 0, (L, C, U, k, what, d.tile)
+          # ... and with the software-pipelined tile the rule prefers on a device
+          # (applied only where the check admits it: host logic)
+          nets._apply_tile_choice(d, nets._static_swp_choice(d))
+          assert lib.cg_swconv_check(ctypes.byref(d)) == 0, (L, C, U, k, what, d.tile)
+          assert d.taps == (k if d.stride == 2 else k // 2)
+  assert admitted == (36 if k == 24 else 45)
+
+
+@pytest.mark.parametrize('k', GRID_K)
 def test_transpose_phase_walk_equals_conv_transpose(k):
   """Host-side phase/tap/offset spec used for dgrad + Conv1DTranspose, checked
   in numpy against the oracle: out[2u+p] = sum_jj x[u+off_p+jj] W[tap0_p-2jj]."""

@@ -25,7 +25,7 @@ from test_layer_ref import GEN_CASES, SEED, SHAPES, case_inputs, shift_case
 pytestmark = pytest.mark.gpu
 
 # name -> (shape, {(module, attribute): value} set before the model is built)
-CRITIC_CASES = {n: (n, {}) for n in SHAPES if n != 'mid'}
+CRITIC_CASES = {n: (n, {}) for n in SHAPES if n not in ('mid', 'l6144')}
 for _n in ('tiny', 'long'):
   CRITIC_CASES[_n + '-mix'] = (_n, {('nets', '_L1_LINEAR_MIN_ROWS'): 0})
 for _n in ('tiny', 'odd_c'):
@@ -143,12 +143,21 @@ def test_case_list_reaches_every_path(precision, monkeypatch, fixed_tiles):
   """From the plans: folded, side + fix-up, cg_unshuffle_mask, jvp_folds,
   norm_deferred and mixes_layer1 each true somewhere and false somewhere."""
   f16 = precision
+  from calciumgan_amd import _lib
   seen = dict(folded=set(), sided=set(), masked=set(), jvp_folds=set(),
               norm_deferred=set(), mixes_layer1=set())
+  classic_sided = set()  # m > 0, classic tiles only, side buffer + fix-up, nothing folded
   for case in CRITIC_CASES:
     with monkeypatch.context() as mp:
       hp, gan, real, r, B = _build(case, f16, mp)
-      fl = LT.plan_flags(gan._get_state(B)['critic'])
+      plan = gan._get_state(B)['critic']
+      fl = LT.plan_flags(plan)
+      tiles = [d.tile for d in plan.fwd] + [d.tile for _, d in plan.dgrad] + [
+          plan.input_grad.tile]
+      if (hp.m > 0 and all(t in _lib.TILES for t in tiles) and fl['sided'] and
+          not fl['folded']):
+        classic_sided.add(case)
+        assert hp.kernel_size != 24, case
     seen['folded'].add(bool(fl['folded']))
     seen['sided'].add(bool(fl['sided']))
     seen['masked'].add(bool(set(range(1, 5)) - fl['folded'] - fl['sided']))
@@ -156,6 +165,9 @@ def test_case_list_reaches_every_path(precision, monkeypatch, fixed_tiles):
       seen[k].add(fl[k])
   assert seen['folded'] == {True, False}, seen
   assert True in seen['sided'] and True in seen['masked'], seen
+  # the forms of every kernel size but 24: no software-pipelined tile anywhere in the
+  # plan, the reflected rows through the side buffer and cg_unshuffle_fixup
+  assert {'k6_c40', 'k12', 'k14_c102', 'k22_u24'} <= classic_sided, classic_sided
   assert seen['jvp_folds'] == {True, False}, seen
   assert seen['mixes_layer1'] == {True, False}, seen
   # (the f16 build never defers the norm: its loss scale multiplies the
@@ -244,7 +256,10 @@ def test_generator_cases_reach_both_layernorm_forms(monkeypatch, fixed_tiles):
   for case in GEN_CASES:
     with monkeypatch.context() as mp:
       hp, gan, real, r, B = _build_gen(case, False, mp)
-      seen |= set(LT.gen_flags(gan, B)['ln_fused'])
+      fused = list(LT.gen_flags(gan, B)['ln_fused'])
+      seen |= set(fused)
+      if case == 'l6144':  # 192, 384, 768, ... rows: only the first fit no 128-row tile
+        assert fused == [False, True, True, True, True]
   assert seen == {True, False}
 
 

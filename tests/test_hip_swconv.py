@@ -133,6 +133,41 @@ def _targets():
       out.append(('splitk', S.SPLIT_CLASSIC, dict(tile=2, ksplit=ksplit, epi=epi), False))
     out.append(('splitk', S.SPLIT_SWP2, dict(tile=13, ksplit=2, epi=epi, pmajor=1), False))
     out.append(('splitk', S.SPLIT_SWP4, dict(tile=13, ksplit=4, epi=epi, pmajor=1), True))
+  out += _sweep_targets()
+  return out
+
+
+SWEEP_TILES = ((0, 2), (0, 4), (1, 2), (1, 4), (2, 2), (2, 4), (4, 2))
+
+
+def _sweep_targets():
+  """Every admitted kernel size other than 24, 8 and 2 (swconv_ref.TAP_SWEEP): the
+  tiles nets._conv_desc's static rule picks (0, 1, 2) at both stage depths and one
+  32x32x16 tile, with the operand order nets packs (parity-major at stride 2; the
+  32x32x16 tile walks the plain order), the narrow last chunk from 6 taps on,
+  split-parity staging on tile 1 wherever the check admits it, a three-chunk walk
+  with several samples per tile, and the fused LayerNorm at k = 6 and 22."""
+  out = []
+  for k in S.TAP_SWEEP:
+    for tile, ks in SWEEP_TILES:
+      pm = int(tile != 4)
+      out.append(('taps', S.K_DOWN[k], dict(tile=tile, ks=ks, pmajor=pm), False))
+      out.append(('taps', S.K_UP[k], dict(tile=tile, ks=ks), False))
+      if k in S.K_DOWN_NARROW:
+        out.append(('tapsnarrow', S.K_DOWN_NARROW[k],
+                    dict(tile=tile, ks=ks, pmajor=1, narrow=1), False))
+    for ks in (2, 4):
+      out.append(('tapssp', S.K_DOWN[k], dict(tile=1, ks=ks, sp=1, pmajor=1), False))
+      if k in S.K_DOWN_NARROW:
+        out.append(('tapssp', S.K_DOWN_NARROW[k],
+                    dict(tile=1, ks=ks, sp=1, pmajor=1, narrow=1), False))
+    for tile, ks in ((1, 2), (1, 4), (4, 2)):
+      out.append(('tapsmulti', S.K_DOWN_MULTI[k], dict(tile=tile, ks=ks, pmajor=int(tile != 4)),
+                  False))
+  for k, G in sorted(S.K_UP_LN.items()):
+    for tile in LN_CLASSIC:
+      for ks in (2, 4):
+        out.append(('tapsln', G, dict(tile=tile, ks=ks, epi=S.EPI_LN), False))
   return out
 
 
@@ -408,8 +443,9 @@ def test_every_dispatch_target(G, kw, exact_only, precision):
   """The nine classic tiles x stage depth x stride, UNI and the CK = 40 walk,
   split-parity, the narrow last chunk with and without split-parity residency, the
   seven software-pipelined tiles x stride 1 / 2 / 2 narrow, the LayerNorm
-  instantiations and split-K -- rounded reals within the bar, then the exact recipe
-  bit for bit (ties round to even; fp16 sums beyond 65504 are +-inf)."""
+  instantiations and split-K, and the classic tiles at every kernel size from 4 to 22
+  (_sweep_targets) -- rounded reals within the bar, then the exact recipe bit for bit
+  (ties round to even; fp16 sums beyond 65504 are +-inf)."""
   f16 = precision
   epi = kw['epi']
   if epi == S.EPI_LN:
@@ -515,15 +551,16 @@ def test_row_scale(tile, precision):
   assert refused(d)
 
 
-@pytest.mark.parametrize('G', S.SHIFT_GEOMS, ids=S.gid)
+@pytest.mark.parametrize('G', S.SHIFT_GEOMS + S.SHIFT_GEOMS_K, ids=S.gid)
 def test_shift_edges(G, precision):
   """+-(Lx - 1), mixed signs within a launch, a segment larger than the batch; the
-  exact recipe, classic and software-pipelined staging."""
+  exact recipe, classic and software-pipelined staging.  Also at 6 and 12 taps
+  (classic tiles only; split-parity staging where a parity fills whole stages: 12)."""
   f16 = precision
   c = case(G, f16, 'exact')
   for kw in (dict(tile=1), dict(tile=2, sp=1, pmajor=1), dict(tile=13, pmajor=1)):
     if not admits(desc_of(G, epi=S.EPI_LRELU, **kw)):
-      assert kw['tile'] == 13 and G.taps != 24
+      assert (kw['tile'] == 13 and G.taps != 24) or (kw.get('sp') and G.taps % 4)
       continue
     L = Launch(G, c, f16, 'exact', alpha=EXACT_ALPHA, epi=S.EPI_LRELU, **kw)
     assert L.run() == 0
@@ -584,8 +621,25 @@ def check_out_shifts(G, c, f16, recipe, osh, oseg, side_rows, alpha, epi, kw):
   y, y_own, side, side_own = S.swconv_out_shifts(G, c['x'], c['Wl'], osh, oseg, side_rows, f16,
                                                  c['bias'], epi, a, c['mask'])
   err = S.acc_bound(G, c['x'], c['Wl'], c['bias'])
-  # (MASK: the rounded value times the slope -- one more product)
-  L.compare(L.y, y, y_own, exact, err + S.U * np.abs(y), 'direct rows')
+  # the bar of a direct row is that of the OUTPUT row t stored there.  MASK: the launch
+  # rounds its f32 value to the activation type BEFORE the mask's product, so within
+  # err of a rounding boundary it may hold the neighbour (swconv_ref.rounded_spread: one
+  # ulp of the UNMASKED value, which the slope scales to more than one ulp of a masked
+  # value in a lower binade); everywhere else the two roundings agree and only the f32
+  # product with the slope rounds
+  pre = S.place(G, S.linear(G, c['x'], c['Wl'], c['bias']))[0]
+  pre_at, err_at = np.zeros_like(y), np.zeros_like(y)
+  for b in range(G.nB):
+    td, r, _, _ = S.out_shift_rows(int(osh[b // oseg]), G.Ly)
+    pre_at[b, r], err_at[b, r] = pre[b, td], err[b, td]
+  if exact:
+    direct_err = 0.0  # (compared bit for bit)
+  elif epi == S.EPI_MASK:
+    direct_err = (S.rounded_spread(pre_at, err_at, f16) * S.mask_factor(c['mask'], a) +
+                  S.U * np.abs(y))
+  else:
+    direct_err = err_at
+  L.compare(L.y, y, y_own, exact, direct_err, 'direct rows')
   sv = L.side[:G.nB * side_rows * L.Cy].reshape(G.nB, side_rows, L.Cy)
   own_t = torch.tensor(side_own, device=sv.device)
   assert P.is_sentinel(sv[~own_t]) and P.is_sentinel(L.side[G.nB * side_rows * L.Cy:])
@@ -634,6 +688,22 @@ def test_out_shifts_and_fixup(tile, side_rows, epi, precision):
     c = case(G, f16, recipe)
     check_out_shifts(G, c, f16, recipe, (2, -2, 0), 1, side_rows,
                      ALPHA if recipe == 'real' else EXACT_ALPHA, epi, dict(tile=tile, epi=epi))
+
+
+@pytest.mark.parametrize('epi', [S.EPI_NONE, S.EPI_MASK])
+@pytest.mark.parametrize('tile,ks', [(1, 2), (2, 4), (4, 2)])
+@pytest.mark.parametrize('k', S.FIXUP_K)
+def test_out_shifts_and_fixup_away_from_24_taps(k, tile, ks, epi, precision):
+  """The same on the classic tiles at kernel sizes 6 (three taps per phase, both
+  phases at one window offset) and 12: the side buffer + cg_unshuffle_fixup form is
+  the one the critic's input gradient takes at every kernel size but 24."""
+  f16 = precision
+  G = S.K_UP[k]
+  for recipe in ('real', 'exact'):
+    c = case(G, f16, recipe)
+    check_out_shifts(G, c, f16, recipe, (2, -2, 0), 1, 2,
+                     ALPHA if recipe == 'real' else EXACT_ALPHA, epi,
+                     dict(tile=tile, ks=ks, epi=epi))
 
 
 @pytest.mark.parametrize('tile', [6, 8, 12, 15])

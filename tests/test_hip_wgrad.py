@@ -160,11 +160,16 @@ def both_recipes(G, f16, what='', recipes=('real', 'exact'), **kw):
 @pytest.mark.parametrize('gi', [0, 1, 2], ids=['Lu8', 'Lu64', 'Lu128'])
 @pytest.mark.parametrize('taps', W.TAPS)
 def test_every_instantiation(taps, gi, precision):
-  """wgrad_kernel<2, TPW, false, PIPE, TT, ALLT>: TPW = 1 (taps 2, 8), 2 (12, 16), 3
-  (20, 24); ALLT = 1 needs taps == 8 TPW and one sample per tile (8, 16, 24 at Lu
-  >= 64), ALLT = 2 is the ring (24); taps 2, 12, 20 and every Lu = 8 case (nseg = 8,
-  no pipe; nB Lu = 72: the second tile holds one live sample of eight) take the
-  per-tap guarded body.  Lu = 64: TT 64, pipe.  Lu = 128: TT 128, and TT 64 with
+  """wgrad_kernel<2, TPW, false, PIPE, TT, ALLT> at every even tap count from 2 to 24:
+
+      taps   2  4  6  8 | 10 12 14 16 | 18 20 22 24
+      TPW    1  1  1  1 |  2  2  2  2 |  3  3  3  3
+      ALLT   0  0  0  1 |  0  0  0  1 |  0  0  0  2     (at Lu >= 64)
+
+  ALLT = 1 needs taps == 8 TPW and one sample per tile (8, 16 at Lu >= 64), ALLT = 2
+  is the ring (24); every other tap count (the last wave owns fewer than TPW live
+  taps) and every Lu = 8 case (nseg = 8, no pipe; nB Lu = 72: the second tile holds
+  one live sample of eight) take the per-tap guarded body.  Lu = 64: TT 64, pipe.  Lu = 128: TT 128, and TT 64 with
   tile_rows = 64.  The bias gradient rides along over half the rows (a multiple of
   32 at Lu >= 64: the ring keeps it; 36 at Lu = 8: inside a tile and a sample)."""
   f16 = precision
@@ -496,11 +501,26 @@ def pack_descs():
               24 * 102 * 130))
   out.append(('narrow_taps6', W.PackDesc(6, 40, 3, 64, parity_major=1, narrow_last=1),
               6 * 40 * 3))
+  # parity-major at every even tap count, narrow_last wherever it has room (6 .. 22;
+  # C = 40 of Cx = 64: the last chunk's 8 real channels next to a full chunk)
+  for taps in range(2, 25, 2):
+    if taps not in (2, 8, 24):
+      out.append(('taps{}_pm'.format(taps), W.PackDesc(taps, 40, 65, 64, parity_major=1),
+                  taps * 40 * 65))
+    if 6 < taps < 24:
+      out.append(('narrow_taps{}'.format(taps),
+                  W.PackDesc(taps, 40, 3, 64, parity_major=1, narrow_last=1), taps * 40 * 3))
   # two phases out of one 24-tap source: taps 22, 20, .. and 23, 21, ..
   for t0 in (22, 23):
     out.append(('phase_tap0_{}'.format(t0),
                 W.PackDesc(12, 33, 70, 64, tap0=t0, tap_step=-2, s_tap=33 * 70),
                 24 * 33 * 70))
+  # ... and out of a 10-tap one (k = 2 mod 4: phase 0 starts on the EVEN tap 8, phase 1 on
+  # 9), 5 taps per phase: ceil16(5 x 4) = 32 groups, 12 of them padding
+  for t0 in (8, 9):
+    out.append(('phase_k10_tap0_{}'.format(t0),
+                W.PackDesc(5, 33, 70, 64, tap0=t0, tap_step=-2, s_tap=33 * 70),
+                10 * 33 * 70))
   # a transposed source (s_c and s_n swapped: the LDS-turned form), CK 64
   out.append(('transposed', W.PackDesc(8, 70, 33, 128, CK=64, s_tap=70 * 33, s_c=1, s_n=70),
               8 * 70 * 33))

@@ -29,6 +29,17 @@ SHAPES = {
     'm0_k8': (128, 6, 8, 8, 0, 3),    # classic tiles, tangent scale not folded
     'b1': (64, 6, 8, 24, 2, 1),
     'mid': (256, 16, 32, 24, 2, 6),
+    # kernel sizes other than 24: the classic tiles, and with them the unfolded forms
+    # of the critic schedule (side buffer + cg_unshuffle_fixup) with m > 0
+    'k2': (64, 6, 8, 2, 2, 3),
+    'k6_c40': (128, 40, 16, 6, 3, 2),    # narrow first layer, half_taps 3
+    'k12': (128, 6, 8, 12, 3, 2),
+    'k14_c102': (128, 102, 16, 14, 3, 2),  # pitch 128, narrow
+    'k22_u24': (128, 6, 24, 22, 3, 2),   # pitches 32 / 64 / 96 / 96 / 128, narrow at layer 4
+    'k4_u40': (64, 6, 40, 4, 2, 2),      # last width 200 -> pitch 224
+    # 192 rows per sample in the generator's first layer: no LayerNorm tile fits them
+    # (generator case only)
+    'l6144': (6144, 6, 8, 24, 2, 1),
 }
 SEED = 42
 # generator cases: name -> (shape, hparams, nets flags set before the model is built)
@@ -42,6 +53,10 @@ GEN_CASES = {
     'tiny_linear': ('tiny', dict(normalize=False), {}),
     'tiny-no_fuse_ln': ('tiny', {}, {'_FUSE_LN': False}),
     'tiny-no_defer_finish': ('tiny', {}, {'_DEFER_FINISH': False}),
+    'k6_c40': ('k6_c40', {}, {}),
+    'k14_c102': ('k14_c102', {}, {}),
+    'k22_u24': ('k22_u24', {}, {}),
+    'l6144': ('l6144', {}, {}),   # LayerNorm fused from the second layer on only
 }
 
 
@@ -160,7 +175,20 @@ VARIANTS = {
 @pytest.mark.parametrize('terms', [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1)],
                          ids=['real', 'fake', 'gp', 'all'])
 def test_critic_closure(terms, variant):
-  hp, gw, dw, real, z, alpha, shifts, B = _setup(case=1)
+  _critic_closure(_setup(case=1), terms, variant)
+
+
+@pytest.mark.parametrize('variant', ['side', 'plain'])
+def test_critic_closure_at_kernel_size_6(variant):
+  """k = 2 (mod 4): both phases of the input gradient share one window offset and
+  phase 0 starts on an even tap; three taps per phase.  The forms a kernel size
+  other than 24 takes (no folded fix-up)."""
+  _critic_closure(case_inputs(SHAPES['k6_c40'], SEED, shift_case('k6_c40')), (1, 1, 1),
+                  variant)
+
+
+def _critic_closure(inputs, terms, variant):
+  hp, gw, dw, real, z, alpha, shifts, B = inputs
   fake, want = _oracle_terms(hp, gw, dw, real, z, alpha, shifts, terms)
   wr, wf, wp = terms
   hp.gradient_penalty = hp.gradient_penalty if wp else 0.0
@@ -259,20 +287,24 @@ GEN_NORMS = {'ln': dict(layer_norm=True), 'plain': dict(layer_norm=False),
 GEN_FLAGS = dict(folded=(1, 2, 3))
 
 
-def _gen_sim(norm, exact, f16=False, fused=False, defer=False, **hpkw):
-  hp, gw, dw, real, z, alpha, shifts, B = _setup(case=2, **dict(GEN_NORMS[norm], **hpkw))
+def _gen_sim(norm, exact, f16=False, fused=False, defer=False, shape=None, **hpkw):
+  hpkw = dict(GEN_NORMS[norm], **hpkw)
+  hp, gw, dw, real, z, alpha, shifts, B = (
+      _setup(case=2, **hpkw) if shape is None else
+      case_inputs(SHAPES[shape], SEED + 1, shift_case(shape), **hpkw))
   ctx = LT.Ctx(hp, B, f16, nseg=1, exact=exact, **GEN_FLAGS)
   g = LT.GenCtx(hp, B, f16, exact=exact, ln_fused=[fused] * 5, defer=defer,
-                Cf=8)
+                Cf=-(-hp.num_channels // 8) * 8)
   if not exact:
     z = z.astype(np.float32)
   sim = LT.GenSim(ctx, g, gw, dw, z, shifts[:, 1])
   return hp, gw, dw, z, shifts[:, 1], ctx, g, sim
 
 
-@pytest.mark.parametrize('norm', list(GEN_NORMS))
-def test_generator_closure(norm):
-  hp, gw, dw, z, sh, ctx, g, sim = _gen_sim(norm, True, fused=(norm == 'ln'))
+@pytest.mark.parametrize('norm,shape', [(n, None) for n in GEN_NORMS] + [('ln', 'k6_c40')],
+                         ids=list(GEN_NORMS) + ['ln-k6_c40'])
+def test_generator_closure(norm, shape):
+  hp, gw, dw, z, sh, ctx, g, sim = _gen_sim(norm, True, fused=(norm == 'ln'), shape=shape)
   sim.run()
   res = O.g_step_grads(_t64(gw), _t64(dw), torch.tensor(z), sh, hp)
   got = LT.gen_grads(sim)

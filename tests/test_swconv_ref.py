@@ -249,7 +249,7 @@ MIN_UNREPRESENTABLE = 0.5  # (sums of >= 1 in units of 2^-9 / 2^-12: at most 1/4
                            # the smallest shapes hold many sums below 1)
 
 
-@pytest.mark.parametrize('G', REAL, ids=S.gid)
+@pytest.mark.parametrize('G', REAL + S.K_MULTI_EXACT_ONLY, ids=S.gid)
 @pytest.mark.parametrize('f16', [False, True], ids=['bf16', 'f16'])
 def test_exact_recipe_is_exact_in_f32_and_needs_rounding(G, f16):
   x, Wl, bias, plants = S.exact_recipe(G, f16)
@@ -352,5 +352,46 @@ def test_every_admissible_dispatch_target_is_collected():
           n += 1
           assert have.get(_key(G, kw)) == {'real', 'exact'}, (build, S.gid(G), kw)
       assert n > 100
+  finally:
+    _lib.use('bf16')
+
+
+def test_tap_sweep_is_collected_at_every_kernel_size():
+  """The dispatch key above does not hold the tap count.  Per kernel size of
+  swconv_ref.TAP_SWEEP, in either build: tiles 0, 1, 2 at both stage depths and tile 4
+  run the stride-2 launch, the narrow one (6 taps and up) and the two phases; the
+  three-chunk geometry runs on tiles 1 and 4; split-parity staging on tile 1 is
+  collected exactly where a parity's K groups fill whole stages (k a multiple of 4
+  at 2 K-steps per stage, of 8 at 4), plain and narrow; the LayerNorm tiles run k = 6
+  and 22.  Nothing the check refuses drops a case of this list silently."""
+  import test_hip_swconv as T
+  try:
+    for build in ('bf16', 'f16'):
+      _lib.use(build)
+      got = set()
+      for p in T.dispatch_cases():
+        G, kw, exact_only = p.values
+        got.add((G, kw['tile'], kw.get('ks', 2), kw.get('sp', 0), kw.get('narrow', 0),
+                 kw['epi'] == S.EPI_LN))
+      for k in S.TAP_SWEEP:
+        for tile, ks in T.SWEEP_TILES:
+          assert (S.K_DOWN[k], tile, ks, 0, 0, False) in got, (build, k, tile, ks)
+          assert (S.K_UP[k], tile, ks, 0, 0, False) in got, (build, k, tile, ks)
+          if k >= 6:
+            assert (S.K_DOWN_NARROW[k], tile, ks, 0, 1, False) in got, (build, k, tile, ks)
+        for tile, ks in ((1, 2), (1, 4), (4, 2)):
+          assert (S.K_DOWN_MULTI[k], tile, ks, 0, 0, False) in got, (build, k, tile, ks)
+        for ks in (2, 4):
+          whole = k % (2 * ks) == 0
+          assert ((S.K_DOWN[k], 1, ks, 1, 0, False) in got) == whole, (build, k, ks)
+          if k >= 6:
+            assert ((S.K_DOWN_NARROW[k], 1, ks, 1, 1, False) in got) == whole, (build, k, ks)
+      for k in (6, 22):
+        for tile in T.LN_CLASSIC:
+          for ks in (2, 4):
+            assert (S.K_UP_LN[k], tile, ks, 0, 0, True) in got, (build, k, tile, ks)
+      # the geometries reach what the sweep is for
+      assert all(S.K_UP[k].off_step == (0 if k % 4 == 2 else 1) for k in S.TAP_SWEEP)
+      assert any((4 * S.K_UP[k].taps) % 16 for k in S.TAP_SWEEP)
   finally:
     _lib.use('bf16')

@@ -326,7 +326,7 @@ def instantiation_geoms(taps):
           geom(2, 128, taps, 8, 65, (-3, 2), 1)]
 
 
-TAPS = [2, 8, 12, 16, 20, 24]
+TAPS = list(range(2, 25, 2))  # every kernel size geometry.validate_hparams admits
 CHANNELS = [(1, 8, 1, 8), (8, 16, 40, 48), (33, 40, 65, 72), (102, 128, 130, 136),
             (102, 128, 1, 8), (1, 8, 130, 136)]  # Cx_real, Cx, Cg_real, Cg
 # (Cx_real, Cg_real) -> gmode of plan_wgrad's XCD grouping (gx = ceil(Cx / 32) cx
