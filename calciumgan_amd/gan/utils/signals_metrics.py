@@ -1,7 +1,10 @@
 """Figures of the calcium traces themselves, before deconvolution (the reference
 keeps its TensorFlow trace summaries in a module of this name; they are not
-restated here): the per-neuron power spectrum averaged over trials.
-compute_metrics.py --spectral_metrics; csrc/trace_psd.hip, DESIGN.md 22.
+restated here): the per-neuron power spectrum averaged over trials
+(compute_metrics.py --spectral_metrics; csrc/trace_psd.hip) and,
+in the second half of the module, the distance from every trial to the nearest
+stretch of the recording (--novelty_metrics; csrc/nearest_stretch.hip, DESIGN.md
+23).
 
 Per trial and neuron, with x the float32 trace of T frames:
   m   = float32(sum_t float64(x_t) / T)
@@ -231,3 +234,226 @@ def spectral_scores(ref, other, T, frame_rate=FRAME_RATE):
         'num_trials': [sides[0][1], sides[1][1]],
         'frame_rate': float(frame_rate),
     }
+
+
+# -- nearest stretch of the recording (compute_metrics.py --novelty_metrics;
+# csrc/nearest_stretch.hip) ---------------------------------------
+#
+# R: the recording, (T_raw, C) float32.  Q: the queries, (N, L, C) float32, L <=
+# T_raw.  step >= 1; offsets s_j = j step for j = 0 .. S - 1, S = (T_raw - L) //
+# step + 1: every full stretch counts, the last one included.
+#   d2[n][j] = sum_{t, c} (float64(Q[n, t, c]) - float64(R[s_j + t, c]))^2
+# in float64; a non-finite d2 is NaN.  The expanded form is |q_n|^2 + W_j - 2 sum
+# q r with every term float64 (the float32 products are exact there), clamped at
+# 0.  Exclusion: `exclude` int32 (N,) of start rows, negative for none; for
+# query n the offsets with |s_j - exclude[n]| < exclude_len are left out of the
+# minimum (d2 holds them all the same).
+#   nearest[n] = the least finite admitted d2[n][j], index[n] the LOWEST j that
+#   attains it; NaN and -1 where no admitted entry is finite.
+# A non-finite sample of a query spoils that query only, a non-finite row of the
+# recording only the offsets whose stretch covers it.
+_OFFSETS_PER_PASS = 64
+
+
+def stretch_offsets(T_raw, L, step=1):
+  """S = (T_raw - L) // step + 1, the number of offsets."""
+  return (int(T_raw) - int(L)) // int(step) + 1
+
+
+def _nearest_stretch_args(queries, recording, step, exclude, exclude_len):
+  q = np.asarray(queries)
+  r = np.asarray(recording)
+  if q.ndim != 3 or r.ndim != 2 or q.shape[2] != r.shape[1] or min(q.shape) < 1:
+    raise ValueError('(N, L, C) queries and a (T_raw, C) recording expected')
+  if q.shape[1] > r.shape[0]:
+    raise ValueError('queries of {} rows, a recording of {}'.format(
+        q.shape[1], r.shape[0]))
+  if int(step) < 1 or int(exclude_len) < 0:
+    raise ValueError('step >= 1 and exclude_len >= 0 expected')
+  q = q.astype(np.float32, copy=False)
+  r = np.ascontiguousarray(r, dtype=np.float32)
+  if exclude is not None:
+    exclude = np.asarray(exclude).astype(np.int64)
+    if exclude.shape != (q.shape[0],):
+      raise ValueError('exclude: one start row per query expected')
+  return q, r, int(step), exclude, int(exclude_len)
+
+
+def nearest_stretch(queries, recording, step=1, exclude=None, exclude_len=0,
+                    return_profile=False, expanded=False):
+  """(nearest float64 (N,), index int64 (N,)[, d2 float64 (N, S)]) of the
+  definitions above.  The default is the direct difference form, walked in
+  chunks of offsets: the statement cg_nearest_stretch and the expanded form are
+  tested against.  expanded=True is the three-term form, a float64 matmul over
+  chunks of the Toeplitz operand (a strided view of the recording: nothing of
+  size S x K is kept), within 4 K 2^-53 (|q_n|^2 + W_j) of the direct form."""
+  q, r, step, exclude, exclude_len = _nearest_stretch_args(
+      queries, recording, step, exclude, exclude_len)
+  N, L, C = q.shape
+  K, S = L * C, stretch_offsets(r.shape[0], L, step)
+  q64 = q.astype(np.float64)
+  flat = r.astype(np.float64).reshape(-1)
+  # row j: the K elements of stretch j, as they lie in the recording
+  toeplitz = np.lib.stride_tricks.sliding_window_view(flat, K)[::step * C]
+  assert toeplitz.shape == (S, K)
+  if expanded:
+    qf = q64.reshape(N, K)
+    q2 = (qf * qf).sum(axis=1)
+  nearest = np.full(N, np.inf)
+  index = np.full(N, -1, np.int64)
+  profile = np.empty((N, S), np.float64) if return_profile else None
+  with np.errstate(invalid='ignore', over='ignore'):
+    for j0 in range(0, S, _OFFSETS_PER_PASS):
+      rows = toeplitz[j0:j0 + _OFFSETS_PER_PASS]
+      if expanded:
+        w = (rows * rows).sum(axis=1)
+        d2 = (q2[:, None] + w[None, :]) - 2.0 * (qf @ rows.T)
+        d2 = np.where(d2 < 0.0, 0.0, d2)
+      else:
+        d2 = np.empty((N, len(rows)), np.float64)
+        for i, row in enumerate(rows):
+          d = q64 - row.reshape(1, L, C)
+          d2[:, i] = (d * d).reshape(N, K).sum(axis=1)
+      d2 = np.where(np.isfinite(d2), d2, np.nan)
+      if return_profile:
+        profile[:, j0:j0 + len(rows)] = d2
+      admitted = np.isfinite(d2)
+      if exclude is not None:
+        s = (j0 + np.arange(len(rows), dtype=np.int64)) * step
+        admitted &= ~((exclude[:, None] >= 0) &
+                      (np.abs(s[None, :] - exclude[:, None]) < exclude_len))
+      cand = np.where(admitted, d2, np.inf)
+      at = cand.argmin(axis=1)            # (the first of equals)
+      least = cand[np.arange(N), at]
+      better = admitted[np.arange(N), at] & ((index < 0) | (least < nearest))
+      nearest = np.where(better, least, nearest)
+      index = np.where(better, j0 + at, index)
+  nearest = np.where(index < 0, np.nan, nearest)
+  return (nearest, index, profile) if return_profile else (nearest, index)
+
+
+def nearest_stretch_device(queries, recording, step=1, exclude=None,
+                           exclude_len=0, return_profile=False):
+  """`nearest_stretch` on the GPU (cg_nearest_stretch): float32 device tensors
+  (N, L, C) and (T_raw, C), any strides, read in place -> device (nearest
+  float64 (N,), index int32 (N,)[, d2 float64 (N, S)]).  exclude: None, or one
+  int32 start row per query (a device tensor is taken as it is).  Five launches,
+  nothing zeroed beforehand, no host synchronisation.  Agrees with the statement
+  within 4 K 2^-53 (|q_n|^2 + W_j), and bit for bit where the sums are exact."""
+  import torch
+  from ... import _lib as hip
+  for t, dim in ((queries, 3), (recording, 2)):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and
+            t.dim() == dim):
+      raise ValueError('float32 device tensors (N, L, C) and (T_raw, C) expected')
+  N, L, C = queries.shape
+  T_raw = recording.shape[0]
+  if min(N, L, C) < 1 or recording.shape[1] != C or L > T_raw:
+    raise ValueError('(N, L, C) queries and a (T_raw >= L, C) recording expected')
+  if int(step) < 1 or int(exclude_len) < 0:
+    raise ValueError('step >= 1 and exclude_len >= 0 expected')
+  if exclude is not None:
+    if not torch.is_tensor(exclude):
+      exclude = torch.as_tensor(np.asarray(exclude).astype(np.int32))
+    exclude = exclude.to(device=queries.device, dtype=torch.int32).contiguous()
+    if exclude.shape != (N,):
+      raise ValueError('exclude: one start row per query expected')
+  nbytes = hip.load().cg_nearest_stretch_ws_bytes(N, L, C, T_raw, int(step))
+  if nbytes < 0:
+    raise ValueError('cg_nearest_stretch: unsupported shape {}'.format(
+        (N, L, C, T_raw, int(step))))
+  dev = queries.device
+  S = stretch_offsets(T_raw, L, step)
+  ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+  nearest = torch.empty(N, dtype=torch.float64, device=dev)
+  index = torch.empty(N, dtype=torch.int32, device=dev)
+  d2 = (torch.empty(N, S, dtype=torch.float64, device=dev)
+        if return_profile else None)
+  hip.call('cg_nearest_stretch', queries, N, L, C, queries.stride(0),
+           queries.stride(1), queries.stride(2), recording, T_raw,
+           recording.stride(0), recording.stride(1), int(step), exclude,
+           int(exclude_len), d2, nearest, index, ws, hip.stream())
+  return (nearest, index, d2) if return_profile else (nearest, index)
+
+
+def nearest_stretch_totals_device(queries, recording, step=1, exclude=None,
+                                  exclude_len=0, group_bytes=256 << 20):
+  """`nearest_stretch_device` with the queries walked in groups of as many
+  trials as hold `group_bytes` of float32 samples (one at least): device
+  (nearest float64 (N,), index int32 (N,)), the bits of the single call (a
+  query's result does not depend on its neighbours).  No host
+  synchronisation."""
+  import torch
+  N, L, C = queries.shape
+  group = max(int(group_bytes) // (L * C * 4), 1)
+  if exclude is not None and not torch.is_tensor(exclude):
+    exclude = torch.as_tensor(np.asarray(exclude).astype(np.int32))
+  parts = [
+      nearest_stretch_device(queries[i:i + group], recording, step,
+                             None if exclude is None else exclude[i:i + group],
+                             exclude_len) for i in range(0, N, group)
+  ]
+  return (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]))
+
+
+def recorded_starts(S, n, step):
+  """The start rows of the n recorded stretches --novelty_metrics measures:
+  v_i = step floor(i (S - 1) / max(n - 1, 1)), on the offset grid, spread over
+  the recording."""
+  i = np.arange(int(n), dtype=np.int64)
+  return int(step) * ((i * (int(S) - 1)) // max(int(n) - 1, 1))
+
+
+def _host(x):
+  return np.asarray(x.cpu() if hasattr(x, 'cpu') else x)
+
+
+def novelty_scores(recorded, generated, L, C, step, offsets=None):
+  """How close the generated trials come to the recording, read against how
+  close the recording comes to itself.  `recorded` and `generated` are (nearest,
+  index) of `nearest_stretch` (either device): of stretches of the recording
+  with their own neighbourhood excluded, and of generated trials.  With rms =
+  sqrt(nearest / (L C)), the distance per sample, NaNs left out:
+
+    nearest_rms            {recorded, generated}: [min, median, max]
+    nearest_rms_ratio      median generated / median recorded
+    copied_fraction        share of generated trials below the recorded minimum
+    below_recorded_median  share below the recorded median; about 0.5 for a
+                           perfect generator
+    distinct_stretches     distinct nearest offsets among the generated trials /
+                           their number: a collapse onto one stretch shows here
+    step, offsets          as used (offsets: S, None if not given)
+    num_trials, undefined  [recorded, generated]; undefined counts the NaNs
+
+  A figure whose side is empty is NaN."""
+  nan = float('nan')
+  sides = []
+  for nearest, index in (recorded, generated):
+    nearest = _host(nearest).astype(np.float64).reshape(-1)
+    index = _host(index).astype(np.int64).reshape(-1)
+    if nearest.shape != index.shape:
+      raise ValueError('(nearest, index) of equal lengths expected')
+    ok = ~np.isnan(nearest)
+    sides.append((np.sqrt(nearest[ok] / (float(L) * float(C))), index[ok],
+                  int(nearest.size), int((~ok).sum())))
+  (rec, _, n_rec, bad_rec), (gen, gen_at, n_gen, bad_gen) = sides
+
+  def spread(x):
+    return ([float(x.min()), float(np.median(x)), float(x.max())]
+            if x.size else [nan, nan, nan])
+
+  both = rec.size > 0 and gen.size > 0
+  return {
+      'nearest_rms': {'recorded': spread(rec), 'generated': spread(gen)},
+      'nearest_rms_ratio': (float(np.median(gen) / np.median(rec))
+                            if both else nan),
+      'copied_fraction': float((gen < rec.min()).mean()) if both else nan,
+      'below_recorded_median': (float((gen < np.median(rec)).mean())
+                                if both else nan),
+      'distinct_stretches': (float(len(np.unique(gen_at))) / gen_at.size
+                             if gen_at.size else nan),
+      'step': int(step),
+      'offsets': None if offsets is None else int(offsets),
+      'num_trials': [n_rec, n_gen],
+      'undefined': [bad_rec, bad_gen],
+  }

@@ -15,6 +15,7 @@ the reference's compute_metrics.py (BASELINE configs[3]: recorded-data pipeline
   python compute_metrics.py --output_dir runs/001 [--all_epochs]
       [--device gpu [--batch_trials 128]] [--victor_purpura [--vp_q 1.0]]
       [--temporal_metrics [--max_lag 24]] [--spectral_metrics]
+      [--novelty_metrics [--novelty_step 2]]
 
 --device gpu (not a reference flag) takes the deconvolution, the firing rates,
 the per-trial correlations and the van Rossum matrices through the HIP kernels
@@ -61,6 +62,28 @@ transform), cg_trace_psd (csrc/trace_psd.hip) on the device in batches of
 --batch_trials (a float32 transform), the recorded side's kept across epochs.
 Unlike `temporal`, the two devices' dicts agree to the rounding of a float32
 transform (about 1e-6 dB), not bit for bit.
+
+--novelty_metrics [--novelty_step k] (not reference flags, absent from the
+namespace unless given) adds `novelty`: signals_metrics.novelty_scores.  Every
+other figure of the report is best for a generator that plays stretches of the
+training recording back; this one tells such a copy from a generator that has
+learned the distribution.  It needs the run's input_dir (hparams.json) to be a
+recording directory (data/recording.py: info['recording']) and raises a
+ValueError for anything else.  For the first num_samples trials of `signals` of
+the generated file, the squared distance to the nearest stretch of the recording
+(raw units, which are the units of the generated files) on the grid of
+--novelty_step rows (default: the dataset's stride), no offset excluded; for
+num_samples stretches of the recording itself, spread evenly over the grid, the
+same with the offsets that overlap the stretch excluded -- computed once and kept
+across epochs.  The report holds both as RMS distances per sample, their ratio,
+the share of generated trials below the recorded minimum (`copied_fraction`) and
+median, and the share of distinct nearest offsets.  signals_metrics.
+nearest_stretch(expanded=True) on the host (a float64 matmul against a strided
+view of the recording), cg_nearest_stretch (csrc/nearest_stretch.hip: float64
+MFMA, the recording's rows staged in LDS, no window materialised) on the device
+in batches of --batch_trials with the recording uploaded once.  The two devices
+agree to float64 summation rounding, not bit for bit; an index may differ where
+two stretches lie that close to each other.
 
 The KL is the reference's: both samples cut into 30 equal-width bins over their
 pooled range by pandas.cut, empty bins replaced by 1e-10 (:80-111) -- pandas is
@@ -315,6 +338,73 @@ def spectral_report(hparams, filename, totals):
   return scores
 
 
+def novelty_recording(hparams):
+  """--novelty_metrics: (raw (T_raw, C) float32, L, step) of the recording the
+  run was trained on, in raw units -- the units of the generated files
+  (utils.save_fake_signals denormalises, and for an FFT recording the files
+  hold traces).  Kept across epochs."""
+  kept = getattr(hparams, '_novelty_recording', None)
+  if kept is not None:
+    return kept
+  from calciumgan_amd.data import recording
+  input_dir = getattr(hparams, 'input_dir', None)
+  info = None
+  if input_dir and os.path.exists(os.path.join(input_dir, 'info.pkl')):
+    with open(os.path.join(input_dir, 'info.pkl'), 'rb') as f:
+      info = pickle.load(f)
+  if not (info and info.get('recording') and
+          os.path.exists(os.path.join(input_dir, recording.FILENAME))):
+    raise ValueError(
+        '--novelty_metrics needs the run\'s input_dir to be a recording '
+        'directory (info[\'recording\'], {}); {!r} is not one'.format(
+            recording.FILENAME, input_dir))
+  raw = np.ascontiguousarray(recording.load(input_dir)['raw'], dtype=np.float32)
+  step = int(getattr(hparams, 'novelty_step', info['stride']))
+  if step < 1:
+    raise ValueError('--novelty_step must be at least 1')
+  hparams._novelty_recording = (raw, int(info['sequence_length']), step)
+  return hparams._novelty_recording
+
+
+def novelty_nearest_host(hparams, queries, exclude, exclude_len):
+  """(nearest, index) of float32 host trials: the expanded form on the host."""
+  raw, _, step = novelty_recording(hparams)
+  return signals_metrics.nearest_stretch(queries, raw, step, exclude,
+                                         exclude_len, expanded=True)
+
+
+def novelty_report(hparams, filename, nearest):
+  """--novelty_metrics: signals_metrics.novelty_scores of the first num_samples
+  trials of `filename` against num_samples stretches of the recording itself,
+  each with the offsets that overlap it excluded; nearest(hparams, queries,
+  exclude, exclude_len) -> (nearest, index), the recorded side's kept across
+  epochs."""
+  raw, L, step = novelty_recording(hparams)
+  C = raw.shape[1]
+  S = signals_metrics.stretch_offsets(len(raw), L, step)
+  frames, neurons = np.shape(h5_helper.get(filename, name='signals', trial=0))
+  if frames != L or neurons != C:
+    raise ValueError('{} holds trials of {} frames of {} neurons, the recording '
+                     'stretches of {} of {}'.format(filename, frames, neurons,
+                                                    L, C))
+  fake = _trial_signals(hparams, filename)
+  real = getattr(hparams, '_recorded_novelty', None)
+  if real is None:  # the recording is the same for every epoch
+    starts = signals_metrics.recorded_starts(S, hparams.num_samples, step)
+    windows = np.lib.stride_tricks.sliding_window_view(raw, L, axis=0)
+    queries = windows[starts].transpose(0, 2, 1)   # (n, L, C) views of raw
+    real = hparams._recorded_novelty = tuple(
+        signals_metrics._host(x) for x in nearest(hparams, queries, starts, L))
+  got = tuple(signals_metrics._host(x) for x in nearest(hparams, fake, None, 0))
+  scores = signals_metrics.novelty_scores(real, got, L, C, step, offsets=S)
+  if hparams.verbose:
+    for name, label in (('nearest_rms_ratio', 'nearest rms    gen / rec'),
+                        ('copied_fraction', 'copied fraction        '),
+                        ('distinct_stretches', 'distinct stretches     ')):
+      print('\t{}: {:.04g}'.format(label, scores[name]))
+  return scores
+
+
 def compute_epoch_spike_metrics(hparams, filename, epoch):
   """:483-497 without plot_signals / raster_plots: dict of the statistics."""
   if not h5_helper.contains(filename, 'spikes'):
@@ -350,6 +440,8 @@ def compute_epoch_spike_metrics(hparams, filename, epoch):
     out['temporal'] = temporal_report(hparams, filename, temporal_totals_host)
   if getattr(hparams, 'spectral_metrics', False):
     out['spectral'] = spectral_report(hparams, filename, spectral_totals_host)
+  if getattr(hparams, 'novelty_metrics', False):
+    out['novelty'] = novelty_report(hparams, filename, novelty_nearest_host)
   return out
 
 
@@ -541,6 +633,28 @@ def spectral_totals_device(hparams, filename):
   return (totals.cpu().numpy(), len(signals)), signals.shape[1]
 
 
+def novelty_nearest_device(hparams, queries, exclude, exclude_len):
+  """`novelty_nearest_host` through cg_nearest_stretch, a batch of trials at a
+  time against the recording uploaded once; the batches' (nearest, index) are
+  joined on the device and brought to the host once."""
+  import torch
+  raw, _, step = novelty_recording(hparams)
+  dev_raw = getattr(hparams, '_novelty_recording_device', None)
+  if dev_raw is None:
+    dev_raw = hparams._novelty_recording_device = torch.from_numpy(raw).to(
+        _device())
+  size = max(int(getattr(hparams, 'batch_trials', 128)), 1)
+  nearest, index = [], []
+  for i, batch in enumerate(_batches(hparams, queries)):
+    part = None if exclude is None else np.asarray(
+        exclude[i * size:(i + 1) * size], dtype=np.int32)
+    n, at = signals_metrics.nearest_stretch_totals_device(
+        batch, dev_raw, step, part, exclude_len)
+    nearest.append(n)
+    index.append(at)
+  return torch.cat(nearest).cpu().numpy(), torch.cat(index).cpu().numpy()
+
+
 def compute_epoch_spike_metrics_device(hparams, filename, epoch):
   """`compute_epoch_spike_metrics` with the statistics from the device; the
   histograms behind the KL from cg_pair_histogram (`device_kl`) unless
@@ -581,6 +695,8 @@ def compute_epoch_spike_metrics_device(hparams, filename, epoch):
     out['temporal'] = temporal_report(hparams, filename, temporal_totals_device)
   if getattr(hparams, 'spectral_metrics', False):
     out['spectral'] = spectral_report(hparams, filename, spectral_totals_device)
+  if getattr(hparams, 'novelty_metrics', False):
+    out['novelty'] = novelty_report(hparams, filename, novelty_nearest_device)
   return out
 
 
@@ -666,6 +782,16 @@ def build_parser():
                       default=argparse.SUPPRESS,
                       help='also report `spectral`: power-spectrum figures of '
                       'the generated against the recorded calcium traces')
+  # (absent unless given, like --victor_purpura)
+  parser.add_argument('--novelty_metrics', action='store_true',
+                      default=argparse.SUPPRESS,
+                      help='also report `novelty`: the distance from every '
+                      'generated trial to the nearest stretch of the recording '
+                      'the run was trained on (a recording directory), against '
+                      'the recording\'s distance to itself')
+  parser.add_argument('--novelty_step', type=int, default=argparse.SUPPRESS,
+                      help='--novelty_metrics: rows between two stretches '
+                      '(default: the stride of the dataset)')
   return parser
 
 

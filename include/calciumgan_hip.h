@@ -958,6 +958,58 @@ int cg_trace_psd(const float* x, int B, int T, int C,
                  double* totals, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Nearest stretch of the recording to every trial (nearest_stretch.hip;
+ * compute_metrics.py --novelty_metrics: not in the reference, none of whose
+ * figures tells a generator that replays the recording from one that learned
+ * it).  Added under ABI 20; the same float32 / float64 code in both precision
+ * builds.
+ * ------------------------------------------------------------------------- */
+/* Squared distances from N query trials (N, L, C) to every stretch of L rows of
+ * a (T_raw, C) float32 recording that starts on the grid s_j = j step, j < S =
+ * (T_raw - L) / step + 1 (the numpy statement is
+ * signals_metrics.nearest_stretch):
+ *   d2[n * S + j] = sum_{t, c} (q[n][t][c] - raw[s_j + t][c])^2
+ * evaluated as (|q_n|^2 + W_j) - 2 sum q r with every term float64 (the float32
+ * products are exact there), clamped at 0; within 4 K 2^-53 (|q_n|^2 + W_j), K =
+ * L C, of the difference form, and equal to it bit for bit on data whose sums
+ * are exact.  A non-finite d2 is stored as NaN: a non-finite sample of a query
+ * spoils that query's row, a non-finite row of the recording the offsets whose
+ * stretch covers it, nothing else.
+ *   nearest[n] = the least finite d2[n][j] over the admitted j, index[n] the
+ *   lowest j that attains it; NaN and -1 where no admitted d2 is finite.
+ * Offset j is left out for query n when exclude is non-NULL, exclude[n] >= 0
+ * and |s_j - exclude[n]| < exclude_len (exclude: device int32 [N] of start
+ * rows, negative for none).  d2 holds every offset's distance, admitted or not.
+ * q at q[n * q_sn + t * q_st + c * q_sc], raw at raw[row * r_st + c * r_sc],
+ * strides in elements, any values; nothing is copied or padded.  d2 (may be
+ * NULL: then nothing of size N S is written outside ws) is float64 (N, S),
+ * nearest float64 [N], index int32 [N], all contiguous and written whole.
+ * Five launches on `stream`: squared norms of the queries and of the
+ * recording's rows, W_j as the sum of its own L rows (no difference of running
+ * sums), the products on v_mfma_f64_16x16x4_f64 with the recording's rows of a
+ * tile of 64 offsets staged in LDS once per chunk of K (while 63 step C + 64
+ * <= 18432; read from global memory beyond) and K split over up to 16
+ * workgroups whose partial sums [splits][N][S rounded up to 64] go to ws, their
+ * sum in split order with the minimum of every 1024 offsets, and an ordered
+ * pass over those.  The plan depends on the shape alone: no atomics, nothing to
+ * zero beforehand, no host sync, the same bits every call.
+ * cg_nearest_stretch_ws_bytes: bytes of `ws` (8-byte aligned; contents do not
+ * matter), -1 for a shape cg_nearest_stretch refuses.
+ * CG_EINVAL (nothing launched, nothing written): a NULL q, raw, nearest, index
+ * or ws, ws not 8-byte aligned, N, L, C or step < 1, L > T_raw, exclude_len <
+ * 0, N > 65535, L C > 2^30, T_raw C > 2^40, T_raw >= 2^31 - 64 (so S < 2^31),
+ * step > 2^20. */
+long long cg_nearest_stretch_ws_bytes(int N, int L, int C, long long T_raw,
+                                      int step);
+int cg_nearest_stretch(const float* q, int N, int L, int C,
+                       long long q_sn, long long q_st, long long q_sc,
+                       const float* raw, long long T_raw,
+                       long long r_st, long long r_sc, int step,
+                       const int* exclude, int exclude_len,
+                       double* d2, double* nearest, int* index,
+                       void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Recording datasets (windows.hip; the reference's generate_tfrecords.py cuts a
  * (neurons, T) recording into overlapping stride-2 windows and writes each one
  * out; here the recording stays resident and every step's windows are cut
