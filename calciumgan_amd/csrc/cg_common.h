@@ -77,6 +77,30 @@ struct CgPerDeviceFlag {
   void mark() { set[cg_device_index()].store(true, std::memory_order_release); }
 };
 
+// A kernel gets 64 KiB of dynamic LDS unasked: before a launch with more (up to
+// `bytes`), once per kernel instantiation and device.  0, or the HIP error.
+template <auto Kernel>
+inline int cg_allow_dynamic_lds(int bytes) {
+  static CgPerDeviceFlag attr_set;
+  if (attr_set.test()) return 0;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     bytes);
+  if (e != hipSuccess) return (int)e;
+  attr_set.mark();
+  return 0;
+}
+
+// The first item of a workgroup that walks its items grid-stride.  Workgroups
+// go to the 8 XCDs (one L2 each) in turn, so the grid is renumbered to give the
+// workgroups that share an L2 a run of consecutive items (speed only: any
+// placement computes the same).
+__device__ __forceinline__ int cg_xcd_first_item() {
+  if ((gridDim.x & 7) == 0)
+    return (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  return blockIdx.x;
+}
+
 __device__ __forceinline__ float act2f(uint16_t v) {
 #if CG_ACT_F16
   return (float)__builtin_bit_cast(_Float16, v);

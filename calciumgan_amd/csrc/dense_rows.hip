@@ -517,14 +517,8 @@ __global__ __launch_bounds__(kWideThreads, KSTEPS <= 4 ? 2 : 1) void dense_rows_
 template <int KSTEPS>
 int launch_dense_wide(const DenseWideArgs& a, hipStream_t s) {
   const size_t lds = (size_t)kWideCols * (KSTEPS * 64 + 16);
-  static CgPerDeviceFlag attr_set;
-  if (!attr_set.test()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&dense_rows_wide_kernel<KSTEPS>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set.mark();
-  }
+  if (int e = cg_allow_dynamic_lds<&dense_rows_wide_kernel<KSTEPS>>(160 * 1024))
+    return e;
   // one workgroup per CU (two at K = 128): 8 XCDs x (32 / panels) row groups x panels
   const int per_xcd = (KSTEPS <= 4 ? 64 : 32) / a.panels * a.panels;
   hipLaunchKernelGGL(dense_rows_wide_kernel<KSTEPS>, dim3(8 * per_xcd),

@@ -1,13 +1,18 @@
-// The butterfly stages shared by the inverse transform of generated spectra
-// (ifft.hip) and the forward transform of recording windows (windows.hip):
-// radix-4 decimation in frequency in LDS with one radix-2 stage when log2 T is
-// odd, on the swizzled [T][G] image and with the quarter-circle twiddle table
-// described at the top of ifft.hip.  The twiddles are e^{+2 pi i k / T}: the
-// forward transform of a real trace runs the same stages and conjugates the
-// result.
+// What the three FFT kernels share -- the inverse transform of generated spectra
+// (ifft.hip), the forward transform of recording windows (windows.hip) and the
+// trace power spectra (trace_psd.hip): radix-4 decimation in frequency in LDS
+// with one radix-2 stage when log2 T is odd, on the swizzled [T][G] image and
+// with the quarter-circle twiddle table described at the top of ifft.hip.  The
+// twiddles are e^{+2 pi i k / T}: the forward transform of a real trace runs the
+// same stages and conjugates the result.  The butterflies, the index functions,
+// the order of the stages (fft_for_each_stage) and a lane's walk through one
+// stage (fft_stage) are stated here once; tests/fft_stages_host.cc runs them on
+// the host as the kernels do.  (trace_psd.hip keeps the walk written out, and
+// says why.)
 #ifndef CG_FFT_STAGES_H_
 #define CG_FFT_STAGES_H_
 
+#include <stddef.h>
 
 #if defined(__HIPCC__)
 #define CG_IFFT_FN __host__ __device__ __forceinline__
@@ -19,14 +24,31 @@ namespace {
 
 constexpr int kIfftMaxGroup = 16;       // neurons per workgroup at most
 constexpr int kIfftTraceElems = 8192;   // complex elements of LDS per workgroup
+constexpr int kFftMinT = 32, kFftMaxT = 8192;
+// Lanes of a workgroup, and the butterflies whose LDS reads a lane has in flight
+// before it finishes the first (at 16 waves a CU nothing else hides their
+// latency), of ifft.hip, windows.hip and trace_psd.hip
+constexpr int kIfftThreads = 512, kIfftBflyBatch = 4;
+constexpr int kWinFftThreads = 512, kWinBflyBatch = 4;
+constexpr int kPsdThreads = 512, kPsdBflyBatch = 2;
 
 struct cf32 {
   float re, im;
 };
 
+// the lengths the kernels take: a power of two in kFftMinT .. kFftMaxT
+CG_IFFT_FN bool fft_length_ok(int T) {
+  return T >= kFftMinT && T <= kFftMaxT && !(T & (T - 1));
+}
+
 CG_IFFT_FN int ifft_group(int T) {
   const int g = kIfftTraceElems / T;
   return g > kIfftMaxGroup ? kIfftMaxGroup : g;
+}
+
+// bytes of the [T][G] image and the T / 4 twiddles behind it
+CG_IFFT_FN size_t fft_lds_bytes(int T) {
+  return ((size_t)T * ifft_group(T) + T / 4) * sizeof(cf32);
 }
 
 // LDS row of logical row t; rows_mask = 32 / G - 1
@@ -120,6 +142,82 @@ CG_IFFT_FN void ifft_radix4(cf32* buf, const cf32* tw, int T, int G, int rows_ma
   ifft_radix4_load(f, buf, G, rows_mask, N, j, g);
   ifft_radix4_finish(f, tw, T, N);
 }
+
+// The stages in their order: f(0) for the radix-2 stage over the whole trace
+// when log2 T is odd, then f(N) for the radix-4 stages on blocks of N = T or
+// T / 2, ..., 16, 4 rows.
+template <class F>
+CG_IFFT_FN void fft_for_each_stage(int T, int odd, F&& f) {
+  int N = T;
+  if (odd) {
+    f(0);
+    N = T / 2;
+  }
+  for (; N >= 4; N >>= 2) f(N);
+}
+
+// One stage as lane `lane` of THREADS runs it: butterfly idx = j G + g is that
+// of ifft_radix2_load / ifft_radix4_load (the neuron index running fastest over
+// the lanes); the lane takes lane + u THREADS, u < BATCH, issues their loads
+// together, finishes them, and strides on by THREADS BATCH.
+template <int THREADS, int BATCH>
+CG_IFFT_FN void fft_stage(cf32* buf, const cf32* tw, int T, int G, int rows_mask,
+                          int stage, int lane) {
+  const int gshift = __builtin_ctz((unsigned)G);
+  const int count = T * G / (stage ? 4 : 2);
+  for (int first = lane; first < count; first += THREADS * BATCH) {
+    IfftBfly f[BATCH];
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) {
+      const int idx = first + u * THREADS;
+      if (idx < count) {  // (the same in every lane)
+        if (stage)
+          ifft_radix4_load(f[u], buf, G, rows_mask, stage, idx >> gshift, idx & (G - 1));
+        else
+          ifft_radix2_load(f[u], buf, T, G, rows_mask, idx >> gshift, idx & (G - 1));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u)
+      if (first + u * THREADS < count) {
+        if (stage)
+          ifft_radix4_finish(f[u], tw, T, stage);
+        else
+          ifft_radix2_finish(f[u], tw, T);
+      }
+  }
+}
+
+// between two stages every lane of the workgroup meets (the host runs the
+// lanes of a stage one after the other)
+CG_IFFT_FN void fft_barrier() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __syncthreads();
+#endif
+}
+
+// Every stage in order, each followed by the barrier, for one lane.
+template <int THREADS, int BATCH>
+CG_IFFT_FN void fft_run_stages(cf32* buf, const cf32* tw, int T, int G,
+                               int rows_mask, int odd, int lane) {
+  fft_for_each_stage(T, odd, [&](int stage) {
+    fft_stage<THREADS, BATCH>(buf, tw, T, G, rows_mask, stage, lane);
+    fft_barrier();
+  });
+}
+
+#if defined(__HIPCC__)
+// tw[k] = e^{2 pi i k / T}, k < T / 4: sincospi in float64 rounded once to
+// float32 (the caller's barrier comes before the first stage)
+template <int THREADS>
+__device__ __forceinline__ void fft_fill_twiddles(cf32* tw, int T, int lane) {
+  for (int k = lane; k < T / 4; k += THREADS) {
+    double s, c;
+    sincospi(2.0 * (double)k / (double)T, &s, &c);
+    tw[k] = cf32{(float)c, (float)s};
+  }
+}
+#endif
 
 // Time index held by row p after the last stage: with u = q0 + 2 (q1 + 4 (q2 +
 // ...)) (q0 only when log2 T is odd), p = q0 T/2 + q1 T/8 + q2 T/32 + ...

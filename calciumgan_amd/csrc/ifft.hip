@@ -35,8 +35,6 @@
 
 namespace {
 
-constexpr int kIfftThreads = 512;
-constexpr int kIfftMinT = 32, kIfftMaxT = 8192;
 constexpr int kIfftMaxGrid = 1024;      // workgroups; beyond: grid-stride
 
 // x scale + offset, the product and the sum rounded to float32 one after the
@@ -61,11 +59,9 @@ struct IfftArgs {
   float scale, offset, inv_T;
 };
 
-// (batches: a lane issues the global loads, or the LDS reads, of kIfft*Batch
-// elements before it uses the first -- at 16 waves a CU nothing else hides
-// their latency)
+// (a lane issues the global loads, or the LDS reads, of kIfftLoadBatch elements
+// before it uses the first, as with the butterflies of kIfftBflyBatch)
 constexpr int kIfftLoadBatch = 8;
-constexpr int kIfftBflyBatch = 4;
 
 __global__ __launch_bounds__(kIfftThreads) void ifft_channels_kernel(IfftArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ifft_lds[];
@@ -76,21 +72,11 @@ __global__ __launch_bounds__(kIfftThreads) void ifft_channels_kernel(IfftArgs a)
   const int gshift = __builtin_ctz(G);
   const int elems = T * G;  // 512 at least, a power of two
 
-  for (int k = tid; k < T / 4; k += kIfftThreads) {
-    double s, c;
-    sincospi(2.0 * (double)k / (double)T, &s, &c);
-    tw[k] = cf32{(float)c, (float)s};
-  }
+  fft_fill_twiddles<kIfftThreads>(tw, T, tid);
 
-  // Consecutive items are neighbouring neuron groups of one sample: at G = 4
-  // eight of them share every 128-byte line of a time row.  Workgroups go to
-  // the 8 XCDs (one L2 each) in turn, so the grid is renumbered to give the
-  // workgroups that share an L2 a run of consecutive items (speed only: any
-  // placement computes the same).
-  int first_item = blockIdx.x;
-  if ((gridDim.x & 7) == 0)
-    first_item = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  for (long long item = first_item; item < a.items; item += gridDim.x) {
+  // (consecutive items are neighbouring neuron groups of one sample: at G = 4
+  // eight of them share every 128-byte line of a time row)
+  for (long long item = cg_xcd_first_item(); item < a.items; item += gridDim.x) {
     const int b = (int)(item / a.groups);
     const int c0 = (int)(item - (long long)b * a.groups) * G;
     const float* xb = a.x + (long long)b * a.s_b;
@@ -126,40 +112,8 @@ __global__ __launch_bounds__(kIfftThreads) void ifft_channels_kernel(IfftArgs a)
     }
     __syncthreads();
 
-    int N = T;
-    if (a.odd) {
-      const int count = elems / 2;
-      for (int first = tid; first < count; first += kIfftThreads * kIfftBflyBatch) {
-        IfftBfly f[kIfftBflyBatch];
-#pragma unroll
-        for (int u = 0; u < kIfftBflyBatch; ++u) {
-          const int idx = first + u * kIfftThreads;
-          if (idx < count)
-            ifft_radix2_load(f[u], buf, T, G, rows_mask, idx >> gshift, idx & (G - 1));
-        }
-#pragma unroll
-        for (int u = 0; u < kIfftBflyBatch; ++u)
-          if (first + u * kIfftThreads < count) ifft_radix2_finish(f[u], tw, T);
-      }
-      __syncthreads();
-      N = T / 2;
-    }
-    for (; N >= 4; N >>= 2) {
-      const int count = elems / 4;
-      for (int first = tid; first < count; first += kIfftThreads * kIfftBflyBatch) {
-        IfftBfly f[kIfftBflyBatch];
-#pragma unroll
-        for (int u = 0; u < kIfftBflyBatch; ++u) {
-          const int idx = first + u * kIfftThreads;
-          if (idx < count)
-            ifft_radix4_load(f[u], buf, G, rows_mask, N, idx >> gshift, idx & (G - 1));
-        }
-#pragma unroll
-        for (int u = 0; u < kIfftBflyBatch; ++u)
-          if (first + u * kIfftThreads < count) ifft_radix4_finish(f[u], tw, T, N);
-      }
-      __syncthreads();
-    }
+    fft_run_stages<kIfftThreads, kIfftBflyBatch>(buf, tw, T, G, rows_mask, a.odd,
+                                                 tid);
 
     for (int first = tid; first < elems; first += kIfftThreads * kIfftLoadBatch) {
       float v[kIfftLoadBatch];
@@ -183,10 +137,6 @@ __global__ __launch_bounds__(kIfftThreads) void ifft_channels_kernel(IfftArgs a)
   }
 }
 
-inline size_t ifft_lds_bytes(int T) {
-  return ((size_t)T * ifft_group(T) + T / 4) * sizeof(cf32);
-}
-
 }  // namespace
 
 extern "C" int cg_ifft_channels(const float* x, int B, int T, int C,
@@ -194,8 +144,7 @@ extern "C" int cg_ifft_channels(const float* x, int B, int T, int C,
                                 float scale, float offset, float* y,
                                 long long y_sb, long long y_st, long long y_sc,
                                 void* stream) {
-  if (!x || !y || B < 1 || C < 1 || T < kIfftMinT || T > kIfftMaxT ||
-      (T & (T - 1)))
+  if (!x || !y || B < 1 || C < 1 || !fft_length_ok(T))
     return CG_EINVAL;
   const int G = ifft_group(T);
   IfftArgs a;
@@ -208,18 +157,12 @@ extern "C" int cg_ifft_channels(const float* x, int B, int T, int C,
   a.scale = scale; a.offset = offset;
   a.inv_T = 1.0f / (float)T;  // a power of two: exact
   // up to 80 KiB of dynamic LDS (T = 8192): above the 64 KiB a kernel gets unasked
-  static CgPerDeviceFlag attr_set;
-  if (!attr_set.test()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&ifft_channels_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)ifft_lds_bytes(kIfftMaxT));
-    if (e != hipSuccess) return (int)e;
-    attr_set.mark();
-  }
+  if (int e = cg_allow_dynamic_lds<&ifft_channels_kernel>(
+          (int)fft_lds_bytes(kFftMaxT)))
+    return e;
   const unsigned grid =
       (unsigned)(a.items < kIfftMaxGrid ? a.items : kIfftMaxGrid);
   hipLaunchKernelGGL(ifft_channels_kernel, dim3(grid), dim3(kIfftThreads),
-                     ifft_lds_bytes(T), cg_stream(stream), a);
+                     fft_lds_bytes(T), cg_stream(stream), a);
   CG_LAUNCH_CHECK();
 }

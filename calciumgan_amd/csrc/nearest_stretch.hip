@@ -403,15 +403,9 @@ hipError_t ns_launch_gemm(const NsArgs& a, const NsPlan& p, hipStream_t stream) 
   if (STAGED) {
     lds = ((size_t)(kNsTileS - 1) * a.jstride + (size_t)p.chunk_steps * kNsGroup) *
           sizeof(float);
-    static CgPerDeviceFlag attr_set;
-    if (!attr_set.test()) {
-      hipError_t e = hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&ns_gemm_kernel<QFLAT, STAGED>),
-          hipFuncAttributeMaxDynamicSharedMemorySize,
-          (int)(kNsLdsFloats * sizeof(float)));
-      if (e != hipSuccess) return e;
-      attr_set.mark();
-    }
+    if (int e = cg_allow_dynamic_lds<&ns_gemm_kernel<QFLAT, STAGED>>(
+            (int)(kNsLdsFloats * sizeof(float))))
+      return (hipError_t)e;
   }
   hipLaunchKernelGGL((ns_gemm_kernel<QFLAT, STAGED>),
                      dim3((unsigned)p.tilesS, p.tilesN, p.splits), dim3(kNsThreads),

@@ -1410,15 +1410,9 @@ template <int R, int WM, int WN, int MT, bool LN = false, bool NRW = false,
           int EPI = kEpiGeneric>
 int launch_swp(const SwpArgs& pa, unsigned gy, size_t lds, bool dry, hipStream_t s) {
   if (dry) return 0;
-  static CgPerDeviceFlag attr_set;
-  if (!attr_set.test()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(
-            &swconv_swp_kernel<R, WM, WN, MT, LN, NRW, EPI>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set.mark();
-  }
+  if (int e = cg_allow_dynamic_lds<&swconv_swp_kernel<R, WM, WN, MT, LN, NRW, EPI>>(
+          160 * 1024))
+    return e;
   // persistent workgroups: one resident set walks all tiles (a multiple of 8
   // workgroups, so each keeps its XCD residue over its tiles)
   long long slots =

@@ -48,9 +48,7 @@
 
 namespace {
 
-constexpr int kPsdThreads = 512;
 constexpr int kPsdWaves = kPsdThreads / 64;
-constexpr int kPsdMinT = 32, kPsdMaxT = 8192;
 constexpr int kPsdMaxGrid = 1024;      // workgroups; beyond: grid-stride
 constexpr int kPsdMaxCols = 2 * kIfftMaxGroup;
 // positions with bin < T / 2 per lane at most, and the one of bin T / 2
@@ -62,7 +60,6 @@ constexpr int kPsdTargetItems = 512;
 constexpr int kPsdMaxChunks = 64;
 constexpr int kPsdMinChunk = 4;
 constexpr int kPsdLoadBatch = 4;
-constexpr int kPsdBflyBatch = 2;
 constexpr int kPsdFinishThreads = 256;
 
 struct PsdPlan {
@@ -117,11 +114,7 @@ __global__ __launch_bounds__(kPsdThreads, 4) void trace_psd_kernel(PsdArgs a) {
   const int floats = 2 * elems;
   const int bins = T / 2 + 1;
 
-  for (int k = tid; k < T / 4; k += kPsdThreads) {
-    double s, c;
-    sincospi(2.0 * (double)k / (double)T, &s, &c);
-    tw[k] = cf32{(float)c, (float)s};
-  }
+  fft_fill_twiddles<kPsdThreads>(tw, T, tid);
   for (int k = tid; k <= T / 2; k += kPsdThreads)
     win[k] = (float)(0.5 - 0.5 * cospi(2.0 * (double)k / (double)T));
 
@@ -138,12 +131,8 @@ __global__ __launch_bounds__(kPsdThreads, 4) void trace_psd_kernel(PsdArgs a) {
   const int col = tid & (cols - 1);
   const int lane = tid & 63, wave = tid >> 6;
 
-  // (consecutive items are neighbouring neuron groups of one chunk: the
-  // renumbering of ifft.hip, speed only)
-  int first_item = blockIdx.x;
-  if ((gridDim.x & 7) == 0)
-    first_item = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  for (long long item = first_item; item < a.items; item += gridDim.x) {
+  // (consecutive items are neighbouring neuron groups of one chunk)
+  for (long long item = cg_xcd_first_item(); item < a.items; item += gridDim.x) {
     const int chunk = (int)(item / a.groups);
     const int c0 = (int)(item - (long long)chunk * a.groups) * cols;
     const int b0 = chunk * a.chunk_len;
@@ -225,6 +214,12 @@ __global__ __launch_bounds__(kPsdThreads, 4) void trace_psd_kernel(PsdArgs a) {
       }
       __syncthreads();
 
+      // fft_run_stages<kPsdThreads, kPsdBflyBatch>(..., lt), written out: called
+      // through the driver the stages are the same and two spills fewer, but
+      // hipcc then fuses dr * dr + si * si of the unpacking below as fma(si, si,
+      // dr * dr) in every slot, where this text gets fma(dr, dr, si * si) in the
+      // later ones, and a few totals in a thousand move by an ulp
+      // (profiles/fft_schedule_once.txt).
       int N = T;
       if (a.odd) {
         const int count = elems / 2;
@@ -312,15 +307,14 @@ __global__ __launch_bounds__(kPsdFinishThreads) void trace_psd_finish_kernel(
 }
 
 inline size_t psd_lds_bytes(int T) {
-  return ((size_t)T * ifft_group(T) + T / 4) * sizeof(cf32) +
-         (size_t)(T / 2 + 2) * sizeof(float) +
+  return fft_lds_bytes(T) + (size_t)(T / 2 + 2) * sizeof(float) +
          (size_t)kPsdWaves * kPsdMaxCols * sizeof(double) +
          (size_t)kPsdMaxCols * (sizeof(float) + 3 * sizeof(int)) +
          (size_t)(T / 2) * sizeof(unsigned short);
 }
 
 inline bool psd_shape_ok(int B, int T, int C) {
-  return B >= 1 && C >= 1 && T >= kPsdMinT && T <= kPsdMaxT && !(T & (T - 1));
+  return B >= 1 && C >= 1 && fft_length_ok(T);
 }
 
 }  // namespace
@@ -346,15 +340,8 @@ extern "C" int cg_trace_psd(const float* x, int B, int T, int C,
   a.odd = __builtin_ctz((unsigned)T) & 1;
   a.items = (long long)plan.chunks * plan.groups;
   // up to 106 KiB of dynamic LDS (T = 8192): above the 64 KiB a kernel gets unasked
-  static CgPerDeviceFlag attr_set;
-  if (!attr_set.test()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&trace_psd_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)psd_lds_bytes(kPsdMaxT));
-    if (e != hipSuccess) return (int)e;
-    attr_set.mark();
-  }
+  if (int e = cg_allow_dynamic_lds<&trace_psd_kernel>((int)psd_lds_bytes(kFftMaxT)))
+    return e;
   const unsigned grid =
       (unsigned)(a.items < kPsdMaxGrid ? a.items : kPsdMaxGrid);
   hipLaunchKernelGGL(trace_psd_kernel, dim3(grid), dim3(kPsdThreads),

@@ -1256,15 +1256,9 @@ inline unsigned wgrad_grid(const WgradArgs& a, int gz) {
 
 template <int R, int TPW, bool ROWSPLIT, bool PIPE, int TT, int ALLT = 0>
 int launch_wgrad1(const WgradArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  static CgPerDeviceFlag attr_set;
-  if (!attr_set.test()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(
-            &wgrad_kernel<R, TPW, ROWSPLIT, PIPE, TT, ALLT>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set.mark();
-  }
+  if (int e = cg_allow_dynamic_lds<&wgrad_kernel<R, TPW, ROWSPLIT, PIPE, TT, ALLT>>(
+          160 * 1024))
+    return e;
   CG_LAUNCH_PROF(CG_FAMILY_WGRAD, (wgrad_kernel<R, TPW, ROWSPLIT, PIPE, TT, ALLT>),
                  dim3(wgrad_grid(a, grid.z)), dim3(512), lds, s, a, (int)grid.z);
   CG_LAUNCH_CHECK();
@@ -1462,14 +1456,8 @@ int launch_plan(const WgradPlan& p, hipStream_t s) {
 
 template <int TPW, int ALLT = 1>
 int launch_multi(const WgradMulti& m, int blocks, size_t lds, hipStream_t s) {
-  static CgPerDeviceFlag attr_set;
-  if (!attr_set.test()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_multi_kernel<2, TPW, ALLT>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set.mark();
-  }
+  if (int e = cg_allow_dynamic_lds<&wgrad_multi_kernel<2, TPW, ALLT>>(160 * 1024))
+    return e;
   CG_LAUNCH_PROF(CG_FAMILY_WGRAD, (wgrad_multi_kernel<2, TPW, ALLT>), dim3(blocks),
                  dim3(512), lds, s, m);
   CG_LAUNCH_CHECK();
@@ -1919,14 +1907,8 @@ FlexPlan* flex_plan_for(const WgradPlan* plans, int n, int mode, hipStream_t s) 
 
 template <int TPW, int ALLT>
 int launch_flex(const WgradFlex& m, int blocks, size_t lds, hipStream_t s) {
-  static CgPerDeviceFlag attr_set;
-  if (!attr_set.test()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_flex_kernel<2, TPW, ALLT>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set.mark();
-  }
+  if (int e = cg_allow_dynamic_lds<&wgrad_flex_kernel<2, TPW, ALLT>>(160 * 1024))
+    return e;
   CG_LAUNCH_PROF(CG_FAMILY_WGRAD, (wgrad_flex_kernel<2, TPW, ALLT>), dim3(blocks),
                  dim3(512), lds, s, m);
   CG_LAUNCH_CHECK();

@@ -40,8 +40,6 @@ namespace {
 constexpr int kWinThreads = 256;       // plain
 constexpr int kWinItemElems = 4 * kWinThreads;
 constexpr int kWinMaxGrid = 2048;      // workgroups; beyond: grid-stride
-constexpr int kWinFftThreads = 512;
-constexpr int kWinFftMinL = 32, kWinFftMaxL = 8192;
 constexpr int kWinFftMaxGrid = 1024;   // workgroups; beyond: grid-stride
 
 // (v - sub) / div: the float32 difference, then the IEEE float32 quotient
@@ -125,10 +123,9 @@ __global__ __launch_bounds__(kWinThreads) void window_gather_kernel(WinArgs a) {
   }
 }
 
-// (batches: as in ifft.hip, a lane issues the global loads, or the LDS reads,
-// of a batch before it uses the first)
+// (as in ifft.hip, a lane issues the global loads, or the LDS reads, of a batch
+// before it uses the first)
 constexpr int kWinLoadBatch = 8;
-constexpr int kWinBflyBatch = 4;
 
 __global__ __launch_bounds__(kWinFftThreads) void window_fft_kernel(WinArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char win_lds[];
@@ -139,19 +136,10 @@ __global__ __launch_bounds__(kWinFftThreads) void window_fft_kernel(WinArgs a) {
   const int gshift = __builtin_ctz(G);
   const int elems = T * G;  // 512 at least, a power of two
 
-  for (int k = tid; k < T / 4; k += kWinFftThreads) {
-    double s, c;
-    sincospi(2.0 * (double)k / (double)T, &s, &c);
-    tw[k] = cf32{(float)c, (float)s};
-  }
+  fft_fill_twiddles<kWinFftThreads>(tw, T, tid);
 
-  // (consecutive items are neighbouring neuron groups of one window; the grid
-  // is renumbered so that the workgroups of one XCD take a run of them, as in
-  // ifft.hip: speed only)
-  int first_item = blockIdx.x;
-  if ((gridDim.x & 7) == 0)
-    first_item = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  for (long long item = first_item; item < a.items; item += gridDim.x) {
+  // (consecutive items are neighbouring neuron groups of one window)
+  for (long long item = cg_xcd_first_item(); item < a.items; item += gridDim.x) {
     const int b = (int)(item / a.groups);
     const int c0 = (int)(item - (long long)b * a.groups) * G;
     const long long start = a.starts[b];
@@ -181,40 +169,8 @@ __global__ __launch_bounds__(kWinFftThreads) void window_fft_kernel(WinArgs a) {
     }
     __syncthreads();
 
-    int N = T;
-    if (a.odd) {
-      const int count = elems / 2;
-      for (int first = tid; first < count; first += kWinFftThreads * kWinBflyBatch) {
-        IfftBfly f[kWinBflyBatch];
-#pragma unroll
-        for (int u = 0; u < kWinBflyBatch; ++u) {
-          const int idx = first + u * kWinFftThreads;
-          if (idx < count)
-            ifft_radix2_load(f[u], buf, T, G, rows_mask, idx >> gshift, idx & (G - 1));
-        }
-#pragma unroll
-        for (int u = 0; u < kWinBflyBatch; ++u)
-          if (first + u * kWinFftThreads < count) ifft_radix2_finish(f[u], tw, T);
-      }
-      __syncthreads();
-      N = T / 2;
-    }
-    for (; N >= 4; N >>= 2) {
-      const int count = elems / 4;
-      for (int first = tid; first < count; first += kWinFftThreads * kWinBflyBatch) {
-        IfftBfly f[kWinBflyBatch];
-#pragma unroll
-        for (int u = 0; u < kWinBflyBatch; ++u) {
-          const int idx = first + u * kWinFftThreads;
-          if (idx < count)
-            ifft_radix4_load(f[u], buf, G, rows_mask, N, idx >> gshift, idx & (G - 1));
-        }
-#pragma unroll
-        for (int u = 0; u < kWinBflyBatch; ++u)
-          if (first + u * kWinFftThreads < count) ifft_radix4_finish(f[u], tw, T, N);
-      }
-      __syncthreads();
-    }
+    fft_run_stages<kWinFftThreads, kWinBflyBatch>(buf, tw, T, G, rows_mask, a.odd,
+                                                  tid);
 
     for (int first = tid; first < elems; first += kWinFftThreads * kWinLoadBatch) {
       cf32 v[kWinLoadBatch];
@@ -240,10 +196,6 @@ __global__ __launch_bounds__(kWinFftThreads) void window_fft_kernel(WinArgs a) {
   }
 }
 
-inline size_t win_fft_lds_bytes(int L) {
-  return ((size_t)L * ifft_group(L) + L / 4) * sizeof(cf32);
-}
-
 inline bool win_aligned16(const void* p) {
   return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
@@ -259,8 +211,7 @@ extern "C" int cg_window_batch(const float* raw, long long T_raw, int C,
   if (!raw || !starts || !y || T_raw < 1 || C < 1 || B < 1 || L < 1 ||
       div == 0.0f)
     return CG_EINVAL;
-  if (fft && (L < kWinFftMinL || L > kWinFftMaxL || (L & (L - 1))))
-    return CG_EINVAL;
+  if (fft && !fft_length_ok(L)) return CG_EINVAL;
   WinArgs a;
   a.raw = raw; a.T_raw = T_raw; a.r_st = r_st; a.r_sc = r_sc;
   a.starts = starts;
@@ -288,18 +239,12 @@ extern "C" int cg_window_batch(const float* raw, long long T_raw, int C,
   a.odd = __builtin_ctz((unsigned)L) & 1;
   a.items = (long long)B * a.groups;
   // up to 80 KiB of dynamic LDS (L = 8192): above the 64 KiB a kernel gets unasked
-  static CgPerDeviceFlag attr_set;
-  if (!attr_set.test()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&window_fft_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)win_fft_lds_bytes(kWinFftMaxL));
-    if (e != hipSuccess) return (int)e;
-    attr_set.mark();
-  }
+  if (int e = cg_allow_dynamic_lds<&window_fft_kernel>(
+          (int)fft_lds_bytes(kFftMaxT)))
+    return e;
   const unsigned grid =
       (unsigned)(a.items < kWinFftMaxGrid ? a.items : kWinFftMaxGrid);
   hipLaunchKernelGGL(window_fft_kernel, dim3(grid), dim3(kWinFftThreads),
-                     win_fft_lds_bytes(L), cg_stream(stream), a);
+                     fft_lds_bytes(L), cg_stream(stream), a);
   CG_LAUNCH_CHECK();
 }

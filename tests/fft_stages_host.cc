@@ -10,6 +10,10 @@
 //       the whole schedule, one butterfly after the other, on n complex float32
 //       traces of T bins ([n][T][re, im]): the inverse transform, scaled by 1 / T
 //       and in time order, written in the same layout
+// The order of the stages (fft_for_each_stage), a lane's walk through a stage
+// (fft_stage) and the driver (fft_run_stages) are the header's, the ones the
+// kernels call; fft_run_stages<1, 1> with lane 0 is the schedule one butterfly
+// after the other.
 // A butterfly holds pointers into the image, so the image lies in the middle of
 // an arena three images long: an index up to one image out of range is seen by
 // the range check here, anything further by the sanitizer.
@@ -22,8 +26,6 @@
 #include "fft_stages.h"
 
 namespace {
-
-constexpr int kMinT = 32, kMaxT = 8192;
 
 int fail(const char* what, int T, long long at) {
   std::fprintf(stderr, "FAILED: %s (T = %d, at %lld)\n", what, T, at);
@@ -54,18 +56,6 @@ struct Image {
                               buf(arena.data() + elems) {}
 };
 
-// the stages of a kernel in its order: (radix, N) with N = 0 for the radix-2 one
-std::vector<int> schedule(const Geometry& s) {
-  std::vector<int> blocks;
-  int N = s.T;
-  if (s.odd) {
-    blocks.push_back(0);
-    N = s.T / 2;
-  }
-  for (; N >= 4; N >>= 2) blocks.push_back(N);
-  return blocks;
-}
-
 // butterfly idx of a stage, as a lane of any of the three kernels loads it
 int load(IfftBfly& f, cf32* buf, const Geometry& s, int N, int idx) {
   const int gshift = __builtin_ctz((unsigned)s.G);
@@ -78,18 +68,35 @@ int load(IfftBfly& f, cf32* buf, const Geometry& s, int N, int idx) {
   return 4;
 }
 
-void run_stages(cf32* buf, const cf32* tw, const Geometry& s) {
-  for (int N : schedule(s)) {
-    const int count = s.elems / (N == 0 ? 2 : 4);
-    for (int idx = 0; idx < count; ++idx) {
-      IfftBfly f;
-      load(f, buf, s, N, idx);
-      if (N == 0)
-        ifft_radix2_finish(f, tw, s.T);
-      else
-        ifft_radix4_finish(f, tw, s.T, N);
-    }
+// the schedule as a workgroup of THREADS lanes with batches of BATCH runs it:
+// stage by stage and, within a stage, lane by lane
+template <int THREADS, int BATCH>
+void run_stages_by_lanes(cf32* buf, const cf32* tw, const Geometry& s) {
+  fft_for_each_stage(s.T, s.odd, [&](int stage) {
+    for (int lane = 0; lane < THREADS; ++lane)
+      fft_stage<THREADS, BATCH>(buf, tw, s.T, s.G, s.rows_mask, stage, lane);
+  });
+}
+
+// a fixed pseudo-random image: 24 bits of a linear congruential generator per
+// component, in [-1, 1)
+void fill_pattern(cf32* buf, int elems) {
+  unsigned state = 12345u;
+  auto next = [&state] {
+    state = state * 1664525u + 1013904223u;
+    return (float)(state >> 8) * (1.0f / 8388608.0f) - 1.0f;
+  };
+  for (int e = 0; e < elems; ++e) {
+    buf[e].re = next();
+    buf[e].im = next();
   }
+}
+
+// the first element whose bytes differ, or -1
+long long first_difference(const cf32* a, const cf32* b, int elems) {
+  for (int e = 0; e < elems; ++e)
+    if (std::memcmp(a + e, b + e, sizeof(cf32))) return e;
+  return -1;
 }
 
 // log2(T) eta of tests/ifft_cases.py: higham_bound
@@ -160,7 +167,9 @@ int check(int T) {
   // disjoint and cover it (no barrier separates the butterflies of a stage)
   Image image(s.elems);
   std::vector<int> touched(s.elems);
-  for (int N : schedule(s)) {
+  std::vector<int> stages;
+  fft_for_each_stage(T, s.odd, [&](int N) { stages.push_back(N); });
+  for (int N : stages) {
     std::fill(touched.begin(), touched.end(), 0);
     const int legs = N == 0 ? 2 : 4, count = s.elems / legs;
     for (int idx = 0; idx < count; ++idx) {
@@ -213,7 +222,7 @@ int check(int T) {
     for (int e = 0; e < s.elems; ++e) image.buf[e] = cf32{0.f, 0.f};
     image.buf[ifft_phys(k0, s.rows_mask) * G + 0].re = 1.f;
     image.buf[ifft_phys(k0, s.rows_mask) * G + (G - 1)].im += 1.f;
-    run_stages(image.buf, tw.data(), s);
+    fft_run_stages<1, 1>(image.buf, tw.data(), T, G, s.rows_mask, s.odd, 0);
     double err0 = 0.0, err1 = 0.0;
     for (int p = 0; p < T; ++p) {
       const int t = ifft_time_of_row(p, T, s.odd);
@@ -237,14 +246,36 @@ int check(int T) {
     if (!(e0 <= higham_bound(T)) || !(e1 <= higham_bound(T)))
       return fail("the schedule on a one-hot bin is the float64 transform", T, k0);
   }
+
+  // the lanes of a workgroup run every butterfly of a stage exactly once: the
+  // schedule walked as the kernels' lanes walk it (ifft.hip and windows.hip;
+  // trace_psd.hip, whose written-out copy of the walk has fft_stage's guards
+  // and strides) leaves the bytes that one butterfly after the other leaves
+  // (a stage's butterflies are disjoint: a butterfly skipped or repeated shows)
+  static_assert(kWinFftThreads == kIfftThreads && kWinBflyBatch == kIfftBflyBatch,
+                "windows.hip walks a stage as ifft.hip does: one run covers both");
+  Image wide(s.elems), narrow(s.elems);
+  fill_pattern(image.buf, s.elems);
+  fill_pattern(wide.buf, s.elems);
+  fill_pattern(narrow.buf, s.elems);
+  fft_run_stages<1, 1>(image.buf, tw.data(), T, G, s.rows_mask, s.odd, 0);
+  run_stages_by_lanes<kIfftThreads, kIfftBflyBatch>(wide.buf, tw.data(), s);
+  run_stages_by_lanes<kPsdThreads, kPsdBflyBatch>(narrow.buf, tw.data(), s);
+  long long at = first_difference(image.buf, wide.buf, s.elems);
+  if (at >= 0)
+    return fail("the lanes of ifft.hip and windows.hip run the schedule", T, at);
+  at = first_difference(image.buf, narrow.buf, s.elems);
+  if (at >= 0) return fail("the lanes of trace_psd.hip run the schedule", T, at);
+
   std::printf("T %5d  G %2d  rows_mask %2d  stages %d  one-hot max e %.3g  "
-              "Higham bound %.3g\n", T, G, s.rows_mask, (int)schedule(s).size(),
-              worst, higham_bound(T));
+              "Higham bound %.3g  lane walks %dx%d %dx%d equal\n", T, G, s.rows_mask,
+              (int)stages.size(), worst, higham_bound(T), kIfftThreads,
+              kIfftBflyBatch, kPsdThreads, kPsdBflyBatch);
   return 0;
 }
 
 int transform(int T, int n, const char* in_path, const char* out_path) {
-  if (T < kMinT || T > kMaxT || (T & (T - 1)) || n < 1) return fail("arguments", T, n);
+  if (!fft_length_ok(T) || n < 1) return fail("arguments", T, n);
   const Geometry s(T);
   std::vector<float> x((size_t)n * T * 2), y((size_t)n * T * 2);
   std::FILE* in = std::fopen(in_path, "rb");
@@ -264,7 +295,7 @@ int transform(int T, int n, const char* in_path, const char* out_path) {
         }
         image.buf[ifft_phys(t, s.rows_mask) * s.G + g] = v;
       }
-    run_stages(image.buf, tw.data(), s);
+    fft_run_stages<1, 1>(image.buf, tw.data(), T, s.G, s.rows_mask, s.odd, 0);
     for (int p = 0; p < T; ++p) {
       const int t = ifft_time_of_row(p, T, s.odd);
       for (int g = 0; g < s.G && c0 + g < n; ++g) {
@@ -285,7 +316,7 @@ int transform(int T, int n, const char* in_path, const char* out_path) {
 
 int main(int argc, char** argv) {
   if (argc == 2 && !std::strcmp(argv[1], "check")) {
-    for (int T = kMinT; T <= kMaxT; T *= 2)
+    for (int T = kFftMinT; T <= kFftMaxT; T *= 2)
       if (check(T)) return 1;
     std::printf("all checks passed\n");
     return 0;

@@ -12,7 +12,10 @@ mirror-row table of trace_psd.hip inside [0, T); in every stage, the radix-2 one
 included, the butterflies' elements inside the image, pairwise disjoint and
 covering it (the only reason the stages need no barrier inside them); every
 leg's rows of an LDS lane group on distinct bank positions; one-hot bins under
-Higham's bound.
+Higham's bound; the schedule walked lane by lane as the kernels' 512 lanes walk
+it, with their batches of 4 and of 2 butterflies, leaving the bytes that one
+butterfly after the other leaves.  The order of the stages, a lane's walk and
+the driver are the header's own, the ones the kernels call.
 
 `ifft` runs the whole schedule one butterfly after the other on float32 spectra
 from a file; the result is held to np.fft.ifft in complex128 under
