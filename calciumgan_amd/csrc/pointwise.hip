@@ -1408,6 +1408,44 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(
   p[i] -= lr_t * mi / (sqrtf(vi) + eps);
 }
 
+// ---- moving average of a flat parameter buffer (algorithms/averaging.py) ----
+// ema = ema - fl(fl(ema - p) * om): three f32 operations, each rounded on its
+// own (no contraction into an fma), so the result is update_statement()'s bit for
+// bit.  12 bytes of traffic per element and nothing to reuse: the grid is
+// bounded and strides.  vec (both pointers 16-byte aligned): 16-byte loads and
+// stores over n / 4 quads, the n % 4 tail one element per lane.
+constexpr int kEmaMaxBlocks = 2048;
+
+__device__ __forceinline__ float ema_step(float e, float p, float om) {
+#pragma clang fp contract(off)
+  const float d = e - p;
+  const float s = d * om;
+  return e - s;
+}
+
+__global__ __launch_bounds__(kThreads) void ema_update_kernel(
+    float* __restrict__ ema, const float* __restrict__ p, long long n, float om,
+    int vec) {
+  const long long t = (long long)blockIdx.x * kThreads + threadIdx.x;
+  const long long stride = (long long)gridDim.x * kThreads;
+  long long done = 0;
+  if (vec) {
+    const long long n4 = n >> 2;
+    f32x4* __restrict__ e4 = reinterpret_cast<f32x4*>(ema);
+    const f32x4* __restrict__ p4 = reinterpret_cast<const f32x4*>(p);
+    for (long long i = t; i < n4; i += stride) {
+      f32x4 e = e4[i];
+      const f32x4 q = p4[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) e[k] = ema_step(e[k], q[k], om);
+      e4[i] = e;
+    }
+    done = n4 << 2;
+  }
+  for (long long i = done + t; i < n; i += stride)
+    ema[i] = ema_step(ema[i], p[i], om);
+}
+
 // ---- dynamic loss scaling (mixed_float16: optimizer.py:10-12,23-29) ---------
 // state ls[4] = {scale S, consecutive finite steps, applied Adam steps t,
 // "gradients finite" flag of the update in progress (1 between updates)}
@@ -2147,6 +2185,17 @@ extern "C" int cg_adam(float* p, const float* grad, float* m, float* v,
   hipLaunchKernelGGL(adam_kernel, dim3(grid1d(n, kThreads, 1LL << 31)),
                      dim3(kThreads), 0, cg_stream(stream), p, grad, m, v, n, lr_t,
                      beta1, beta2, eps, grad_scale, lr_t_dev);
+  CG_LAUNCH_CHECK();
+}
+
+extern "C" int cg_ema_update(float* ema, const float* p, long long n, float om,
+                             void* stream) {
+  if (!ema || !p || n < 1 || !(om >= 0.f && om <= 1.f)) return CG_EINVAL;
+  const int vec = (((uintptr_t)ema | (uintptr_t)p) & 15) == 0;
+  const long long work = vec ? (n + 3) / 4 : n;
+  hipLaunchKernelGGL(ema_update_kernel,
+                     dim3(grid1d(work, kThreads, kEmaMaxBlocks)), dim3(kThreads), 0,
+                     cg_stream(stream), ema, p, n, om, vec);
   CG_LAUNCH_CHECK();
 }
 

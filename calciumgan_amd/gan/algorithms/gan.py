@@ -23,6 +23,7 @@ GAN is also the base of every algorithm: train() is a template over the
 per-class pieces (_build_state, _segments, _fill_stage, _adam_steps,
 _graph_under_dp) that replay.py drives, eagerly or as hipGraph replays.
 """
+import contextlib
 import os
 
 import torch
@@ -30,6 +31,7 @@ import torch
 from ... import _lib
 from ... import nets
 from ... import parallel
+from . import averaging
 from . import draws
 from . import replay
 from .optimizer import Optimizer
@@ -84,6 +86,12 @@ class GAN(object):
       raise ValueError('generator and discriminator differ in precision')
     self.gen_optimizer = Optimizer(hparams, self.device)
     self.dis_optimizer = Optimizer(hparams, self.device)
+    # --ema_decay: the running average of the generator's weights
+    # (averaging.py); None without the flag, and then nothing below runs
+    self.average = None
+    if hasattr(hparams, 'ema_decay'):
+      self.average = averaging.WeightAverage(
+          generator.net.params, averaging.check_decay(hparams.ema_decay))
 
     self._sync = parallel.GradSync()
     self._streams = parallel.RandomStreams(_SEED, self.device, hparams.m)
@@ -358,14 +366,31 @@ class GAN(object):
         (self._graph_under_dp or self._sync.world == 1)):
       st['calls'] = st.get('calls', 0) + 1
       if st['calls'] > replay.GRAPH_WARMUP_CALLS:
-        return self._outputs(replay.replay(self, st, real))
+        return self._averaged(self._outputs(replay.replay(self, st, real)))
     # an eager step between replays (injected randomness, main.py's --profile
     # window).  The captured graphs stay valid: they hold pointers to buffers
     # that live as long as this object, and nothing in them depends on what ran
     # in between.  (Round 2 dropped them here after "stale graph" penalties of
     # 1e25; the cause was a hipMemsetAsync NODE inside the captured step --
     # cg_rownorm's -- not stale memory: DESIGN.md section 8.)
-    return self._outputs(replay.eager(self, st, real, rand))
+    return self._averaged(self._outputs(replay.eager(self, st, real, rand)))
+
+  def _averaged(self, outputs):
+    """The end of every train(): the generator has had its one update, the
+    average takes its one (after the step on the same stream, outside the
+    captured graphs; under mixed precision also when the loss scaler skipped
+    the Adam step, as StyleGAN does).  Hands `outputs` through."""
+    if self.average is not None:
+      self.average.update()
+    return outputs
+
+  def averaged_generator(self):
+    """Context manager: inside, the generator computes with its averaged
+    weights (validate / generate / checkpoints of --ema_decay); a null context
+    when averaging is off."""
+    if self.average is None:
+      return contextlib.nullcontext()
+    return self.average.applied(self.generator.net)
 
   def validate(self, inputs, rand=None):
     """gan.py:87-90 / :58-70: the same losses with training=False, no update.

@@ -141,7 +141,7 @@ class MLP_WGAN_GP(GAN):
     metrics = self._metrics_of(real, fake)
     _lib.call('cg_step_outputs', st['gen_loss'], st['loss'], st['gp'],
               metrics[_METRIC_KEYS[0]], n, st['out'], _lib.stream())
-    return self._outputs(st['out'])
+    return self._averaged(self._outputs(st['out']))
 
   def validate(self, inputs, rand=None):
     """gan.py:87-90 with the WGAN-GP loss: training=False (no dropout), the

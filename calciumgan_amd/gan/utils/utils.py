@@ -187,14 +187,21 @@ def save_models(hparams, gan, epoch):
   if not os.path.exists(hparams.ckpt_dir):
     os.makedirs(hparams.ckpt_dir)
   filename = os.path.join(hparams.ckpt_dir, 'epoch-{:03d}.pkl'.format(epoch))
+  ckpt = {
+      'epoch': epoch,
+      'gen_weights': gan.generator.get_weights(),
+      'dis_weights': gan.discriminator.get_weights(),
+      'gen_steps': int(gan.gen_optimizer.iterations),
+      'dis_steps': int(gan.dis_optimizer.iterations)
+  }
+  average = getattr(gan, 'average', None)
+  if average is not None:
+    # --ema_decay: the averaged generator next to the raw one, and how many
+    # updates it has had (the warm-up of its decay depends on the count)
+    ckpt['gen_ema_weights'] = average.get_weights()
+    ckpt['ema_updates'] = int(average.updates)
   with open(filename, 'wb') as file:
-    pickle.dump({
-        'epoch': epoch,
-        'gen_weights': gan.generator.get_weights(),
-        'dis_weights': gan.discriminator.get_weights(),
-        'gen_steps': int(gan.gen_optimizer.iterations),
-        'dis_steps': int(gan.dis_optimizer.iterations)
-    }, file)
+    pickle.dump(ckpt, file)
   if hparams.verbose:
     print('Saved checkpoint to {}'.format(filename))
 
@@ -214,6 +221,14 @@ def load_models(hparams, gan):
     gan.discriminator.set_weights(ckpt['dis_weights'])
     gan.gen_optimizer.iterations = int(ckpt['gen_steps'])
     gan.dis_optimizer.iterations = int(ckpt['dis_steps'])
+    average = getattr(gan, 'average', None)
+    if average is not None:
+      # (a checkpoint of a run without --ema_decay: averaging starts from the
+      # loaded weights; without the flag the keys are ignored)
+      have = 'gen_ema_weights' in ckpt and 'ema_updates' in ckpt
+      average.set_weights(ckpt['gen_ema_weights'] if have else
+                          ckpt['gen_weights'])
+      average.updates = int(ckpt['ema_updates']) if have else 0
     if hparams.verbose:
       print('\n\nRestored checkpoint at {}\n\n'.format(filename))
 

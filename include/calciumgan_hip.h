@@ -627,6 +627,20 @@ int cg_adam(float* p, const float* grad, float* m, float* v, long long n,
             void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Exponential moving average of a flat f32 parameter buffer (--ema_decay;
+ * gan/algorithms/averaging.py), TF's assign_moving_average:
+ *   ema[i] = ema[i] - fl(fl(ema[i] - p[i]) * om),   om = 1 - decay
+ * three f32 operations, each rounded on its own (never an fma): the bits of
+ * averaging.update_statement, the same on every call.  p is only read.  Any
+ * n >= 1 and any 4-byte aligned pointers; 16-byte loads and stores where ema
+ * and p are both 16-byte aligned.  ema and p must not overlap.  No atomics, no
+ * workspace.  CG_EINVAL, nothing launched: ema or p NULL, n < 1, om outside
+ * [0, 1] or NaN.
+ * ------------------------------------------------------------------------- */
+int cg_ema_update(float* ema, const float* p, long long n, float om,
+                  void* stream);
+
+/* ---------------------------------------------------------------------------
  * Dynamic loss scaling of the mixed_float16 mode -- mixed_precision.
  * LossScaleOptimizer(Adam, 'dynamic') (gan/algorithms/optimizer.py:10-12,23-29):
  * the loss is multiplied by S before the backward pass, the gradients divided by

@@ -143,8 +143,11 @@ def train_and_validate(hparams, train_ds, validation_ds, gan, summary):
     start = time()
     train_gen_loss, train_dis_loss = train(hparams, train_ds, gan, summary,
                                            epoch)
-    val_gen_loss, val_dis_loss = validate(hparams, validation_ds, gan, summary,
-                                          epoch)
+    # --ema_decay: validation (with --save_generated and --spike_metrics) runs
+    # on the averaged generator; training above always on the raw weights
+    with gan.averaged_generator():
+      val_gen_loss, val_dis_loss = validate(hparams, validation_ds, gan,
+                                            summary, epoch)
     if epoch % 10 == 0 or epoch == hparams.epochs - 1:
       if not hparams.skip_checkpoints and hparams.rank == 0:
         utils.save_models(hparams, gan, epoch)
@@ -231,7 +234,8 @@ def main(hparams, return_metrics=False):
     summary.scalar('elapse/total', end - start)
 
   if hparams.surrogate_ds and hparams.rank == 0:
-    utils.generate_dataset(hparams, gan=gan, num_samples=2 * 10**6)
+    with gan.averaged_generator():
+      utils.generate_dataset(hparams, gan=gan, num_samples=2 * 10**6)
   if return_metrics:
     return test(validation_ds, gan, hparams)
 
@@ -281,6 +285,13 @@ def build_parser():
                       'the GPU and logs spike_metrics/{firing_rate_mae,'
                       'firing_rate_rmse,covariance_mae,covariance_mse} against '
                       'the ground-truth spike trains (single process only)')
+  # (absent unless given, like --spike_metrics)
+  parser.add_argument('--ema_decay', type=float, default=argparse.SUPPRESS,
+                      metavar='D',
+                      help='keep an exponential moving average of the '
+                      'generator\'s weights (0 < D < 1, e.g. 0.999): validation, '
+                      'generated samples and the checkpoint\'s gen_ema_weights '
+                      'come from the average, training stays on the raw weights')
   parser.add_argument('--dpi', default=120, type=int)
   parser.add_argument('--verbose', default=1, type=int)
   return parser
