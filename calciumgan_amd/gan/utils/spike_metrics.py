@@ -837,3 +837,241 @@ def temporal_scores(ref, other, T):
       'max_lag': L - 1,
       'num_trials': [sides[0][2], sides[1][2]],
   }
+
+
+# -- population states: precision, recall and coverage --------------------------
+# (compute_metrics.py --state_metrics; csrc/state_neighbours.hip)
+STATE_K_STEP = 32          # CG_STATE_K_STEP
+STATE_MAX_K = 8            # CG_STATE_MAX_K
+STATE_MAX_BIN = 127        # CG_STATE_MAX_BIN
+STATE_MAX_NEURONS = 4096   # CG_STATE_MAX_C
+STATE_EXACT_SUM = 1 << 24  # CG_STATE_EXACT_SUM: C bin^2 may not exceed it
+STATE_NONE = 2**31 - 1     # CG_STATE_NONE: knn entry where fewer than k are admitted
+
+
+def _state_bin(bin):
+  bin = int(bin)
+  if not 1 <= bin <= STATE_MAX_BIN:
+    raise ValueError('bin = {}: 1 .. {} frames supported'.format(bin,
+                                                                 STATE_MAX_BIN))
+  return bin
+
+
+def population_states(spikes, bin=12):
+  """int32 (N nb, C) of trials (N, T, C), a frame a spike when it is != 0: row
+  n nb + b holds the spike counts of the C neurons in frames b bin .. (b + 1)
+  bin - 1 of trial n, nb = T // bin (a trailing partial bin is dropped, as
+  `bin_counts` drops it; T < bin raises).  The population state of one bin."""
+  s = _binary_trials(spikes)
+  bin = _state_bin(bin)
+  N, T, C = s.shape
+  nb = T // bin
+  if nb < 1:
+    raise ValueError('trials of {} frames hold no bin of {}'.format(T, bin))
+  return s[:, :nb * bin].reshape(N, nb, bin, C).sum(2).reshape(
+      N * nb, C).astype(np.int32)
+
+
+def _state_k(k):
+  k = int(k)
+  if not 1 <= k <= STATE_MAX_K:
+    raise ValueError('k = {}: 1 .. {} supported'.format(k, STATE_MAX_K))
+  return k
+
+
+def state_neighbours(a, b, k, exclude_self=False, radius_b=None, chunk=1024):
+  """Neighbour query of the states a (Sa, C) against the states b (Sb, C), with
+  d2(x, y) = sum_c (x_c - y_c)^2, an integer:
+    knn (Sa, k) int32     the k smallest d2(a_i, b_j) over the admitted j,
+                          ascending; STATE_NONE where fewer than k are admitted
+    within (Sa,) int32    #{admitted j : d2(a_i, b_j) <= radius_b[j]}, None
+                          without radius_b (int (Sb,))
+  Every j is admitted, except j == i with exclude_self (a and b the same set):
+  by index, so a duplicate of a_i at another index counts, at distance 0.
+  Walked in chunks of rows of a; the products are a float64 matmul of integers,
+  exact below 2^53.  The statement cg_state_neighbours is tested against, for
+  equality."""
+  a, b = (np.asarray(x) for x in (a, b))
+  k = _state_k(k)
+  if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1] or not len(a) or \
+      not len(b):
+    raise ValueError('states (Sa, C) and (Sb, C) expected')
+  if exclude_self and a.shape != b.shape:
+    raise ValueError('exclude_self: a and b must be the same set')
+  Sa, Sb = len(a), len(b)
+  fa, fb = a.astype(np.float64), b.astype(np.float64)
+  nb2 = (fb * fb).sum(1)
+  if radius_b is not None:
+    radius_b = np.asarray(radius_b).astype(np.int64)
+    if radius_b.shape != (Sb,):
+      raise ValueError('radius_b (Sb,) expected')
+  knn = np.full((Sa, k), STATE_NONE, np.int32)
+  within = None if radius_b is None else np.zeros((Sa,), np.int32)
+  for i0 in range(0, Sa, int(chunk)):
+    x = fa[i0:i0 + int(chunk)]
+    d2 = ((x * x).sum(1)[:, None] + nb2[None, :] - 2.0 * (x @ fb.T)).astype(
+        np.int64)
+    admitted = np.ones(d2.shape, bool)
+    if exclude_self:
+      rows = np.arange(len(x))
+      admitted[rows, i0 + rows] = False
+    if within is not None:
+      within[i0:i0 + len(x)] = ((d2 <= radius_b[None, :]) & admitted).sum(1)
+    d2[~admitted] = STATE_NONE
+    if Sb < k:
+      d2 = np.concatenate(
+          [d2, np.full((len(x), k - Sb), STATE_NONE, np.int64)], axis=1)
+    knn[i0:i0 + len(x)] = np.sort(np.partition(d2, k - 1, axis=1)[:, :k], axis=1)
+  return knn, within
+
+
+class DeviceStates(object):
+  """A set of states on the device as cg_population_states writes it: `tensor`
+  bfloat16 (S, C rounded up to STATE_K_STEP) with zeros in the padding, the
+  number of neurons C and the bin the counts came from."""
+  __slots__ = ('tensor', 'C', 'bin')
+
+  def __init__(self, tensor, C, bin):
+    self.tensor, self.C, self.bin = tensor, int(C), int(bin)
+
+  def __len__(self):
+    return int(self.tensor.shape[0])
+
+  @classmethod
+  def cat(cls, parts):
+    import torch
+    parts = list(parts)
+    if len({(p.C, p.bin) for p in parts}) != 1:
+      raise ValueError('sets of one C and one bin expected')
+    return cls(torch.cat([p.tensor for p in parts]), parts[0].C, parts[0].bin)
+
+  def counts(self):
+    """int32 device (S, C): the states as `population_states` holds them."""
+    import torch
+    return self.tensor[:, :self.C].to(torch.int32)
+
+
+def population_states_device(spikes, bin=12):
+  """`population_states` on the GPU (cg_population_states): float32 device
+  tensor (B, T, C), any strides, read in place -> DeviceStates of B (T // bin)
+  states.  One launch, no host synchronisation.  C bin^2 <= 2^24 and C <= 4096
+  (the bound under which cg_state_neighbours is exact)."""
+  import torch
+  from ... import _lib as hip
+  B, T, C = _trial_batch(spikes)
+  bin = _state_bin(bin)
+  if T < bin:
+    raise ValueError('trials of {} frames hold no bin of {}'.format(T, bin))
+  Cp = -(-C // STATE_K_STEP) * STATE_K_STEP
+  states = torch.empty(B * (T // bin), Cp, dtype=torch.bfloat16,
+                       device=spikes.device)
+  hip.call('cg_population_states', spikes, B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), bin, states, hip.stream())
+  return DeviceStates(states, C, bin)
+
+
+def state_neighbours_device(a, b, k, exclude_self=False, radius_b=None,
+                            knn=True):
+  """`state_neighbours` on the GPU (cg_state_neighbours): DeviceStates a and b
+  -> (knn int32 device (Sa, k) or None with knn=False, within int32 device (Sa,)
+  or None without radius_b), the statement's integers.  radius_b: int32 (Sb,),
+  a device tensor or anything numpy takes.  exclude_self needs `b is a` or the
+  same tensor.  No Sa x Sb matrix exists anywhere; no host synchronisation."""
+  import torch
+  from ... import _lib as hip
+  if not (isinstance(a, DeviceStates) and isinstance(b, DeviceStates)):
+    raise ValueError('DeviceStates expected')
+  if (a.C, a.bin) != (b.C, b.bin):
+    raise ValueError('sets of one C and one bin expected')
+  k = _state_k(k)
+  ta, tb = a.tensor, b.tensor
+  if not (ta.is_contiguous() and tb.is_contiguous()):
+    raise ValueError('contiguous states expected')
+  if exclude_self and not (ta.data_ptr() == tb.data_ptr() and
+                           ta.shape == tb.shape):
+    raise ValueError('exclude_self: a and b must be the same set')
+  Sa, Sb = len(a), len(b)
+  dev = ta.device
+  if radius_b is not None:
+    if not torch.is_tensor(radius_b):
+      radius_b = torch.from_numpy(
+          np.ascontiguousarray(np.asarray(radius_b).astype(np.int32)))
+    radius_b = radius_b.to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(radius_b.shape) != (Sb,):
+      raise ValueError('radius_b (Sb,) expected')
+  elif not knn:
+    raise ValueError('nothing asked for: knn=False without radius_b')
+  need = hip.load().cg_state_neighbours_ws_bytes(Sa, Sb, a.C, a.bin, k)
+  if need < 0:
+    raise ValueError('cg_state_neighbours: unsupported shape (Sa = {}, Sb = {}, '
+                     'C = {}, bin = {}, k = {})'.format(Sa, Sb, a.C, a.bin, k))
+  ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+  out = torch.empty(Sa, k, dtype=torch.int32, device=dev) if knn else None
+  within = (torch.empty(Sa, dtype=torch.int32, device=dev)
+            if radius_b is not None else None)
+  hip.call('cg_state_neighbours', ta, Sa, tb, Sb, a.C, a.bin, k,
+           1 if exclude_self else 0, radius_b, out, within, ws, hip.stream())
+  return out, within
+
+
+def _state_host(x):
+  return None if x is None else np.asarray(x.cpu() if hasattr(x, 'cpu') else x)
+
+
+def state_radii(states, k, neighbours=state_neighbours):
+  """int32 (S,): the distance d2 from every state of the set to its k-th nearest
+  other state of the set (self excluded by index).  The set needs more than k
+  states."""
+  k = _state_k(k)
+  if len(states) <= k:
+    raise ValueError('a set of {} states has no {}-th neighbour'.format(
+        len(states), k))
+  return _state_host(neighbours(states, states, k, exclude_self=True)[0])[
+      :, k - 1].astype(np.int32)
+
+
+def state_scores(ref, other, k, neighbours=state_neighbours, rad_ref=None):
+  """Improved precision and recall (Kynkaanniemi et al. 2019) and coverage
+  (Naeem et al. 2020) of the states `other` against the states `ref`, closed
+  balls, integer distances.  neighbours(a, b, k, exclude_self=, radius_b=) ->
+  (knn, within) is `state_neighbours` (sets as `population_states` gives them)
+  or `state_neighbours_device` (DeviceStates); everything after the integers is
+  host arithmetic, so both give the same dict bit for bit.  rad_ref:
+  `state_radii(ref, k)` where the caller keeps it.
+    precision         share of `other` states inside the ball of some ref state
+    recall            share of ref states inside the ball of some `other` state
+    coverage          share of ref states whose ball holds an `other` state
+    exact_match       [share of ref states found in `other`, share of `other`
+                      states found in ref] (nearest d2 = 0)
+    nearest_distance  [median over ref of the distance to the nearest `other`
+                      state, median over `other` of that to the nearest ref one]
+    radius_median     [median ball radius of ref, of `other`]
+    num_states        [S_ref, S_other]
+  The ball of a state reaches to its k-th nearest other state of its own set.
+  Both sets need more than k states (ValueError)."""
+  k = _state_k(k)
+  if len(ref) <= k or len(other) <= k:
+    raise ValueError('both sets need more than k = {} states ({} and {})'
+                     .format(k, len(ref), len(other)))
+  if rad_ref is None:
+    rad_ref = state_radii(ref, k, neighbours)
+  rad_ref = np.asarray(rad_ref).astype(np.int32)
+  rad_other = state_radii(other, k, neighbours)
+  knn_o, within_o = (_state_host(x)
+                     for x in neighbours(other, ref, k, radius_b=rad_ref))
+  knn_r, within_r = (_state_host(x)
+                     for x in neighbours(ref, other, k, radius_b=rad_other))
+  near_r, near_o = knn_r[:, 0].astype(np.int64), knn_o[:, 0].astype(np.int64)
+
+  def root_median(x):
+    return float(np.median(np.sqrt(np.asarray(x).astype(np.float64))))
+
+  return {
+      'precision': float(np.mean(within_o > 0)),
+      'recall': float(np.mean(within_r > 0)),
+      'coverage': float(np.mean(near_r <= rad_ref.astype(np.int64))),
+      'exact_match': [float(np.mean(near_r == 0)), float(np.mean(near_o == 0))],
+      'nearest_distance': [root_median(near_r), root_median(near_o)],
+      'radius_median': [root_median(rad_ref), root_median(rad_other)],
+      'num_states': [int(len(ref)), int(len(other))],
+  }

@@ -16,6 +16,7 @@ the reference's compute_metrics.py (BASELINE configs[3]: recorded-data pipeline
       [--device gpu [--batch_trials 128]] [--victor_purpura [--vp_q 1.0]]
       [--temporal_metrics [--max_lag 24]] [--spectral_metrics]
       [--novelty_metrics [--novelty_step 2]]
+      [--state_metrics [--state_k 5] [--state_bin 12]]
 
 --device gpu (not a reference flag) takes the deconvolution, the firing rates,
 the per-trial correlations and the van Rossum matrices through the HIP kernels
@@ -84,6 +85,24 @@ MFMA, the recording's rows staged in LDS, no window materialised) on the device
 in batches of --batch_trials with the recording uploaded once.  The two devices
 agree to float64 summation rounding, not bit for bit; an index may differ where
 two stretches lie that close to each other.
+
+--state_metrics [--state_k 5] [--state_bin 12] (not reference flags, absent from
+the namespace unless given) adds `states`: the only figures that ask of single
+samples whether each generated one is something the data contains (precision)
+and whether everything the data contains is generated (recall, coverage).  The
+sample is a population state, the spike counts of all neurons in one bin of
+--state_bin frames; the ball of a state reaches to its --state_k-th nearest
+other state of its own set (spike_metrics.state_scores).  The recorded trials 0,
+2, 4, ... of the first num_samples are the reference set; `generated` scores the
+generated trials 1, 3, 5, ... against it and `floor` the recorded trials 1, 3,
+5, ...: the figures depend on the set sizes and two draws of one distribution
+do not score 1, so each is read beside its floor (computed once, kept across
+epochs).  On a recording dataset the validation windows overlap in time, so
+the floor there is optimistic.  spike_metrics.state_neighbours on the host,
+cg_population_states and cg_state_neighbours (csrc/state_neighbours.hip: the
+products on the matrix pipe, the k smallest of every row selected in registers,
+no distance matrix in memory) on the device in batches of --batch_trials.  All
+distances are exact integers on both, so both devices write the same dict.
 
 The KL is the reference's: both samples cut into 30 equal-width bins over their
 pooled range by pandas.cut, empty bins replaced by 1e-10 (:80-111) -- pandas is
@@ -405,6 +424,48 @@ def novelty_report(hparams, filename, nearest):
   return scores
 
 
+STATE_K, STATE_BIN = 5, 12  # --state_k, --state_bin (500 ms of frames)
+
+
+def state_sets_host(hparams, spikes):
+  """The states of an NWC host array of trials as spike_metrics.state_neighbours
+  takes them."""
+  return spike_metrics.population_states(
+      spikes, getattr(hparams, 'state_bin', STATE_BIN))
+
+
+def state_report(hparams, filename, states, neighbours):
+  """--state_metrics: spike_metrics.state_scores of the population states of the
+  generated trials 1, 3, 5, ... against those of the recorded trials 0, 2, 4,
+  ... (`generated`), beside the same scores of the recorded trials 1, 3, 5, ...
+  against them (`floor`: what two draws of the data score at these sizes).
+  states(hparams, trials) -> a set, neighbours the query on such sets; the
+  recorded side (the reference set, its radii and the floor) is kept across
+  epochs."""
+  k = int(getattr(hparams, 'state_k', STATE_K))
+  fake = _trial_spikes(hparams, filename)
+  real = getattr(hparams, '_recorded_states', None)
+  if real is None:  # the validation set is the same for every epoch
+    spikes = _trial_spikes(hparams, hparams.validation_cache)
+    ref = states(hparams, spikes[0::2])
+    rad_ref = spike_metrics.state_radii(ref, k, neighbours)
+    floor = spike_metrics.state_scores(ref, states(hparams, spikes[1::2]), k,
+                                       neighbours, rad_ref=rad_ref)
+    real = hparams._recorded_states = (ref, rad_ref, floor, spikes.shape[1])
+  ref, rad_ref, floor, frames = real
+  if fake.shape[1] != frames:
+    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
+                     .format(filename, fake.shape[1], frames))
+  generated = spike_metrics.state_scores(ref, states(hparams, fake[1::2]), k,
+                                         neighbours, rad_ref=rad_ref)
+  if hparams.verbose:
+    for name in ('precision', 'recall', 'coverage'):
+      print('\tstate {:<9}  gen | floor: {:.04f} | {:.04f}'.format(
+          name, generated[name], floor[name]))
+  return dict(generated=generated, floor=floor, k=k,
+              bin_frames=int(getattr(hparams, 'state_bin', STATE_BIN)))
+
+
 def compute_epoch_spike_metrics(hparams, filename, epoch):
   """:483-497 without plot_signals / raster_plots: dict of the statistics."""
   if not h5_helper.contains(filename, 'spikes'):
@@ -442,6 +503,9 @@ def compute_epoch_spike_metrics(hparams, filename, epoch):
     out['spectral'] = spectral_report(hparams, filename, spectral_totals_host)
   if getattr(hparams, 'novelty_metrics', False):
     out['novelty'] = novelty_report(hparams, filename, novelty_nearest_host)
+  if getattr(hparams, 'state_metrics', False):
+    out['states'] = state_report(hparams, filename, state_sets_host,
+                                 spike_metrics.state_neighbours)
   return out
 
 
@@ -655,6 +719,15 @@ def novelty_nearest_device(hparams, queries, exclude, exclude_len):
   return torch.cat(nearest).cpu().numpy(), torch.cat(index).cpu().numpy()
 
 
+def state_sets_device(hparams, spikes):
+  """`state_sets_host` through cg_population_states, a batch of trials at a
+  time; the states stay on the device."""
+  return spike_metrics.DeviceStates.cat(
+      spike_metrics.population_states_device(
+          batch, getattr(hparams, 'state_bin', STATE_BIN))
+      for batch in _batches(hparams, spikes))
+
+
 def compute_epoch_spike_metrics_device(hparams, filename, epoch):
   """`compute_epoch_spike_metrics` with the statistics from the device; the
   histograms behind the KL from cg_pair_histogram (`device_kl`) unless
@@ -697,6 +770,9 @@ def compute_epoch_spike_metrics_device(hparams, filename, epoch):
     out['spectral'] = spectral_report(hparams, filename, spectral_totals_device)
   if getattr(hparams, 'novelty_metrics', False):
     out['novelty'] = novelty_report(hparams, filename, novelty_nearest_device)
+  if getattr(hparams, 'state_metrics', False):
+    out['states'] = state_report(hparams, filename, state_sets_device,
+                                 spike_metrics.state_neighbours_device)
   return out
 
 
@@ -792,6 +868,19 @@ def build_parser():
   parser.add_argument('--novelty_step', type=int, default=argparse.SUPPRESS,
                       help='--novelty_metrics: rows between two stretches '
                       '(default: the stride of the dataset)')
+  # (absent unless given, like --victor_purpura)
+  parser.add_argument('--state_metrics', action='store_true',
+                      default=argparse.SUPPRESS,
+                      help='also report `states`: precision, recall and '
+                      'coverage of the generated population states against the '
+                      'recorded ones, beside the floor two halves of the '
+                      'recorded trials score')
+  parser.add_argument('--state_k', type=int, default=argparse.SUPPRESS,
+                      help='--state_metrics: the ball of a state reaches to its '
+                      'k-th nearest neighbour (default 5, at most 8)')
+  parser.add_argument('--state_bin', type=int, default=argparse.SUPPRESS,
+                      help='--state_metrics: frames per bin of a state '
+                      '(default 12, at most 127)')
   return parser
 
 

@@ -1024,6 +1024,72 @@ int cg_nearest_stretch(const float* q, int N, int L, int C,
                        void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Population states and their nearest neighbours (state_neighbours.hip;
+ * compute_metrics.py --state_metrics: improved precision / recall and coverage
+ * of the generated population states against the recorded ones; not in the
+ * reference, whose figures all compare averages over trials).  Added under ABI
+ * 20; the same code in both precision builds.
+ * ------------------------------------------------------------------------- */
+/* A state is the vector of spike counts of the C neurons of a trial in one bin
+ * of `bin` frames (the numpy statement is spike_metrics.population_states):
+ *   x[n * nb + b][c] = #{t in [b bin, (b + 1) bin) : trains[n * s_b + t * s_t +
+ *                        c * s_c] != 0},   nb = T / bin (a partial bin is dropped)
+ * (a NaN is a spike, -0.0 is not).  Strides in elements, any values; every
+ * element of the bins is read once.  states: bf16 [B nb][Cp], Cp = C rounded up
+ * to CG_STATE_K_STEP, 16-byte aligned, written whole: the counts 0 .. bin are
+ * exact in bf16 and columns C .. Cp - 1 are zeros.  One launch, no atomics.
+ * CG_EINVAL (nothing launched, nothing written): a NULL trains or states,
+ * states not 16-byte aligned, B, T or C < 1, bin < 1 or > CG_STATE_MAX_BIN,
+ * T < bin, C > CG_STATE_MAX_C, C bin^2 > CG_STATE_EXACT_SUM, B nb >
+ * CG_STATE_MAX_ROWS. */
+#define CG_STATE_K_STEP 32
+#define CG_STATE_MAX_BIN 127
+#define CG_STATE_MAX_C 4096
+#define CG_STATE_MAX_ROWS 16777216
+#define CG_STATE_EXACT_SUM 16777216
+#define CG_STATE_MAX_K 8
+#define CG_STATE_NONE 2147483647
+int cg_population_states(const float* trains, int B, int T, int C,
+                         long long s_b, long long s_t, long long s_c, int bin,
+                         void* states, void* stream);
+/* Neighbour query of a set A of Sa states against a set B of Sb states, both as
+ * cg_population_states writes them (values 0 .. bin; the numpy statement is
+ * spike_metrics.state_neighbours).  d2(x, y) = sum_c (x_c - y_c)^2, an integer.
+ *   knn[i * k + 0 .. k - 1] = the k smallest d2(a_i, b_j) over the admitted j,
+ *                             ascending; CG_STATE_NONE where fewer are admitted
+ *   within[i] = #{admitted j : d2(a_i, b_j) <= radius_b[j]}
+ * Every j < Sb is admitted, except j == i when exclude_self != 0 (by index: a
+ * duplicate of a_i elsewhere counts, at distance 0).  knn int32 [Sa][k], within
+ * int32 [Sa], radius_b int32 [Sb]; knn or within may be NULL (not both), within
+ * and radius_b are given together or not at all.
+ * d2 = |a_i|^2 + |b_j|^2 - 2 a_i . b_j with the products on
+ * v_mfma_f32_16x16x32_bf16 (K = the neurons): every partial sum is an integer
+ * of at most C bin^2 <= CG_STATE_EXACT_SUM = 2^24, which f32 holds, so every d2
+ * is the exact integer.  Hence the limits: C <= CG_STATE_MAX_C with C bin^2 <=
+ * 2^24 (C <= 1040 at bin 127, bin <= 64 at C 4096), Sa and Sb <=
+ * CG_STATE_MAX_ROWS.
+ * Launches on `stream`: the int32 squared norms of both sets (to ws); the
+ * fused launch, in which a workgroup owns 128 states of A and a run of 64-state
+ * tiles of B and every lane keeps the 8 smallest d2 and the count of one state
+ * of A in registers -- nothing of size Sa Sb exists in memory; where A has few
+ * states B is split over up to 64 workgroups per 128 states of A (a function of
+ * Sa and Sb alone) whose lists and counts go to ws, and one more launch merges
+ * them in split order.  No atomics, nothing to zero beforehand, no host sync,
+ * the same bits every call.
+ * cg_state_neighbours_ws_bytes: bytes of `ws` (16-byte aligned; contents do not
+ * matter), -1 for a shape cg_state_neighbours refuses.
+ * CG_EINVAL (nothing launched, nothing written): a NULL a, b or ws; a, b or ws
+ * not 16-byte aligned; radius_b, knn or within not 4-byte aligned; knn and
+ * within both NULL; one of within and radius_b NULL and the other not; Sa, Sb or
+ * C < 1; Sa or Sb > CG_STATE_MAX_ROWS; C > CG_STATE_MAX_C; bin < 1 or >
+ * CG_STATE_MAX_BIN; C bin^2 > CG_STATE_EXACT_SUM; k < 1 or > CG_STATE_MAX_K;
+ * exclude_self with a != b or Sa != Sb. */
+long long cg_state_neighbours_ws_bytes(int Sa, int Sb, int C, int bin, int k);
+int cg_state_neighbours(const void* a, int Sa, const void* b, int Sb, int C,
+                        int bin, int k, int exclude_self, const int* radius_b,
+                        int* knn, int* within, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Recording datasets (windows.hip; the reference's generate_tfrecords.py cuts a
  * (neurons, T) recording into overlapping stride-2 windows and writes each one
  * out; here the recording stays resident and every step's windows are cut
