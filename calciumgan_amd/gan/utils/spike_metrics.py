@@ -1075,3 +1075,264 @@ def state_scores(ref, other, k, neighbours=state_neighbours, rad_ref=None):
       'radius_median': [root_median(rad_ref), root_median(rad_other)],
       'num_states': [int(len(ref)), int(len(other))],
   }
+
+
+# -- third-order correlations of binarised population states ---------------------
+# (compute_metrics.py --triplet_metrics; csrc/triplets.hip)
+TRIPLET_MAX_NEURONS = 512       # CG_TRIPLET_MAX_C
+TRIPLET_MAX_WORDS = 2**26 - 1   # CG_TRIPLET_MAX_WORDS: every count below 2^31
+
+
+def _triplet_bin(bin):
+  bin = int(bin)
+  if bin < 1:
+    raise ValueError('bin = {}: at least one frame'.format(bin))
+  return bin
+
+
+def binary_states(spikes, bin=12):
+  """uint8 (N nb, C) of trials (N, T, C), a frame a spike when it is != 0: entry
+  (n nb + b, c) is 1 iff neuron c has any spike in frames b bin .. (b + 1) bin -
+  1 of trial n, nb = T // bin (a trailing partial bin is dropped; T < bin
+  raises).  Binarised on purpose: the counts of binary states need no exactness
+  bound."""
+  s = _binary_trials(spikes)
+  bin = _triplet_bin(bin)
+  N, T, C = s.shape
+  nb = T // bin
+  if nb < 1:
+    raise ValueError('trials of {} frames hold no bin of {}'.format(T, bin))
+  return s[:, :nb * bin].reshape(N, nb, bin, C).any(2).reshape(
+      N * nb, C).astype(np.uint8)
+
+
+def triplet_index(C):
+  """int32 (C(C,3), 3): the (i, j, k), i < j < k, of every rank, in
+  lexicographic order (itertools.combinations(range(C), 3))."""
+  C = int(C)
+  if C < 3:
+    raise ValueError('C = {}: three neurons at least'.format(C))
+  parts = []
+  for i in range(C - 2):
+    j, k = np.triu_indices(C - i - 1, 1)
+    parts.append(np.stack([np.full(len(j), i), j + i + 1, k + i + 1], 1))
+  return np.concatenate(parts).astype(np.int32)
+
+
+def triplet_counts(states, chunk=1 << 16):
+  """(singles (C,), pairs (C, C), triplets (C(C,3),)), int64, of binary states
+  (S, C):
+    singles[i]  = sum_s x_si
+    pairs[i][j] = sum_s x_si x_sj     (symmetric, the singles on the diagonal)
+    triplets[r] = sum_s x_si x_sj x_sk   for the r-th i < j < k of triplet_index
+  One (C x S)(S x C) float64 product per neuron and chunk of states, exact on
+  these integers below 2^53.  The statement cg_triplet_counts is tested
+  against, for equality."""
+  x = np.asarray(states)
+  if x.ndim != 2 or x.shape[1] < 3 or not len(x):
+    raise ValueError('states (S, C), C >= 3, expected')
+  x = (x != 0).astype(np.float64)
+  S, C = x.shape
+  pairs = np.zeros((C, C), np.float64)
+  ju, ku = np.triu_indices(C, 1)   # ordered by j, then k
+  # the pairs j > i are the tail of (ju, ku) from first[i + 1] on
+  first = np.concatenate([[0], np.cumsum(C - 1 - np.arange(C))])
+  offset = np.concatenate(
+      [[0], np.cumsum([len(ju) - first[i + 1] for i in range(C - 2)])])
+  triplets = np.zeros((int(offset[-1]),), np.float64)
+  for s0 in range(0, S, int(chunk)):
+    xs = x[s0:s0 + int(chunk)]
+    pairs += xs.T @ xs
+    for i in range(C - 2):
+      m = (xs * xs[:, i:i + 1]).T @ xs
+      sel = slice(first[i + 1], None)
+      triplets[offset[i]:offset[i + 1]] += m[ju[sel], ku[sel]]
+  pairs = pairs.astype(np.int64)
+  return np.diagonal(pairs).copy(), pairs, triplets.astype(np.int64)
+
+
+def pack_state_words(states, nb):
+  """uint32 (C, N wpt) of binary states (N nb, C), the layout of
+  cg_binary_words: bit b % 32 of word n wpt + b // 32 of row c is state n nb + b
+  of neuron c, wpt = ceil(nb / 32), the tail bits of a trial's last word zero."""
+  x = (np.asarray(states) != 0)
+  nb = int(nb)
+  S, C = x.shape
+  if nb < 1 or S % nb:
+    raise ValueError('{} states are no whole trials of {}'.format(S, nb))
+  N, wpt = S // nb, -(-nb // 32)
+  bits = np.zeros((N, wpt * 32, C), np.uint64)
+  bits[:, :nb] = x.reshape(N, nb, C)
+  bits = bits.reshape(N, wpt, 32, C) << np.arange(32, dtype=np.uint64)[:, None]
+  return np.ascontiguousarray(
+      bits.sum(2).astype(np.uint32).transpose(2, 0, 1).reshape(C, N * wpt))
+
+
+def unpack_state_words(words, nb):
+  """uint8 (N nb, C): the states of uint32 (C, N wpt) words; what
+  `pack_state_words` packed."""
+  w = np.asarray(words).astype(np.uint32)
+  nb = int(nb)
+  wpt = -(-nb // 32)
+  C, W = w.shape
+  if nb < 1 or W % wpt:
+    raise ValueError('{} words are no whole trials of {}'.format(W, wpt))
+  N = W // wpt
+  bits = (w.reshape(C, N, wpt, 1) >> np.arange(32, dtype=np.uint32)) & 1
+  return np.ascontiguousarray(
+      bits.reshape(C, N, wpt * 32)[:, :, :nb].transpose(1, 2, 0).reshape(
+          N * nb, C).astype(np.uint8))
+
+
+class DeviceWords(object):
+  """Binary states on the device as cg_binary_words writes them: `tensor` int32
+  (C, trials wpt), the uint32 words of every neuron (bit b % 32 of word b // 32
+  of a trial is the state of its bin b, wpt = ceil(nb / 32)), with the number of
+  neurons C, the bin, the bins per trial nb and the number of trials."""
+  __slots__ = ('tensor', 'C', 'bin', 'nb', 'trials')
+
+  def __init__(self, tensor, C, bin, nb, trials):
+    self.tensor, self.C, self.bin = tensor, int(C), int(bin)
+    self.nb, self.trials = int(nb), int(trials)
+
+  def __len__(self):
+    """The number of states."""
+    return self.nb * self.trials
+
+  @classmethod
+  def cat(cls, parts):
+    """The sets joined along the words."""
+    import torch
+    parts = list(parts)
+    if len({(p.C, p.bin, p.nb) for p in parts}) != 1:
+      raise ValueError('sets of one C, one bin and one trial length expected')
+    p = parts[0]
+    return cls(torch.cat([q.tensor for q in parts], dim=1), p.C, p.bin, p.nb,
+               sum(q.trials for q in parts))
+
+  def states(self):
+    """uint8 host (trials nb, C): the states as `binary_states` holds them."""
+    return unpack_state_words(
+        self.tensor.cpu().numpy().view(np.uint32), self.nb)
+
+
+def binary_words_device(spikes, bin=12):
+  """`binary_states` on the GPU, packed (cg_binary_words): float32 device tensor
+  (B, T, C), any strides, read in place -> DeviceWords of B (T // bin) states.
+  One launch, no host synchronisation.  3 <= C <= 512."""
+  import torch
+  from ... import _lib as hip
+  B, T, C = _trial_batch(spikes)
+  bin = _triplet_bin(bin)
+  if T < bin:
+    raise ValueError('trials of {} frames hold no bin of {}'.format(T, bin))
+  nb = T // bin
+  W = B * -(-nb // 32)
+  words = torch.empty(C, W, dtype=torch.int32, device=spikes.device)
+  hip.call('cg_binary_words', spikes, B, T, C, spikes.stride(0),
+           spikes.stride(1), spikes.stride(2), bin, words, W, hip.stream())
+  return DeviceWords(words, C, bin, nb, B)
+
+
+def triplet_counts_device(words):
+  """`triplet_counts` on the GPU (cg_triplet_counts): DeviceWords -> ((singles
+  (C,), pairs (C, C), triplets (C(C,3),)) int32 device, S), the statement's
+  integers and the number of states.  No atomics, no host synchronisation."""
+  import torch
+  from ... import _lib as hip
+  if not isinstance(words, DeviceWords):
+    raise ValueError('DeviceWords expected')
+  t = words.tensor
+  if not t.is_contiguous():
+    raise ValueError('contiguous words expected')
+  C, W = int(t.shape[0]), int(t.shape[1])
+  need = hip.load().cg_triplet_counts_ws_bytes(C, W)
+  if need < 0:
+    raise ValueError('cg_triplet_counts: unsupported shape (C = {}, W = {})'
+                     .format(C, W))
+  dev = t.device
+  ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+  singles = torch.empty(C, dtype=torch.int32, device=dev)
+  pairs = torch.empty(C, C, dtype=torch.int32, device=dev)
+  triplets = torch.empty(C * (C - 1) * (C - 2) // 6, dtype=torch.int32,
+                         device=dev)
+  hip.call('cg_triplet_counts', t, C, W, W, singles, pairs, triplets, ws,
+           hip.stream())
+  return (singles, pairs, triplets), len(words)
+
+
+def _triplet_moments(side):
+  """(pair covariances over i < j, p_ijk, kappa_ijk) of one side (singles,
+  pairs, triplets, S), float64."""
+  singles, pairs, triplets, S = side
+  S = int(S)
+  if S < 1:
+    raise ValueError('no states')
+  p1 = _state_host(singles).astype(np.float64) / S
+  p2 = _state_host(pairs).astype(np.float64) / S
+  p3 = _state_host(triplets).astype(np.float64) / S
+  C = len(p1)
+  if C < 3 or p2.shape != (C, C) or p3.shape != (C * (C - 1) * (C - 2) // 6,):
+    raise ValueError('singles (C,), pairs (C, C), triplets (C(C,3),), C >= 3, '
+                     'expected')
+  ju, ku = np.triu_indices(C, 1)
+  cov = p2[ju, ku] - p1[ju] * p1[ku]
+  kappa = np.empty_like(p3)
+  first = np.concatenate([[0], np.cumsum(C - 1 - np.arange(C))])
+  at = 0
+  for i in range(C - 2):   # the block of rank (i, j, k), j > i
+    j, k = ju[first[i + 1]:], ku[first[i + 1]:]
+    n = len(j)
+    kappa[at:at + n] = (p3[at:at + n] - p2[i, j] * p1[k] - p2[i, k] * p1[j] -
+                        p2[j, k] * p1[i] + 2.0 * p1[i] * p1[j] * p1[k])
+    at += n
+  return cov, p3, kappa
+
+
+def triplet_scores(ref, other):
+  """How far the third-order structure of `other` is from that of `ref`; each
+  side (singles, pairs, triplets, S) as `triplet_counts` or
+  `triplet_counts_device` gives them, and its number of states.  Host float64,
+  whichever device counted.  With p = n / S:
+    c_ij      = p_ij - p_i p_j                                   (i < j)
+    kappa_ijk = p_ijk - p_ij p_k - p_ik p_j - p_jk p_i + 2 p_i p_j p_k
+  the connected third-order correlation (third joint cumulant) of i < j < k.
+    pair_covariance_mae, pair_covariance_correlation   over i < j: the second
+                                  order at the same binning, to read the third
+                                  order against
+    triplet_probability_mae       mean |difference| of p_ijk
+    triplet_cumulant_mae, triplet_cumulant_correlation   over all triplets
+    triplet_cumulant_top_mae, triplet_cumulant_top_correlation   the same over
+                                  the max(2, ceil(Tr / 100)) triplets of largest
+                                  |kappa_ref| (stable order: the lower rank first
+                                  on ties; NaN when Tr < 2)
+    triplet_cumulant_mean_abs     [ref, other]: mean |kappa|
+    triplets_observed             [ref, other]: share of triplets with a count
+    num_states, num_triplets      [S_ref, S_other], Tr
+  A correlation is NaN with fewer than two values or no variance on a side."""
+  cov_r, p3_r, k_r = _triplet_moments(ref)
+  cov_o, p3_o, k_o = _triplet_moments(other)
+  if k_r.shape != k_o.shape:
+    raise ValueError('sides of one C expected')
+  Tr = len(k_r)
+  nan = float('nan')
+  if Tr >= 2:
+    top = np.argsort(-np.abs(k_r), kind='stable')[:max(2, -(-Tr // 100))]
+    top_mae = _mean_abs_difference(k_r[top], k_o[top])
+    top_corr = _pearson(k_r[top], k_o[top])
+  else:
+    top_mae = top_corr = nan
+  return {
+      'pair_covariance_mae': _mean_abs_difference(cov_r, cov_o),
+      'pair_covariance_correlation': _pearson(cov_r, cov_o),
+      'triplet_probability_mae': _mean_abs_difference(p3_r, p3_o),
+      'triplet_cumulant_mae': _mean_abs_difference(k_r, k_o),
+      'triplet_cumulant_correlation': _pearson(k_r, k_o),
+      'triplet_cumulant_top_mae': top_mae,
+      'triplet_cumulant_top_correlation': top_corr,
+      'triplet_cumulant_mean_abs': [float(np.mean(np.abs(k_r))),
+                                    float(np.mean(np.abs(k_o)))],
+      'triplets_observed': [float(np.mean(p3_r > 0)), float(np.mean(p3_o > 0))],
+      'num_states': [int(ref[3]), int(other[3])],
+      'num_triplets': int(Tr),
+  }

@@ -17,6 +17,7 @@ the reference's compute_metrics.py (BASELINE configs[3]: recorded-data pipeline
       [--temporal_metrics [--max_lag 24]] [--spectral_metrics]
       [--novelty_metrics [--novelty_step 2]]
       [--state_metrics [--state_k 5] [--state_bin 12]]
+      [--triplet_metrics [--triplet_bin 12]]
 
 --device gpu (not a reference flag) takes the deconvolution, the firing rates,
 the per-trial correlations and the van Rossum matrices through the HIP kernels
@@ -103,6 +104,21 @@ cg_population_states and cg_state_neighbours (csrc/state_neighbours.hip: the
 products on the matrix pipe, the k smallest of every row selected in registers,
 no distance matrix in memory) on the device in batches of --batch_trials.  All
 distances are exact integers on both, so both devices write the same dict.
+
+--triplet_metrics [--triplet_bin 12] (not reference flags, absent from the
+namespace unless given) adds `triplets`: the only figures past the second
+order.  A dichotomised-Gaussian twin of a recording matches every rate and every
+pairwise covariance by construction; what a generator can have that the twin
+cannot is structure beyond pairs, and these figures measure it.  The states are
+binary (did the neuron fire in a bin of --triplet_bin frames); kappa_ijk is the
+connected third-order correlation of a neuron triplet and the figures compare
+it, over all C(C,3) triplets, between the sides (spike_metrics.triplet_scores).
+`generated`, `floor` and the trials they are taken from are --state_metrics'.
+spike_metrics.triplet_counts on the host; on the device cg_binary_words packs
+the states 32 to a word in batches of --batch_trials and cg_triplet_counts
+(csrc/triplets.hip: AND and popcount, exact with no bound on the counts) counts
+a side in one call.  Only integers come to the host, so both devices write the
+same dict.
 
 The KL is the reference's: both samples cut into 30 equal-width bins over their
 pooled range by pandas.cut, empty bins replaced by 1e-10 (:80-111) -- pandas is
@@ -466,6 +482,51 @@ def state_report(hparams, filename, states, neighbours):
               bin_frames=int(getattr(hparams, 'state_bin', STATE_BIN)))
 
 
+TRIPLET_BIN = 12  # --triplet_bin (500 ms of frames)
+
+
+def triplet_sets_host(hparams, spikes):
+  """(singles, pairs, triplets, S) of an NWC host array of trials: the side
+  spike_metrics.triplet_scores takes."""
+  states = spike_metrics.binary_states(
+      spikes, getattr(hparams, 'triplet_bin', TRIPLET_BIN))
+  return spike_metrics.triplet_counts(states) + (len(states),)
+
+
+def triplet_report(hparams, filename, sets):
+  """--triplet_metrics: spike_metrics.triplet_scores of the binary states of the
+  generated trials 1, 3, 5, ... against those of the recorded trials 0, 2, 4,
+  ... (`generated`), beside the same scores of the recorded trials 1, 3, 5, ...
+  against them (`floor`: what two draws of the data score at these sizes).
+  sets(hparams, trials) -> a side (singles, pairs, triplets, S), host integers;
+  the recorded side and the floor are kept across epochs."""
+  bin = int(getattr(hparams, 'triplet_bin', TRIPLET_BIN))
+  fake = _trial_spikes(hparams, filename)
+  real = getattr(hparams, '_recorded_triplets', None)
+  if real is None:  # the validation set is the same for every epoch
+    spikes = _trial_spikes(hparams, hparams.validation_cache)
+    if spikes.shape[2] < 3:
+      raise ValueError('--triplet_metrics needs three neurons, not {}'.format(
+          spikes.shape[2]))
+    if spikes.shape[1] < bin:
+      raise ValueError('trials of {} frames hold no bin of {}'.format(
+          spikes.shape[1], bin))
+    ref = sets(hparams, spikes[0::2])
+    floor = spike_metrics.triplet_scores(ref, sets(hparams, spikes[1::2]))
+    real = hparams._recorded_triplets = (ref, floor, spikes.shape[1])
+  ref, floor, frames = real
+  if fake.shape[1] != frames:
+    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
+                     .format(filename, fake.shape[1], frames))
+  generated = spike_metrics.triplet_scores(ref, sets(hparams, fake[1::2]))
+  if hparams.verbose:
+    for name in ('correlation', 'mae'):
+      key = 'triplet_cumulant_' + name
+      print('\ttriplet cumulant {:<11}  gen | floor: {:.06f} | {:.06f}'.format(
+          name, generated[key], floor[key]))
+  return dict(generated=generated, floor=floor, bin_frames=bin)
+
+
 def compute_epoch_spike_metrics(hparams, filename, epoch):
   """:483-497 without plot_signals / raster_plots: dict of the statistics."""
   if not h5_helper.contains(filename, 'spikes'):
@@ -506,6 +567,8 @@ def compute_epoch_spike_metrics(hparams, filename, epoch):
   if getattr(hparams, 'state_metrics', False):
     out['states'] = state_report(hparams, filename, state_sets_host,
                                  spike_metrics.state_neighbours)
+  if getattr(hparams, 'triplet_metrics', False):
+    out['triplets'] = triplet_report(hparams, filename, triplet_sets_host)
   return out
 
 
@@ -728,6 +791,17 @@ def state_sets_device(hparams, spikes):
       for batch in _batches(hparams, spikes))
 
 
+def triplet_sets_device(hparams, spikes):
+  """`triplet_sets_host` through cg_binary_words, a batch of trials at a time,
+  and one cg_triplet_counts of the side; the integers come to the host."""
+  words = spike_metrics.DeviceWords.cat(
+      spike_metrics.binary_words_device(
+          batch, getattr(hparams, 'triplet_bin', TRIPLET_BIN))
+      for batch in _batches(hparams, spikes))
+  counts, S = spike_metrics.triplet_counts_device(words)
+  return tuple(x.cpu().numpy().astype(np.int64) for x in counts) + (S,)
+
+
 def compute_epoch_spike_metrics_device(hparams, filename, epoch):
   """`compute_epoch_spike_metrics` with the statistics from the device; the
   histograms behind the KL from cg_pair_histogram (`device_kl`) unless
@@ -773,6 +847,8 @@ def compute_epoch_spike_metrics_device(hparams, filename, epoch):
   if getattr(hparams, 'state_metrics', False):
     out['states'] = state_report(hparams, filename, state_sets_device,
                                  spike_metrics.state_neighbours_device)
+  if getattr(hparams, 'triplet_metrics', False):
+    out['triplets'] = triplet_report(hparams, filename, triplet_sets_device)
   return out
 
 
@@ -881,6 +957,15 @@ def build_parser():
   parser.add_argument('--state_bin', type=int, default=argparse.SUPPRESS,
                       help='--state_metrics: frames per bin of a state '
                       '(default 12, at most 127)')
+  parser.add_argument('--triplet_metrics', action='store_true',
+                      default=argparse.SUPPRESS,
+                      help='also report `triplets`: the connected third-order '
+                      'correlations of all neuron triplets, generated against '
+                      'recorded, beside the floor two halves of the recorded '
+                      'trials score')
+  parser.add_argument('--triplet_bin', type=int, default=argparse.SUPPRESS,
+                      help='--triplet_metrics: frames per bin of a binary state '
+                      '(default 12)')
   return parser
 
 

@@ -1090,6 +1090,62 @@ int cg_state_neighbours(const void* a, int Sa, const void* b, int Sb, int C,
                         int* knn, int* within, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Third-order spike counts of binarised population states (triplets.hip;
+ * compute_metrics.py --triplet_metrics: the connected third-order correlation
+ * of all neuron triplets; not in the reference, whose figures stop at pairs).
+ * Added under ABI 20; the same code in both precision builds.
+ * ------------------------------------------------------------------------- */
+/* The binary state of neuron c in bin b of trial n (the numpy statement is
+ * spike_metrics.binary_states):
+ *   x[n * nb + b][c] = 1 iff some t in [b bin, (b + 1) bin) has trains[n * s_b +
+ *                      t * s_t + c * s_c] != 0,   nb = T / bin (a partial bin is
+ *                      dropped)
+ * (a NaN is a spike, -0.0 is not), packed 32 states to a word, neuron-major:
+ *   words[c * row_stride + n * wpt + w], wpt = ceil(nb / 32), bit b % 32 of word
+ *   b / 32 of trial n is x[n * nb + b][c]; the tail bits of a trial's last word
+ *   are zero.
+ * Strides in elements, any values; every element of the whole bins is read once.
+ * words: uint32, 16-byte aligned.  One launch; every word of the C x B wpt block
+ * is written exactly once by a plain store and nothing else is written; nothing
+ * has to be zeroed beforehand.
+ * CG_EINVAL (nothing launched, nothing written): a NULL trains or words, words
+ * not 16-byte aligned, B or T < 1, bin < 1, T < bin, C outside 3 ..
+ * CG_TRIPLET_MAX_C, B wpt > CG_TRIPLET_MAX_WORDS, row_stride < B wpt. */
+#define CG_TRIPLET_MAX_C 512
+#define CG_TRIPLET_MAX_WORDS 67108863
+int cg_binary_words(const float* trains, int B, int T, int C, long long s_b,
+                    long long s_t, long long s_c, int bin, void* words,
+                    long long row_stride, void* stream);
+/* Counts of the states in which one, two and three neurons are active together,
+ * from W words a neuron as cg_binary_words writes them (the numpy statement is
+ * spike_metrics.triplet_counts):
+ *   singles[i]      = sum_w popcount(w_i)                      int32 [C]
+ *   pairs[i * C + j] = sum_w popcount(w_i & w_j)               int32 [C][C],
+ *                      symmetric, the singles on the diagonal
+ *   triplets[r]     = sum_w popcount(w_i & w_j & w_k)          int32 [C(C,3)],
+ *                      r the rank of i < j < k in lexicographic order
+ * A zero bit counts nothing, so padding bits may sit anywhere.  Every count is
+ * at most 32 W < 2^31 (CG_TRIPLET_MAX_WORDS = 2^26 - 1): exact, no other bound.
+ * The neurons are cut into tiles of 16; a workgroup owns one tile triple I <= J
+ * <= K over a run of 64-word chunks staged in LDS, a lane two (j, k) pairs whose
+ * AND it forms once per word, walking the 16 words of I as broadcast LDS reads
+ * into 32 register accumulators (v_and_b32, v_bcnt_u32_b32).  Where the tile
+ * triples are few the words are split over up to 64 workgroups a triple (a
+ * function of C and W alone), whose partial counts go to ws, and one more
+ * launch adds them in split order.  No atomics, nothing to zero beforehand, no
+ * host sync, every output written exactly once, the same bits every call.
+ * cg_triplet_counts_ws_bytes: bytes of `ws` (16-byte aligned; contents do not
+ * matter), -1 for a shape cg_triplet_counts refuses.
+ * CG_EINVAL (nothing launched, nothing written): a NULL words, ws, singles,
+ * pairs or triplets; words or ws not 16-byte aligned; an output not 4-byte
+ * aligned; C outside 3 .. CG_TRIPLET_MAX_C; W outside 1 ..
+ * CG_TRIPLET_MAX_WORDS; row_stride < W. */
+long long cg_triplet_counts_ws_bytes(int C, int W);
+int cg_triplet_counts(const void* words, int C, int W, long long row_stride,
+                      int* singles, int* pairs, int* triplets, void* ws,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------
  * Recording datasets (windows.hip; the reference's generate_tfrecords.py cuts a
  * (neurons, T) recording into overlapping stride-2 windows and writes each one
  * out; here the recording stays resident and every step's windows are cut
