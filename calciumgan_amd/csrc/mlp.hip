@@ -14,8 +14,13 @@
 // Dropout: the keep decision of element e of a layer's (rows x out) output is
 // word e & 3 of the Philox4x32-10 block with counter (e >> 2, stream id) and
 // key (seed): a pure function of its arguments, so no mask is stored.  The
-// backward kernels read the decision back from the stored h: a kept element is
-// non-zero (z = 0 exactly aside), and its sign tells the activation's slope.
+// backward kernels read the decision back from the stored h: h > 0 is a kept
+// element of slope 1, h < 0 one of slope alpha, and a stored zero of EITHER sign
+// counts as dropped (mask_of gives 0).  A KEPT element is stored as zero in three
+// cases: every z < 0 under alpha = 0 (as -0.0; its factor s alpha is 0 anyway),
+// z exactly 0, and alpha z underflowing to -0.0; in the last two the backward
+// gives 0 where the derivative is s alpha (tests/test_hip_mlp_parity.py pins
+// the rule at +0.0 and -0.0).
 #include "cg_common.h"
 
 namespace {
