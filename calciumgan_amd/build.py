@@ -18,7 +18,7 @@ SOURCES = ['swconv.hip', 'swconv_swp.hip', 'wgrad.hip', 'pointwise.hip',
            'victor_purpura.hip', 'pair_hist.hip', 'ifft.hip', 'summary.hip',
            'windows.hip', 'mlp.hip', 'patterns.hip', 'dg_fit.hip',
            'spike_ccg.hip', 'trace_psd.hip', 'nearest_stretch.hip',
-           'state_neighbours.hip', 'triplets.hip']
+           'state_neighbours.hip', 'triplets.hip', 'spike_intervals.hip']
 HEADERS = ['cg_common.h', 'swconv_args.h', 'swconv_epilogue.h', 'oasis_flat.h',
            'fft_stages.h',
            os.path.join('..', '..', 'include', 'calciumgan_hip.h')]

@@ -1336,3 +1336,203 @@ def triplet_scores(ref, other):
       'num_states': [int(ref[3]), int(other[3])],
       'num_triplets': int(Tr),
   }
+
+
+# -- inter-spike intervals and trial-to-trial variability --------------------------
+# (compute_metrics.py --interval_metrics; csrc/spike_intervals.hip)
+INTERVAL_MAX_NEURONS = 4096     # CG_INTERVAL_MAX_C
+INTERVAL_MAX_ISI = 4095         # CG_INTERVAL_MAX_ISI
+
+
+def _max_isi(max_isi):
+  max_isi = int(max_isi)
+  if not 1 <= max_isi <= INTERVAL_MAX_ISI:
+    raise ValueError('max_isi = {}: 1 .. {} expected'.format(
+        max_isi, INTERVAL_MAX_ISI))
+  return max_isi
+
+
+def interval_counts(spikes, max_isi=240):
+  """(hist (C, max_isi + 1), moments (C, 6), counts (N, C)), int64, of trials (N,
+  T, C), a frame a spike when it is != 0.  Train (n, c) has its spikes at t_1 <
+  ... < t_m and the intervals I_k = t_{k+1} - t_k (m - 1 of them, m - 2
+  consecutive pairs); no interval runs from one trial into the next.
+    hist[c][d - 1]   intervals of neuron c equal to d, 1 <= d <= max_isi, over
+                     its trials; hist[c][max_isi] those > max_isi
+    moments[c]       spikes, intervals, sum I, sum I^2, consecutive pairs, sum
+                     I_k I_{k+1} (an overflow interval with its true length)
+    counts[n][c]     spikes of train (n, c)
+  The statement cg_spike_intervals is tested against, for equality."""
+  s = np.asarray(spikes)
+  if s.ndim != 3:
+    raise ValueError('(B, T, C) expected')
+  s = s != 0   # as _binary_trials: a NaN is a spike, -0.0 is not
+  max_isi = _max_isi(max_isi)
+  N, T, C = s.shape
+  H = max_isi + 1
+  counts = s.sum(1).astype(np.int64)
+  # every spike as (neuron, trial, frame), sorted in that order
+  c, n, t = np.nonzero(s.transpose(2, 0, 1))
+  t = t.astype(np.int64)
+  same = (c[1:] == c[:-1]) & (n[1:] == n[:-1])   # the spike before: same train
+  I = (t[1:] - t[:-1])[same]
+  owner = c[1:][same]
+  hist = np.bincount(owner * H + np.minimum(I, H) - 1,
+                     minlength=C * H).reshape(C, H).astype(np.int64)
+  moments = np.zeros((C, 6), np.int64)
+  moments[:, 0] = counts.sum(0)
+  np.add.at(moments[:, 1], owner, 1)
+  np.add.at(moments[:, 2], owner, I)
+  np.add.at(moments[:, 3], owner, I * I)
+  both = same[1:] & same[:-1]                    # and the one before that
+  d = t[1:] - t[:-1]
+  np.add.at(moments[:, 4], c[2:][both], 1)
+  np.add.at(moments[:, 5], c[2:][both], (d[1:] * d[:-1])[both])
+  return hist, moments, counts
+
+
+def interval_counts_device(words, max_isi=240):
+  """`interval_counts` on the GPU (cg_spike_intervals): DeviceWords of bin 1 ->
+  (hist (C, max_isi + 1) int32, moments (C, 6) int64, counts (trials, C) int32)
+  on the device, the statement's integers.  One call, no atomics in global
+  memory, no host synchronisation."""
+  import torch
+  from ... import _lib as hip
+  if not isinstance(words, DeviceWords):
+    raise ValueError('DeviceWords expected')
+  max_isi = _max_isi(max_isi)
+  t = words.tensor
+  if words.bin != 1:
+    raise ValueError('words of bin 1 expected, not {}'.format(words.bin))
+  if not t.is_contiguous():
+    raise ValueError('contiguous words expected')
+  C, W = int(t.shape[0]), int(t.shape[1])
+  trials, wpt = words.trials, -(-words.nb // 32)
+  if W != trials * wpt:
+    raise ValueError('{} words are no {} trials of {}'.format(W, trials, wpt))
+  need = hip.load().cg_spike_intervals_ws_bytes(C, trials, wpt, max_isi)
+  if need < 0:
+    raise ValueError('cg_spike_intervals: unsupported shape (C = {}, trials = '
+                     '{}, wpt = {})'.format(C, trials, wpt))
+  dev = t.device
+  ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+  hist = torch.empty(C, max_isi + 1, dtype=torch.int32, device=dev)
+  moments = torch.empty(C, 6, dtype=torch.int64, device=dev)
+  counts = torch.empty(trials, C, dtype=torch.int32, device=dev)
+  hip.call('cg_spike_intervals', t, C, trials, wpt, W, max_isi, hist, moments,
+           counts, ws, hip.stream())
+  return hist, moments, counts
+
+
+def _interval_side(side):
+  hist, moments, counts = (_state_host(x).astype(np.int64) for x in side)
+  if not (hist.ndim == 2 and hist.shape[1] >= 2 and counts.ndim == 2 and
+          moments.shape == (len(hist), 6) and counts.shape[1] == len(hist)):
+    raise ValueError('hist (C, max_isi + 1), moments (C, 6), counts (N, C) '
+                     'expected')
+  if len(counts) < 2:
+    raise ValueError('{} trial(s): the Fano factor needs two'.format(
+        len(counts)))
+  m = moments.astype(np.float64)
+  nan = np.full(len(hist), np.nan)
+  some = m[:, 1] > 0
+  mu, var, cv, rho = nan.copy(), nan.copy(), nan.copy(), nan.copy()
+  mu[some] = m[some, 2] / m[some, 1]
+  var[some] = m[some, 3] / m[some, 1] - mu[some] ** 2
+  cv[some] = np.sqrt(np.maximum(var[some], 0.0)) / mu[some]
+  serial = some & (m[:, 4] >= 1) & (var > 0)
+  rho[serial] = (m[serial, 5] / m[serial, 4] - mu[serial] ** 2) / var[serial]
+  x = counts.astype(np.float64)
+  mean = x.mean(0)
+  d = x - mean
+  ss = (d * d).sum(0)
+  fano = nan.copy()
+  on = mean != 0
+  fano[on] = ss[on] / (len(x) - 1) / mean[on]
+  varies = ss > 0
+  r = np.full((len(hist), len(hist)), np.nan)
+  if varies.any():
+    v = np.flatnonzero(varies)
+    r[np.ix_(v, v)] = (d[:, v].T @ d[:, v]) / np.sqrt(np.outer(ss[v], ss[v]))
+  return dict(hist=hist, n=moments[:, 1], pairs=moments[:, 4], mu=mu, var=var,
+              cv=cv, rho=rho, serial=serial, fano=fano, on=on, varies=varies,
+              r=r, counts=counts)
+
+
+def interval_scores(ref, other):
+  """How far the inter-spike intervals and the trial-to-trial variability of
+  `other` are from those of `ref`; each side (hist, moments, counts) as
+  `interval_counts` or `interval_counts_device` gives them.  Host float64,
+  whichever device counted.  Per neuron, with n intervals: mu = sum I / n,
+  sigma^2 = sum I^2 / n - mu^2, CV = sqrt(max(sigma^2, 0)) / mu, rho = (sum I_k
+  I_{k+1} / pairs - mu^2) / sigma^2 (the stationary estimator of the lag-1
+  serial correlation), F = var(counts, ddof=1) / mean(counts) over the trials.
+    isi_js_bits            mean, over the neurons with an interval on both
+                           sides, of the Jensen-Shannon divergence in bits of
+                           the two hist / n (the overflow bin included)
+    isi_js_bits_pooled     the same of the histograms summed over the neurons
+    isi_mean_mae           mean |mu_ref - mu_other| in frames, the same neurons
+    cv_mae, cv_correlation, cv_mean   over the neurons with two intervals on
+                           both sides; cv_mean is [ref, other]
+    serial_correlation_mae, serial_correlation_mean   over the neurons with a
+                           pair and sigma^2 > 0 on both sides
+    adjacent_fraction, overflow_fraction   [ref, other]: share of all intervals
+                           equal to 1 frame, and > max_isi
+    fano_mae, fano_correlation, fano_mean   over the neurons with a non-zero
+                           mean count on both sides
+    count_correlation_mae, count_correlation_correlation   Pearson r of the
+                           counts of neurons i < j across trials, over the pairs
+                           whose two neurons vary on both sides
+    silent_trains          [ref, other]: share of trains with no spike
+    num_trials, num_intervals, max_isi   [ref, other], [ref, other], as used
+  A figure over an empty set is NaN, a correlation with fewer than two values
+  or no variance on a side too.  Sides of different C or max_isi, or a side of
+  fewer than two trials, raise ValueError."""
+  a, b = _interval_side(ref), _interval_side(other)
+  if a['hist'].shape != b['hist'].shape:
+    raise ValueError('sides of one C and one max_isi expected')
+  nan = float('nan')
+
+  def mean(x):
+    return float(np.mean(x)) if np.size(x) else nan
+
+  def share(s, column):
+    total = int(s['n'].sum())
+    return float(s['hist'][:, column].sum()) / total if total else nan
+
+  one = np.flatnonzero((a['n'] >= 1) & (b['n'] >= 1))
+  js = [_js_divergence_bits(a['hist'][c] / float(a['n'][c]),
+                            b['hist'][c] / float(b['n'][c])) for c in one]
+  pa, pb = a['hist'].sum(0), b['hist'].sum(0)
+  pooled = (_js_divergence_bits(pa / float(pa.sum()), pb / float(pb.sum()))
+            if pa.sum() and pb.sum() else nan)
+  two = (a['n'] >= 2) & (b['n'] >= 2)
+  ser = a['serial'] & b['serial']
+  on = a['on'] & b['on']
+  ju, ku = np.triu_indices(len(a['n']), 1)
+  vary = a['varies'] & b['varies']
+  sel = vary[ju] & vary[ku]
+  ra, rb = a['r'][ju[sel], ku[sel]], b['r'][ju[sel], ku[sel]]
+  return {
+      'isi_js_bits': mean(js),
+      'isi_js_bits_pooled': pooled,
+      'isi_mean_mae': _mean_abs_difference(a['mu'][one], b['mu'][one]),
+      'cv_mae': _mean_abs_difference(a['cv'][two], b['cv'][two]),
+      'cv_correlation': _pearson(a['cv'][two], b['cv'][two]),
+      'cv_mean': [mean(a['cv'][two]), mean(b['cv'][two])],
+      'serial_correlation_mae': _mean_abs_difference(a['rho'][ser],
+                                                     b['rho'][ser]),
+      'serial_correlation_mean': [mean(a['rho'][ser]), mean(b['rho'][ser])],
+      'adjacent_fraction': [share(a, 0), share(b, 0)],
+      'overflow_fraction': [share(a, -1), share(b, -1)],
+      'fano_mae': _mean_abs_difference(a['fano'][on], b['fano'][on]),
+      'fano_correlation': _pearson(a['fano'][on], b['fano'][on]),
+      'fano_mean': [mean(a['fano'][on]), mean(b['fano'][on])],
+      'count_correlation_mae': _mean_abs_difference(ra, rb),
+      'count_correlation_correlation': _pearson(ra, rb),
+      'silent_trains': [float(np.mean(a['counts'] == 0)),
+                        float(np.mean(b['counts'] == 0))],
+      'num_trials': [int(len(a['counts'])), int(len(b['counts']))],
+      'num_intervals': [int(a['n'].sum()), int(b['n'].sum())],
+      'max_isi': int(a['hist'].shape[1] - 1),
+  }

@@ -18,6 +18,7 @@ the reference's compute_metrics.py (BASELINE configs[3]: recorded-data pipeline
       [--novelty_metrics [--novelty_step 2]]
       [--state_metrics [--state_k 5] [--state_bin 12]]
       [--triplet_metrics [--triplet_bin 12]]
+      [--interval_metrics [--max_isi 240]]
 
 --device gpu (not a reference flag) takes the deconvolution, the firing rates,
 the per-trial correlations and the van Rossum matrices through the HIP kernels
@@ -119,6 +120,21 @@ the states 32 to a word in batches of --batch_trials and cg_triplet_counts
 (csrc/triplets.hip: AND and popcount, exact with no bound on the counts) counts
 a side in one call.  Only integers come to the host, so both devices write the
 same dict.
+
+--interval_metrics [--max_isi 240] (not reference flags, absent from the
+namespace unless given) adds `intervals`: the inter-spike-interval histogram of
+every neuron (bins of 1 .. --max_isi frames and one overflow bin), its
+coefficient of variation and the serial correlation of consecutive intervals,
+and across trials the Fano factor of the spike count and the count ("noise")
+correlations of neuron pairs (spike_metrics.interval_scores).  The
+autocorrelogram of --temporal_metrics stops at --max_lag frames, short of most
+intervals; every covariance above is taken within a trial, so a generator whose
+trials all carry the expected count passes them.  `generated`, `floor` and the
+trials they are taken from are --state_metrics'.  spike_metrics.interval_counts
+on the host; on the device cg_binary_words at bin 1 packs the frames 32 to a
+word in batches of --batch_trials and cg_spike_intervals
+(csrc/spike_intervals.hip) counts a side in one call.  Only integers come to
+the host, so both devices write the same dict.
 
 The KL is the reference's: both samples cut into 30 equal-width bins over their
 pooled range by pandas.cut, empty bins replaced by 1e-10 (:80-111) -- pandas is
@@ -527,6 +543,49 @@ def triplet_report(hparams, filename, sets):
   return dict(generated=generated, floor=floor, bin_frames=bin)
 
 
+MAX_ISI = 240  # --max_isi (10 s of frames)
+
+
+def interval_sets_host(hparams, spikes):
+  """(hist, moments, counts) of an NWC host array of trials: the side
+  spike_metrics.interval_scores takes."""
+  return spike_metrics.interval_counts(
+      spikes, getattr(hparams, 'max_isi', MAX_ISI))
+
+
+def interval_report(hparams, filename, sets):
+  """--interval_metrics: spike_metrics.interval_scores of the generated trials
+  1, 3, 5, ... against the recorded trials 0, 2, 4, ... (`generated`), beside
+  the same scores of the recorded trials 1, 3, 5, ... against them (`floor`:
+  what two draws of the data score at these sizes).  sets(hparams, trials) -> a
+  side (hist, moments, counts), host integers; the recorded side and the floor
+  are kept across epochs."""
+  max_isi = int(getattr(hparams, 'max_isi', MAX_ISI))
+  fake = _trial_spikes(hparams, filename)
+  real = getattr(hparams, '_recorded_intervals', None)
+  if real is None:  # the validation set is the same for every epoch
+    spikes = _trial_spikes(hparams, hparams.validation_cache)
+    if len(spikes[1::2]) < 2:
+      raise ValueError('--interval_metrics needs two trials a side, the '
+                       'validation cache holds {} in all'.format(len(spikes)))
+    ref = sets(hparams, spikes[0::2])
+    floor = spike_metrics.interval_scores(ref, sets(hparams, spikes[1::2]))
+    real = hparams._recorded_intervals = (ref, floor, spikes.shape[1])
+  ref, floor, frames = real
+  if fake.shape[1] != frames:
+    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
+                     .format(filename, fake.shape[1], frames))
+  if len(fake[1::2]) < 2:
+    raise ValueError('--interval_metrics needs two trials a side, {} holds {} '
+                     'in all'.format(filename, len(fake)))
+  generated = spike_metrics.interval_scores(ref, sets(hparams, fake[1::2]))
+  if hparams.verbose:
+    for key in ('cv_mae', 'isi_js_bits', 'fano_mae'):
+      print('\tinterval {:<12}  gen | floor: {:.06f} | {:.06f}'.format(
+          key, generated[key], floor[key]))
+  return dict(generated=generated, floor=floor, max_isi=max_isi)
+
+
 def compute_epoch_spike_metrics(hparams, filename, epoch):
   """:483-497 without plot_signals / raster_plots: dict of the statistics."""
   if not h5_helper.contains(filename, 'spikes'):
@@ -569,6 +628,8 @@ def compute_epoch_spike_metrics(hparams, filename, epoch):
                                  spike_metrics.state_neighbours)
   if getattr(hparams, 'triplet_metrics', False):
     out['triplets'] = triplet_report(hparams, filename, triplet_sets_host)
+  if getattr(hparams, 'interval_metrics', False):
+    out['intervals'] = interval_report(hparams, filename, interval_sets_host)
   return out
 
 
@@ -802,6 +863,24 @@ def triplet_sets_device(hparams, spikes):
   return tuple(x.cpu().numpy().astype(np.int64) for x in counts) + (S,)
 
 
+def interval_sets_device(hparams, spikes):
+  """`interval_sets_host` through cg_binary_words at bin 1, a batch of trials at
+  a time, and one cg_spike_intervals of the side; the integers come to the
+  host."""
+  C = spikes.shape[2]
+  if not 3 <= C <= spike_metrics.TRIPLET_MAX_NEURONS:
+    raise ValueError('--interval_metrics --device gpu packs the trains with '
+                     'cg_binary_words, which takes 3 .. {} neurons, not {} '
+                     '(--device cpu takes any)'.format(
+                         spike_metrics.TRIPLET_MAX_NEURONS, C))
+  words = spike_metrics.DeviceWords.cat(
+      spike_metrics.binary_words_device(batch, 1)
+      for batch in _batches(hparams, spikes))
+  return tuple(x.cpu().numpy().astype(np.int64)
+               for x in spike_metrics.interval_counts_device(
+                   words, getattr(hparams, 'max_isi', MAX_ISI)))
+
+
 def compute_epoch_spike_metrics_device(hparams, filename, epoch):
   """`compute_epoch_spike_metrics` with the statistics from the device; the
   histograms behind the KL from cg_pair_histogram (`device_kl`) unless
@@ -849,6 +928,8 @@ def compute_epoch_spike_metrics_device(hparams, filename, epoch):
                                  spike_metrics.state_neighbours_device)
   if getattr(hparams, 'triplet_metrics', False):
     out['triplets'] = triplet_report(hparams, filename, triplet_sets_device)
+  if getattr(hparams, 'interval_metrics', False):
+    out['intervals'] = interval_report(hparams, filename, interval_sets_device)
   return out
 
 
@@ -966,6 +1047,18 @@ def build_parser():
   parser.add_argument('--triplet_bin', type=int, default=argparse.SUPPRESS,
                       help='--triplet_metrics: frames per bin of a binary state '
                       '(default 12)')
+  # (absent unless given, like --victor_purpura)
+  parser.add_argument('--interval_metrics', action='store_true',
+                      default=argparse.SUPPRESS,
+                      help='also report `intervals`: inter-spike-interval '
+                      'histogram, CV and serial correlation, Fano factor and '
+                      'count correlations across trials, generated against '
+                      'recorded, beside the floor two halves of the recorded '
+                      'trials score')
+  parser.add_argument('--max_isi', type=int, default=argparse.SUPPRESS,
+                      help='--interval_metrics: the longest interval with a '
+                      'histogram bin of its own, in frames (default 240, at '
+                      'most 4095)')
   return parser
 
 

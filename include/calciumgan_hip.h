@@ -1146,6 +1146,51 @@ int cg_triplet_counts(const void* words, int C, int W, long long row_stride,
                       void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Inter-spike intervals and spike counts of spike trains (spike_intervals.hip;
+ * compute_metrics.py --interval_metrics: ISI histogram, CV, serial correlation,
+ * Fano factor and count correlations; not in the reference).  Added under ABI
+ * 20; the same code in both precision builds.
+ * ------------------------------------------------------------------------- */
+/* From the words of cg_binary_words at bin = 1 (uint32, row c at c *
+ * row_stride, trial n's wpt words at n * wpt, bit t % 32 of word t / 32 the
+ * frame t; a zero bit is no spike, so padding bits may sit anywhere).  Train
+ * (n, c) has its spikes at t_1 < ... < t_m and the intervals I_k = t_{k+1} -
+ * t_k; no interval runs from one trial into the next.  The numpy statement is
+ * spike_metrics.interval_counts:
+ *   hist[c * (max_isi + 1) + d - 1]  intervals of neuron c equal to d, 1 <= d <=
+ *                                    max_isi, over its trials; [.. + max_isi]
+ *                                    those > max_isi       int32 [C][max_isi + 1]
+ *   moments[c * 6 + 0 .. 5]          spikes, intervals, sum I, sum I^2,
+ *                                    consecutive pairs, sum I_k I_{k+1} (an
+ *                                    overflow interval with its true length)
+ *                                                          int64 [C][6]
+ *   counts[n * C + c]                spikes of train (n, c)   int32 [trials][C]
+ * trials wpt <= CG_TRIPLET_MAX_WORDS keeps every int32 below 2^31 and every
+ * int64 below 2^62: exact, no other bound.
+ * A workgroup owns a neuron and a run of trials, a wave a trial at a time in
+ * chunks of 64 words, a word a lane; the two spikes before a lane's word come
+ * from the ballot of the non-empty words and three cross-lane reads (a carry
+ * between chunks), the set bits are walked by count-trailing-zeros into an LDS
+ * histogram and register sums.  Where the neurons are few the trials are split
+ * over up to 64 workgroups a neuron (a function of C and trials alone), whose
+ * partial results go to ws, and one more launch adds them in split order.  No
+ * global atomics, nothing to zero beforehand, no host sync, every output
+ * written exactly once, the same bits every call.
+ * cg_spike_intervals_ws_bytes: bytes of `ws` (16-byte aligned; contents do not
+ * matter; at least 16), -1 for a shape cg_spike_intervals refuses.
+ * CG_EINVAL (nothing launched, nothing written): a NULL words, ws, hist,
+ * moments or counts; words or ws not 16-byte aligned; hist or counts not 4-byte
+ * aligned; moments not 8-byte aligned; C outside 1 .. CG_INTERVAL_MAX_C; trials
+ * or wpt < 1; trials wpt > CG_TRIPLET_MAX_WORDS; max_isi outside 1 ..
+ * CG_INTERVAL_MAX_ISI; row_stride < trials wpt. */
+#define CG_INTERVAL_MAX_C 4096
+#define CG_INTERVAL_MAX_ISI 4095
+long long cg_spike_intervals_ws_bytes(int C, int trials, int wpt, int max_isi);
+int cg_spike_intervals(const void* words, int C, int trials, int wpt,
+                       long long row_stride, int max_isi, int* hist,
+                       long long* moments, int* counts, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Recording datasets (windows.hip; the reference's generate_tfrecords.py cuts a
  * (neurons, T) recording into overlapping stride-2 windows and writes each one
  * out; here the recording stays resident and every step's windows are cut
