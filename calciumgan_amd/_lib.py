@@ -247,6 +247,18 @@ def call(name, *args):
   check(rc, name)
 
 
+def workspace(query, device, *args, least=0):
+  """The workspace an entry point asks for: a uint8 tensor on `device` of the
+  bytes its size query `query`(*args) returns (so numel() is the size to hand
+  to the entry point), of `least` bytes where that is more, None for no bytes
+  at all.  A shape the entry point refuses (the query's -1) is a ValueError."""
+  need = getattr(load(), query)(*args)
+  if need < 0:
+    raise ValueError('{}: unsupported shape {}'.format(query, args))
+  size = max(need, least)
+  return torch.empty(size, dtype=torch.uint8, device=device) if size else None
+
+
 def stream():
   """The current torch stream as the `void* stream` argument."""
   return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -20,6 +20,7 @@ import math
 import numpy as np
 
 from .spike_helper import FRAME_RATE
+from .spike_metrics import _host, _trial_batch
 
 # lengths cg_trace_psd takes (csrc/trace_psd.hip): powers of two in this range
 PSD_DEVICE_MIN_LENGTH = 32
@@ -105,19 +106,13 @@ def trace_power_spectrum_device(signals):
   totals come back up as a device tensor."""
   import torch
   from ... import _lib as hip
-  if not (torch.is_tensor(signals) and signals.is_cuda and
-          signals.dtype == torch.float32 and signals.dim() == 3):
-    raise ValueError('float32 device tensor (B, T, C) expected')
-  B, T, C = signals.shape
+  B, T, C = _trial_batch(signals)
   if B < 1 or T < 2 or C < 1:
     raise ValueError('(B, T, C) trials with B, C >= 1 and T >= 2 expected')
   if (T & (T - 1)) or not PSD_DEVICE_MIN_LENGTH <= T <= PSD_DEVICE_MAX_LENGTH:
     return torch.from_numpy(trace_power_spectrum(signals.cpu().numpy())).to(
         signals.device)
-  nbytes = hip.load().cg_trace_psd_ws_bytes(B, T, C)
-  if nbytes < 0:
-    raise ValueError('cg_trace_psd: unsupported shape {}'.format((B, T, C)))
-  ws = torch.empty(nbytes, dtype=torch.uint8, device=signals.device)
+  ws = hip.workspace('cg_trace_psd_ws_bytes', signals.device, B, T, C)
   totals = torch.empty(T // 2 + 1, C, dtype=torch.float64,
                        device=signals.device)
   hip.call('cg_trace_psd', signals, B, T, C, signals.stride(0),
@@ -358,13 +353,10 @@ def nearest_stretch_device(queries, recording, step=1, exclude=None,
     exclude = exclude.to(device=queries.device, dtype=torch.int32).contiguous()
     if exclude.shape != (N,):
       raise ValueError('exclude: one start row per query expected')
-  nbytes = hip.load().cg_nearest_stretch_ws_bytes(N, L, C, T_raw, int(step))
-  if nbytes < 0:
-    raise ValueError('cg_nearest_stretch: unsupported shape {}'.format(
-        (N, L, C, T_raw, int(step))))
   dev = queries.device
+  ws = hip.workspace('cg_nearest_stretch_ws_bytes', dev, N, L, C, T_raw,
+                     int(step))
   S = stretch_offsets(T_raw, L, step)
-  ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
   nearest = torch.empty(N, dtype=torch.float64, device=dev)
   index = torch.empty(N, dtype=torch.int32, device=dev)
   d2 = (torch.empty(N, S, dtype=torch.float64, device=dev)
@@ -402,10 +394,6 @@ def recorded_starts(S, n, step):
   the recording."""
   i = np.arange(int(n), dtype=np.int64)
   return int(step) * ((i * (int(S) - 1)) // max(int(n) - 1, 1))
-
-
-def _host(x):
-  return np.asarray(x.cpu() if hasattr(x, 'cpu') else x)
 
 
 def novelty_scores(recorded, generated, L, C, step, offsets=None):

@@ -319,10 +319,7 @@ def batch_statistics_device(spikes):
   often: equal to ~1e-7 relative)."""
   import torch
   from ... import _lib as hip
-  if not (torch.is_tensor(spikes) and spikes.is_cuda and
-          spikes.dtype == torch.float32 and spikes.dim() == 3):
-    raise ValueError('float32 device tensor (B, T, C) expected')
-  B, T, C = spikes.shape
+  B, T, C = _trial_batch(spikes)
   rates = torch.empty(B, C, dtype=torch.float32, device=spikes.device)
   covs = torch.empty(B, C * (C + 1) // 2, dtype=torch.float32,
                      device=spikes.device)
@@ -357,12 +354,18 @@ def error_sums_device(rates_a, rates_b, covs_a, covs_b):
 VAN_ROSSUM_CHUNK = 16
 
 
-def _trial_batch(spikes):
+def _trial_batch(spikes, shape='(B, T, C)'):
+  """The shape of a batch of trials as every device wrapper takes it."""
   import torch
   if not (torch.is_tensor(spikes) and spikes.is_cuda and
           spikes.dtype == torch.float32 and spikes.dim() == 3):
-    raise ValueError('float32 device tensor (B, T, C) expected')
+    raise ValueError('float32 device tensor {} expected'.format(shape))
   return spikes.shape
+
+
+def _host(x):
+  """A device tensor, or anything numpy takes, as a host array; None stays."""
+  return None if x is None else np.asarray(x.cpu() if hasattr(x, 'cpu') else x)
 
 
 def van_rossum_distance_device(spikes, tau=1.0, return_gram=False):
@@ -405,14 +408,11 @@ def victor_purpura_distance_device(spikes, q=1.0):
   import torch
   from ... import _lib as hip
   B, T, C = _trial_batch(spikes)
-  nbytes = hip.load().cg_victor_purpura_ws_bytes(B, T, C)
-  if nbytes < 0:
-    raise ValueError('cg_victor_purpura: unsupported shape {}'.format((B, T, C)))
-  ws = torch.empty(nbytes, dtype=torch.uint8, device=spikes.device)
+  ws = hip.workspace('cg_victor_purpura_ws_bytes', spikes.device, B, T, C)
   dist = torch.empty(B, C, C, dtype=torch.float64, device=spikes.device)
   hip.call('cg_victor_purpura', spikes, B, T, C, spikes.stride(0),
            spikes.stride(1), spikes.stride(2), victor_purpura_cost(q), dist, ws,
-           nbytes, hip.stream())
+           ws.numel(), hip.stream())
   return dist
 
 
@@ -561,19 +561,13 @@ def pattern_histogram_device(spikes):
   synchronisation."""
   import torch
   from ... import _lib as hip
-  if not (torch.is_tensor(spikes) and spikes.is_cuda and
-          spikes.dtype == torch.float32 and spikes.dim() == 3):
-    raise ValueError('float32 device tensor (N, T, C) expected')
-  N, T, C = spikes.shape
-  nbytes = hip.load().cg_pattern_hist_ws_bytes(N, T, C)
-  if nbytes < 0:
-    raise ValueError('cg_pattern_histogram: unsupported shape {} (N >= 1, '
-                     '1 <= T C <= {})'.format((N, T, C), PATTERN_MAX_BITS))
-  ws = (torch.empty(nbytes, dtype=torch.uint8, device=spikes.device)
-        if nbytes else None)
+  N, T, C = _trial_batch(spikes, '(N, T, C)')
+  # (refused: N < 1 or T C outside 1 .. PATTERN_MAX_BITS)
+  ws = hip.workspace('cg_pattern_hist_ws_bytes', spikes.device, N, T, C)
   counts = torch.empty(1 << (T * C), dtype=torch.int64, device=spikes.device)
   hip.call('cg_pattern_histogram', spikes, N, T, C, spikes.stride(0),
-           spikes.stride(1), spikes.stride(2), counts, ws, nbytes, hip.stream())
+           spikes.stride(1), spikes.stride(2), counts, ws,
+           0 if ws is None else ws.numel(), hip.stream())
   return counts
 
 
@@ -1001,21 +995,14 @@ def state_neighbours_device(a, b, k, exclude_self=False, radius_b=None,
       raise ValueError('radius_b (Sb,) expected')
   elif not knn:
     raise ValueError('nothing asked for: knn=False without radius_b')
-  need = hip.load().cg_state_neighbours_ws_bytes(Sa, Sb, a.C, a.bin, k)
-  if need < 0:
-    raise ValueError('cg_state_neighbours: unsupported shape (Sa = {}, Sb = {}, '
-                     'C = {}, bin = {}, k = {})'.format(Sa, Sb, a.C, a.bin, k))
-  ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+  ws = hip.workspace('cg_state_neighbours_ws_bytes', dev, Sa, Sb, a.C, a.bin, k,
+                     least=16)
   out = torch.empty(Sa, k, dtype=torch.int32, device=dev) if knn else None
   within = (torch.empty(Sa, dtype=torch.int32, device=dev)
             if radius_b is not None else None)
   hip.call('cg_state_neighbours', ta, Sa, tb, Sb, a.C, a.bin, k,
            1 if exclude_self else 0, radius_b, out, within, ws, hip.stream())
   return out, within
-
-
-def _state_host(x):
-  return None if x is None else np.asarray(x.cpu() if hasattr(x, 'cpu') else x)
 
 
 def state_radii(states, k, neighbours=state_neighbours):
@@ -1026,7 +1013,7 @@ def state_radii(states, k, neighbours=state_neighbours):
   if len(states) <= k:
     raise ValueError('a set of {} states has no {}-th neighbour'.format(
         len(states), k))
-  return _state_host(neighbours(states, states, k, exclude_self=True)[0])[
+  return _host(neighbours(states, states, k, exclude_self=True)[0])[
       :, k - 1].astype(np.int32)
 
 
@@ -1057,9 +1044,9 @@ def state_scores(ref, other, k, neighbours=state_neighbours, rad_ref=None):
     rad_ref = state_radii(ref, k, neighbours)
   rad_ref = np.asarray(rad_ref).astype(np.int32)
   rad_other = state_radii(other, k, neighbours)
-  knn_o, within_o = (_state_host(x)
+  knn_o, within_o = (_host(x)
                      for x in neighbours(other, ref, k, radius_b=rad_ref))
-  knn_r, within_r = (_state_host(x)
+  knn_r, within_r = (_host(x)
                      for x in neighbours(ref, other, k, radius_b=rad_other))
   near_r, near_o = knn_r[:, 0].astype(np.int64), knn_o[:, 0].astype(np.int64)
 
@@ -1246,12 +1233,8 @@ def triplet_counts_device(words):
   if not t.is_contiguous():
     raise ValueError('contiguous words expected')
   C, W = int(t.shape[0]), int(t.shape[1])
-  need = hip.load().cg_triplet_counts_ws_bytes(C, W)
-  if need < 0:
-    raise ValueError('cg_triplet_counts: unsupported shape (C = {}, W = {})'
-                     .format(C, W))
   dev = t.device
-  ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+  ws = hip.workspace('cg_triplet_counts_ws_bytes', dev, C, W, least=16)
   singles = torch.empty(C, dtype=torch.int32, device=dev)
   pairs = torch.empty(C, C, dtype=torch.int32, device=dev)
   triplets = torch.empty(C * (C - 1) * (C - 2) // 6, dtype=torch.int32,
@@ -1268,9 +1251,9 @@ def _triplet_moments(side):
   S = int(S)
   if S < 1:
     raise ValueError('no states')
-  p1 = _state_host(singles).astype(np.float64) / S
-  p2 = _state_host(pairs).astype(np.float64) / S
-  p3 = _state_host(triplets).astype(np.float64) / S
+  p1 = _host(singles).astype(np.float64) / S
+  p2 = _host(pairs).astype(np.float64) / S
+  p3 = _host(triplets).astype(np.float64) / S
   C = len(p1)
   if C < 3 or p2.shape != (C, C) or p3.shape != (C * (C - 1) * (C - 2) // 6,):
     raise ValueError('singles (C,), pairs (C, C), triplets (C(C,3),), C >= 3, '
@@ -1410,12 +1393,9 @@ def interval_counts_device(words, max_isi=240):
   trials, wpt = words.trials, -(-words.nb // 32)
   if W != trials * wpt:
     raise ValueError('{} words are no {} trials of {}'.format(W, trials, wpt))
-  need = hip.load().cg_spike_intervals_ws_bytes(C, trials, wpt, max_isi)
-  if need < 0:
-    raise ValueError('cg_spike_intervals: unsupported shape (C = {}, trials = '
-                     '{}, wpt = {})'.format(C, trials, wpt))
   dev = t.device
-  ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+  ws = hip.workspace('cg_spike_intervals_ws_bytes', dev, C, trials, wpt, max_isi,
+                     least=16)
   hist = torch.empty(C, max_isi + 1, dtype=torch.int32, device=dev)
   moments = torch.empty(C, 6, dtype=torch.int64, device=dev)
   counts = torch.empty(trials, C, dtype=torch.int32, device=dev)
@@ -1425,7 +1405,7 @@ def interval_counts_device(words, max_isi=240):
 
 
 def _interval_side(side):
-  hist, moments, counts = (_state_host(x).astype(np.int64) for x in side)
+  hist, moments, counts = (_host(x).astype(np.int64) for x in side)
   if not (hist.ndim == 2 and hist.shape[1] >= 2 and counts.ndim == 2 and
           moments.shape == (len(hist), 6) and counts.shape[1] == len(hist)):
     raise ValueError('hist (C, max_isi + 1), moments (C, 6), counts (N, C) '

@@ -145,6 +145,7 @@ from gan/utils/spike_metrics.py and csrc/oasis_ar1.c.  Results go to
 to the scalar log.
 """
 import argparse
+import collections
 import json
 import multiprocessing
 import os
@@ -159,6 +160,36 @@ from calciumgan_amd.gan.utils import (h5_helper, signals_metrics, spike_helper,
                                       spike_metrics, utils)
 
 NUM_BINS = 30  # compute_metrics.py:96
+# What an option that is absent from the namespace reads as (`option`; the
+# parser's help texts quote these).  --novelty_step falls back to the dataset's
+# stride, which `novelty_recording` hands to `option`.
+DEFAULTS = dict(
+    batch_trials=128,  # --device gpu: trials per launch
+    vp_q=1.0,          # --victor_purpura: cost per second of shift
+    max_lag=24,        # --temporal_metrics: one second of frames
+    state_k=5, state_bin=12,  # --state_metrics (500 ms of frames)
+    triplet_bin=12,    # --triplet_metrics (500 ms of frames)
+    max_isi=240)       # --interval_metrics (10 s of frames)
+
+
+def option(hparams, name, default=None):
+  """hparams.<name>, or the default of an option that was not given."""
+  return getattr(hparams, name, DEFAULTS.get(name, default))
+
+
+def kept(hparams, name, make):
+  """hparams.<name>, made on first use and kept across epochs: the validation
+  set and the recording are the same for every epoch."""
+  if getattr(hparams, name, None) is None:
+    setattr(hparams, name, make())
+  return getattr(hparams, name)
+
+
+def same_frames(filename, frames, recorded_frames):
+  """A file whose trials are not as long as the validation cache's is refused."""
+  if frames != recorded_frames:
+    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
+                     .format(filename, frames, recorded_frames))
 
 
 def kl_divergence(p, q):
@@ -272,7 +303,7 @@ def trial_victor_purpura(hparams, filename, trial):
   out = []
   for f in (hparams.validation_cache, filename):
     d = spike_metrics.victor_purpura_distance_frames(
-        _spikes(hparams, f, 'CW', trial=trial), q=getattr(hparams, 'vp_q', 1.0))
+        _spikes(hparams, f, 'CW', trial=trial), q=option(hparams, 'vp_q'))
     out.append(d[np.triu_indices(len(d), k=1)])
   assert out[0].shape == out[1].shape
   return tuple(out)
@@ -314,52 +345,57 @@ def _map(hparams, fn, args):
   return [fn(*a) for a in args]
 
 
-TEMPORAL_MAX_LAG = 24  # --max_lag: one second of frames
+def _trials(hparams, filename, name='spikes', count=None):
+  """The first `count` (num_samples) trials of dataset `name` of `filename` as
+  an NWC host array."""
+  trials = utils.set_array_format(
+      np.asarray(h5_helper.get(filename, name=name)), 'NWC', hparams)
+  return trials[:hparams.num_samples if count is None else count]
 
 
-def _trial_spikes(hparams, filename):
-  """The first num_samples trials of `filename` as an NWC host array."""
-  spikes = utils.set_array_format(
-      np.asarray(h5_helper.get(filename, name='spikes')), 'NWC', hparams)
-  return spikes[:hparams.num_samples]
+def _trial_signals(hparams, filename):
+  """The first num_samples trials of `signals` of `filename`, float32."""
+  return np.asarray(_trials(hparams, filename, 'signals'), dtype=np.float32)
+
+
+def _print_scores(hparams, scores, labels):
+  if hparams.verbose:
+    for name, label in labels:
+      print('\t{}: {:.04g}'.format(label, scores[name]))
+  return scores
+
+
+def _totals_report(hparams, filename, totals, kept_as, scores, labels):
+  """The skeleton of the reports that come from totals over the trials:
+  scores(recorded totals, generated totals, T) of `filename` against the
+  validation cache; totals(hparams, filename) -> (totals, T), the recorded
+  side's kept across epochs as hparams.<kept_as>."""
+  real = kept(hparams, kept_as,
+              lambda: totals(hparams, hparams.validation_cache))
+  fake = totals(hparams, filename)
+  same_frames(filename, fake[1], real[1])
+  return _print_scores(hparams, scores(real[0], fake[0], real[1]), labels)
 
 
 def temporal_totals_host(hparams, filename):
   """(spike_metrics.temporal_totals, T) of the trials of `filename`."""
-  spikes = _trial_spikes(hparams, filename)
+  spikes = _trials(hparams, filename)
   return spike_metrics.temporal_totals(
-      spikes, getattr(hparams, 'max_lag', TEMPORAL_MAX_LAG)), spikes.shape[1]
+      spikes, option(hparams, 'max_lag')), spikes.shape[1]
 
 
 def temporal_report(hparams, filename, totals):
   """--temporal_metrics: spike_metrics.temporal_scores of `filename` against
   the validation cache; totals(hparams, filename) -> ((ccg, hist, trials), T),
   the recorded side's kept across epochs."""
-  real = getattr(hparams, '_recorded_temporal_totals', None)
-  if real is None:  # the validation set is the same for every epoch
-    real = hparams._recorded_temporal_totals = totals(hparams,
-                                                      hparams.validation_cache)
-  fake = totals(hparams, filename)
-  if real[1] != fake[1]:
-    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
-                     .format(filename, fake[1], real[1]))
-  scores = spike_metrics.temporal_scores(real[0], fake[0], real[1])
-  if hparams.verbose:
-    for name, label in (('autocorrelogram_mae', 'autocorrelogram    MAE'),
-                        ('lag_covariance_mae', 'lag-1 covariance   MAE'),
-                        ('lag_covariance_correlation', 'lag-1 covariance     r'),
-                        ('cross_correlogram_mae', 'cross-correlogram  MAE'),
-                        ('population_count_js_bits', 'population count    JS')):
-      print('\t{}: {:.04g}'.format(label, scores[name]))
-  return scores
-
-
-def _trial_signals(hparams, filename):
-  """The first num_samples trials of `signals` of `filename` as a float32 NWC
-  host array."""
-  signals = utils.set_array_format(
-      np.asarray(h5_helper.get(filename, name='signals')), 'NWC', hparams)
-  return np.asarray(signals[:hparams.num_samples], dtype=np.float32)
+  return _totals_report(
+      hparams, filename, totals, '_recorded_temporal_totals',
+      spike_metrics.temporal_scores,
+      (('autocorrelogram_mae', 'autocorrelogram    MAE'),
+       ('lag_covariance_mae', 'lag-1 covariance   MAE'),
+       ('lag_covariance_correlation', 'lag-1 covariance     r'),
+       ('cross_correlogram_mae', 'cross-correlogram  MAE'),
+       ('population_count_js_bits', 'population count    JS')))
 
 
 def spectral_totals_host(hparams, filename):
@@ -372,21 +408,12 @@ def spectral_report(hparams, filename, totals):
   """--spectral_metrics: signals_metrics.spectral_scores of `filename` against
   the validation cache; totals(hparams, filename) -> ((totals, trials), T), the
   recorded side's kept across epochs."""
-  real = getattr(hparams, '_recorded_spectral_totals', None)
-  if real is None:  # the validation set is the same for every epoch
-    real = hparams._recorded_spectral_totals = totals(hparams,
-                                                      hparams.validation_cache)
-  fake = totals(hparams, filename)
-  if real[1] != fake[1]:
-    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
-                     .format(filename, fake[1], real[1]))
-  scores = signals_metrics.spectral_scores(real[0], fake[0], real[1])
-  if hparams.verbose:
-    for name, label in (('log_spectral_distance_db', 'log-spectral dist.  dB'),
-                        ('log_spectral_rmse_db', 'log-spectral RMSE   dB'),
-                        ('total_power_ratio_db', 'total power ratio   dB')):
-      print('\t{}: {:.04g}'.format(label, scores[name]))
-  return scores
+  return _totals_report(
+      hparams, filename, totals, '_recorded_spectral_totals',
+      signals_metrics.spectral_scores,
+      (('log_spectral_distance_db', 'log-spectral dist.  dB'),
+       ('log_spectral_rmse_db', 'log-spectral RMSE   dB'),
+       ('total_power_ratio_db', 'total power ratio   dB')))
 
 
 def novelty_recording(hparams):
@@ -394,27 +421,27 @@ def novelty_recording(hparams):
   run was trained on, in raw units -- the units of the generated files
   (utils.save_fake_signals denormalises, and for an FFT recording the files
   hold traces).  Kept across epochs."""
-  kept = getattr(hparams, '_novelty_recording', None)
-  if kept is not None:
-    return kept
-  from calciumgan_amd.data import recording
-  input_dir = getattr(hparams, 'input_dir', None)
-  info = None
-  if input_dir and os.path.exists(os.path.join(input_dir, 'info.pkl')):
-    with open(os.path.join(input_dir, 'info.pkl'), 'rb') as f:
-      info = pickle.load(f)
-  if not (info and info.get('recording') and
-          os.path.exists(os.path.join(input_dir, recording.FILENAME))):
-    raise ValueError(
-        '--novelty_metrics needs the run\'s input_dir to be a recording '
-        'directory (info[\'recording\'], {}); {!r} is not one'.format(
-            recording.FILENAME, input_dir))
-  raw = np.ascontiguousarray(recording.load(input_dir)['raw'], dtype=np.float32)
-  step = int(getattr(hparams, 'novelty_step', info['stride']))
-  if step < 1:
-    raise ValueError('--novelty_step must be at least 1')
-  hparams._novelty_recording = (raw, int(info['sequence_length']), step)
-  return hparams._novelty_recording
+  def load():
+    from calciumgan_amd.data import recording
+    input_dir = getattr(hparams, 'input_dir', None)
+    info = None
+    if input_dir and os.path.exists(os.path.join(input_dir, 'info.pkl')):
+      with open(os.path.join(input_dir, 'info.pkl'), 'rb') as f:
+        info = pickle.load(f)
+    if not (info and info.get('recording') and
+            os.path.exists(os.path.join(input_dir, recording.FILENAME))):
+      raise ValueError(
+          '--novelty_metrics needs the run\'s input_dir to be a recording '
+          'directory (info[\'recording\'], {}); {!r} is not one'.format(
+              recording.FILENAME, input_dir))
+    raw = np.ascontiguousarray(recording.load(input_dir)['raw'],
+                               dtype=np.float32)
+    step = int(option(hparams, 'novelty_step', info['stride']))
+    if step < 1:
+      raise ValueError('--novelty_step must be at least 1')
+    return raw, int(info['sequence_length']), step
+
+  return kept(hparams, '_novelty_recording', load)
 
 
 def novelty_nearest_host(hparams, queries, exclude, exclude_len):
@@ -439,198 +466,152 @@ def novelty_report(hparams, filename, nearest):
                      'stretches of {} of {}'.format(filename, frames, neurons,
                                                     L, C))
   fake = _trial_signals(hparams, filename)
-  real = getattr(hparams, '_recorded_novelty', None)
-  if real is None:  # the recording is the same for every epoch
+
+  def recorded():
     starts = signals_metrics.recorded_starts(S, hparams.num_samples, step)
     windows = np.lib.stride_tricks.sliding_window_view(raw, L, axis=0)
     queries = windows[starts].transpose(0, 2, 1)   # (n, L, C) views of raw
-    real = hparams._recorded_novelty = tuple(
-        signals_metrics._host(x) for x in nearest(hparams, queries, starts, L))
+    return tuple(signals_metrics._host(x)
+                 for x in nearest(hparams, queries, starts, L))
+
+  real = kept(hparams, '_recorded_novelty', recorded)
   got = tuple(signals_metrics._host(x) for x in nearest(hparams, fake, None, 0))
-  scores = signals_metrics.novelty_scores(real, got, L, C, step, offsets=S)
+  return _print_scores(
+      hparams, signals_metrics.novelty_scores(real, got, L, C, step, offsets=S),
+      (('nearest_rms_ratio', 'nearest rms    gen / rec'),
+       ('copied_fraction', 'copied fraction        '),
+       ('distinct_stretches', 'distinct stretches     ')))
+
+
+def _floor_report(hparams, filename, kept_as, sets, scores, line, names,
+                  settings, prepare=lambda ref: (), check_recorded=None,
+                  check_generated=None):
+  """The skeleton of the reports that read the generated trials beside a floor.
+  With ref = sets(hparams, the recorded trials 0, 2, 4, ...), `generated` is
+  scores(ref, sets(hparams, the generated trials 1, 3, 5, ...), *prepare(ref))
+  and `floor` the same of the recorded trials 1, 3, 5, ...: what two draws of
+  the data score at these sizes.  The recorded side (ref, *prepare(ref), floor,
+  frames) is kept across epochs as hparams.<kept_as>.  check_recorded and
+  check_generated(trials) are the family's own refusals; `line` prints name,
+  generated[key], floor[key] of `names`; `settings` joins the returned dict."""
+  fake = _trials(hparams, filename)
+
+  def recorded():
+    spikes = _trials(hparams, hparams.validation_cache)
+    if check_recorded is not None:
+      check_recorded(spikes)
+    ref = sets(hparams, spikes[0::2])
+    more = prepare(ref)
+    floor = scores(ref, sets(hparams, spikes[1::2]), *more)
+    return (ref,) + more + (floor, spikes.shape[1])
+
+  ref, *more, floor, frames = kept(hparams, kept_as, recorded)
+  same_frames(filename, fake.shape[1], frames)
+  if check_generated is not None:
+    check_generated(fake)
+  generated = scores(ref, sets(hparams, fake[1::2]), *more)
   if hparams.verbose:
-    for name, label in (('nearest_rms_ratio', 'nearest rms    gen / rec'),
-                        ('copied_fraction', 'copied fraction        '),
-                        ('distinct_stretches', 'distinct stretches     ')):
-      print('\t{}: {:.04g}'.format(label, scores[name]))
-  return scores
-
-
-STATE_K, STATE_BIN = 5, 12  # --state_k, --state_bin (500 ms of frames)
+    for name, key in names:
+      print(line.format(name, generated[key], floor[key]))
+  return dict(generated=generated, floor=floor, **settings)
 
 
 def state_sets_host(hparams, spikes):
   """The states of an NWC host array of trials as spike_metrics.state_neighbours
   takes them."""
-  return spike_metrics.population_states(
-      spikes, getattr(hparams, 'state_bin', STATE_BIN))
+  return spike_metrics.population_states(spikes, option(hparams, 'state_bin'))
 
 
 def state_report(hparams, filename, states, neighbours):
-  """--state_metrics: spike_metrics.state_scores of the population states of the
-  generated trials 1, 3, 5, ... against those of the recorded trials 0, 2, 4,
-  ... (`generated`), beside the same scores of the recorded trials 1, 3, 5, ...
-  against them (`floor`: what two draws of the data score at these sizes).
-  states(hparams, trials) -> a set, neighbours the query on such sets; the
-  recorded side (the reference set, its radii and the floor) is kept across
-  epochs."""
-  k = int(getattr(hparams, 'state_k', STATE_K))
-  fake = _trial_spikes(hparams, filename)
-  real = getattr(hparams, '_recorded_states', None)
-  if real is None:  # the validation set is the same for every epoch
-    spikes = _trial_spikes(hparams, hparams.validation_cache)
-    ref = states(hparams, spikes[0::2])
-    rad_ref = spike_metrics.state_radii(ref, k, neighbours)
-    floor = spike_metrics.state_scores(ref, states(hparams, spikes[1::2]), k,
-                                       neighbours, rad_ref=rad_ref)
-    real = hparams._recorded_states = (ref, rad_ref, floor, spikes.shape[1])
-  ref, rad_ref, floor, frames = real
-  if fake.shape[1] != frames:
-    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
-                     .format(filename, fake.shape[1], frames))
-  generated = spike_metrics.state_scores(ref, states(hparams, fake[1::2]), k,
-                                         neighbours, rad_ref=rad_ref)
-  if hparams.verbose:
-    for name in ('precision', 'recall', 'coverage'):
-      print('\tstate {:<9}  gen | floor: {:.04f} | {:.04f}'.format(
-          name, generated[name], floor[name]))
-  return dict(generated=generated, floor=floor, k=k,
-              bin_frames=int(getattr(hparams, 'state_bin', STATE_BIN)))
-
-
-TRIPLET_BIN = 12  # --triplet_bin (500 ms of frames)
+  """--state_metrics: `_floor_report` of spike_metrics.state_scores of the
+  population states.  states(hparams, trials) -> a set, neighbours the query on
+  such sets; the radii of the reference set are kept with it."""
+  k = int(option(hparams, 'state_k'))
+  return _floor_report(
+      hparams, filename, '_recorded_states', states,
+      lambda ref, other, rad_ref: spike_metrics.state_scores(
+          ref, other, k, neighbours, rad_ref=rad_ref),
+      '\tstate {:<9}  gen | floor: {:.04f} | {:.04f}',
+      [(name, name) for name in ('precision', 'recall', 'coverage')],
+      dict(k=k, bin_frames=int(option(hparams, 'state_bin'))),
+      prepare=lambda ref: (spike_metrics.state_radii(ref, k, neighbours),))
 
 
 def triplet_sets_host(hparams, spikes):
   """(singles, pairs, triplets, S) of an NWC host array of trials: the side
   spike_metrics.triplet_scores takes."""
-  states = spike_metrics.binary_states(
-      spikes, getattr(hparams, 'triplet_bin', TRIPLET_BIN))
+  states = spike_metrics.binary_states(spikes, option(hparams, 'triplet_bin'))
   return spike_metrics.triplet_counts(states) + (len(states),)
 
 
 def triplet_report(hparams, filename, sets):
-  """--triplet_metrics: spike_metrics.triplet_scores of the binary states of the
-  generated trials 1, 3, 5, ... against those of the recorded trials 0, 2, 4,
-  ... (`generated`), beside the same scores of the recorded trials 1, 3, 5, ...
-  against them (`floor`: what two draws of the data score at these sizes).
-  sets(hparams, trials) -> a side (singles, pairs, triplets, S), host integers;
-  the recorded side and the floor are kept across epochs."""
-  bin = int(getattr(hparams, 'triplet_bin', TRIPLET_BIN))
-  fake = _trial_spikes(hparams, filename)
-  real = getattr(hparams, '_recorded_triplets', None)
-  if real is None:  # the validation set is the same for every epoch
-    spikes = _trial_spikes(hparams, hparams.validation_cache)
+  """--triplet_metrics: `_floor_report` of spike_metrics.triplet_scores of the
+  binary states.  sets(hparams, trials) -> a side (singles, pairs, triplets,
+  S), host integers."""
+  bin = int(option(hparams, 'triplet_bin'))
+
+  def check(spikes):
     if spikes.shape[2] < 3:
       raise ValueError('--triplet_metrics needs three neurons, not {}'.format(
           spikes.shape[2]))
     if spikes.shape[1] < bin:
       raise ValueError('trials of {} frames hold no bin of {}'.format(
           spikes.shape[1], bin))
-    ref = sets(hparams, spikes[0::2])
-    floor = spike_metrics.triplet_scores(ref, sets(hparams, spikes[1::2]))
-    real = hparams._recorded_triplets = (ref, floor, spikes.shape[1])
-  ref, floor, frames = real
-  if fake.shape[1] != frames:
-    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
-                     .format(filename, fake.shape[1], frames))
-  generated = spike_metrics.triplet_scores(ref, sets(hparams, fake[1::2]))
-  if hparams.verbose:
-    for name in ('correlation', 'mae'):
-      key = 'triplet_cumulant_' + name
-      print('\ttriplet cumulant {:<11}  gen | floor: {:.06f} | {:.06f}'.format(
-          name, generated[key], floor[key]))
-  return dict(generated=generated, floor=floor, bin_frames=bin)
 
-
-MAX_ISI = 240  # --max_isi (10 s of frames)
+  return _floor_report(
+      hparams, filename, '_recorded_triplets', sets,
+      spike_metrics.triplet_scores,
+      '\ttriplet cumulant {:<11}  gen | floor: {:.06f} | {:.06f}',
+      [(name, 'triplet_cumulant_' + name) for name in ('correlation', 'mae')],
+      dict(bin_frames=bin), check_recorded=check)
 
 
 def interval_sets_host(hparams, spikes):
   """(hist, moments, counts) of an NWC host array of trials: the side
   spike_metrics.interval_scores takes."""
-  return spike_metrics.interval_counts(
-      spikes, getattr(hparams, 'max_isi', MAX_ISI))
+  return spike_metrics.interval_counts(spikes, option(hparams, 'max_isi'))
 
 
 def interval_report(hparams, filename, sets):
-  """--interval_metrics: spike_metrics.interval_scores of the generated trials
-  1, 3, 5, ... against the recorded trials 0, 2, 4, ... (`generated`), beside
-  the same scores of the recorded trials 1, 3, 5, ... against them (`floor`:
-  what two draws of the data score at these sizes).  sets(hparams, trials) -> a
-  side (hist, moments, counts), host integers; the recorded side and the floor
-  are kept across epochs."""
-  max_isi = int(getattr(hparams, 'max_isi', MAX_ISI))
-  fake = _trial_spikes(hparams, filename)
-  real = getattr(hparams, '_recorded_intervals', None)
-  if real is None:  # the validation set is the same for every epoch
-    spikes = _trial_spikes(hparams, hparams.validation_cache)
-    if len(spikes[1::2]) < 2:
-      raise ValueError('--interval_metrics needs two trials a side, the '
-                       'validation cache holds {} in all'.format(len(spikes)))
-    ref = sets(hparams, spikes[0::2])
-    floor = spike_metrics.interval_scores(ref, sets(hparams, spikes[1::2]))
-    real = hparams._recorded_intervals = (ref, floor, spikes.shape[1])
-  ref, floor, frames = real
-  if fake.shape[1] != frames:
-    raise ValueError('{} holds trials of {} frames, the validation cache of {}'
-                     .format(filename, fake.shape[1], frames))
-  if len(fake[1::2]) < 2:
-    raise ValueError('--interval_metrics needs two trials a side, {} holds {} '
-                     'in all'.format(filename, len(fake)))
-  generated = spike_metrics.interval_scores(ref, sets(hparams, fake[1::2]))
-  if hparams.verbose:
-    for key in ('cv_mae', 'isi_js_bits', 'fano_mae'):
-      print('\tinterval {:<12}  gen | floor: {:.06f} | {:.06f}'.format(
-          key, generated[key], floor[key]))
-  return dict(generated=generated, floor=floor, max_isi=max_isi)
+  """--interval_metrics: `_floor_report` of spike_metrics.interval_scores.
+  sets(hparams, trials) -> a side (hist, moments, counts), host integers."""
+  def check(trials, holder='the validation cache'):
+    if len(trials[1::2]) < 2:
+      raise ValueError('--interval_metrics needs two trials a side, {} holds {} '
+                       'in all'.format(holder, len(trials)))
+
+  return _floor_report(
+      hparams, filename, '_recorded_intervals', sets,
+      spike_metrics.interval_scores,
+      '\tinterval {:<12}  gen | floor: {:.06f} | {:.06f}',
+      [(name, name) for name in ('cv_mae', 'isi_js_bits', 'fano_mae')],
+      dict(max_isi=int(option(hparams, 'max_isi'))), check_recorded=check,
+      check_generated=lambda fake: check(fake, filename))
 
 
-def compute_epoch_spike_metrics(hparams, filename, epoch):
-  """:483-497 without plot_signals / raster_plots: dict of the statistics."""
-  if not h5_helper.contains(filename, 'spikes'):
-    deconvolve_from_file(hparams, filename)
-  out = {}
-  pairs = _map(hparams, firing_rate, [(hparams, filename, n, hparams.num_samples)
-                                      for n in range(hparams.num_neurons)])
-  kl = pairs_kl_divergence(pairs)
-  out['firing_rate_kl'] = dict(
-      mean=float(np.mean(kl)),
-      neurons={int(n): float(kl[n]) for n in hparams.neurons})
-  if hparams.verbose:
-    print('\tfiring rate        KL mean: {:.04f}'.format(np.mean(kl)))
+def host_kl(hparams, filename):
+  """name -> callable giving the float32 KL per pair behind each figure of the
+  host report (`device_kl` is its counterpart): per neuron the firing rates
+  over the trials, per trial the upper triangles of the matrices between its
+  neurons, each through a pool of its own."""
   trials = [(hparams, filename, i) for i in range(hparams.num_samples)]
-  kl = pairs_kl_divergence(_map(hparams, correlation_coefficient, trials))
-  out['correlation_kl'] = dict(mean=float(np.mean(kl)))
-  if hparams.verbose:
-    print('\tcorrelation        KL mean: {:.04f}'.format(np.mean(kl)))
+  figures = dict(firing_rate=lambda: pairs_kl_divergence(_map(
+      hparams, firing_rate, [(hparams, filename, n, hparams.num_samples)
+                             for n in range(hparams.num_neurons)])))
+  per_trial = dict(correlation=correlation_coefficient,
+                   van_rossum=trial_van_rossum)
+  if getattr(hparams, 'victor_purpura', False):
+    per_trial['victor_purpura'] = trial_victor_purpura
+  for name, fn in per_trial.items():
+    figures[name] = lambda fn=fn: pairs_kl_divergence(_map(hparams, fn, trials))
+  return figures
+
+
+def heatmap_minima_host(hparams, filename):
+  """The least distance of the heat map of every chosen neuron."""
   heat = _map(hparams, neuron_van_rossum,
               [(hparams, filename, n, 45) for n in hparams.neurons])
-  out['van_rossum_heatmap_min'] = {
-      int(n): float(np.nanmin(h['heatmap'])) for n, h in zip(hparams.neurons, heat)}
-  kl = pairs_kl_divergence(_map(hparams, trial_van_rossum, trials))
-  out['van_rossum_kl'] = dict(mean=float(np.mean(kl)))
-  if hparams.verbose:
-    print('\tvan Rossum         KL mean: {:.04f}'.format(np.mean(kl)))
-  if getattr(hparams, 'victor_purpura', False):
-    kl = pairs_kl_divergence(_map(hparams, trial_victor_purpura, trials))
-    out['victor_purpura_kl'] = dict(mean=float(np.mean(kl)))
-    if hparams.verbose:
-      print('\tVictor-Purpura     KL mean: {:.04f}'.format(np.mean(kl)))
-  if getattr(hparams, 'temporal_metrics', False):
-    out['temporal'] = temporal_report(hparams, filename, temporal_totals_host)
-  if getattr(hparams, 'spectral_metrics', False):
-    out['spectral'] = spectral_report(hparams, filename, spectral_totals_host)
-  if getattr(hparams, 'novelty_metrics', False):
-    out['novelty'] = novelty_report(hparams, filename, novelty_nearest_host)
-  if getattr(hparams, 'state_metrics', False):
-    out['states'] = state_report(hparams, filename, state_sets_host,
-                                 spike_metrics.state_neighbours)
-  if getattr(hparams, 'triplet_metrics', False):
-    out['triplets'] = triplet_report(hparams, filename, triplet_sets_host)
-  if getattr(hparams, 'interval_metrics', False):
-    out['intervals'] = interval_report(hparams, filename, interval_sets_host)
-  return out
+  return [np.nanmin(h['heatmap']) for h in heat]
 
 
 # -- --device gpu ---------------------------------------------------------------
@@ -642,7 +623,7 @@ def _device():
 def _batches(hparams, array):
   """float32 device tensors of `batch_trials` trials of an NWC host array."""
   import torch
-  step = max(int(getattr(hparams, 'batch_trials', 128)), 1)
+  step = max(int(option(hparams, 'batch_trials')), 1)
   for i in range(0, len(array), step):
     yield torch.from_numpy(
         np.ascontiguousarray(array[i:i + step], dtype=np.float32)).to(_device())
@@ -674,16 +655,14 @@ def trial_statistics_device(hparams, filename, matrices_on_device=False):
   distances (cg_victor_purpura) as well.  matrices_on_device: the (n, C, C)
   matrices stay device tensors (the firing rates come to the host either way)."""
   import torch
-  spikes = utils.set_array_format(
-      np.asarray(h5_helper.get(filename, name='spikes')), 'NWC', hparams)
   rates, corr, dist, vp = [], [], [], []
-  for batch in _batches(hparams, spikes[:hparams.num_samples]):
+  for batch in _batches(hparams, _trials(hparams, filename)):
     rates.append(spike_metrics.batch_statistics_device(batch)[0].cpu().numpy())
     corr.append(spike_metrics.correlation_coefficients_device(batch))
     dist.append(spike_metrics.van_rossum_distance_device(batch))
     if getattr(hparams, 'victor_purpura', False):
       vp.append(spike_metrics.victor_purpura_distance_device(
-          batch, q=getattr(hparams, 'vp_q', 1.0)))
+          batch, q=option(hparams, 'vp_q')))
     if not matrices_on_device:
       for per_batch in (corr, dist, vp):
         if per_batch:
@@ -704,10 +683,9 @@ def neuron_van_rossum_blocks_device(hparams, filename, neurons, num_trials=45):
   import torch
   sides = []
   for f in (hparams.validation_cache, filename):
-    spikes = utils.set_array_format(
-        np.asarray(h5_helper.get(f, name='spikes')), 'NWC', hparams)
     # (trials, T, neurons) -> (neurons, T, trials)
-    sides.append(spikes[:num_trials][:, :, list(neurons)].transpose(2, 1, 0))
+    sides.append(_trials(hparams, f, count=num_trials)[:, :, list(neurons)]
+                 .transpose(2, 1, 0))
   n_real, n_fake = sides[0].shape[2], sides[1].shape[2]
   batch = torch.from_numpy(np.ascontiguousarray(
       np.concatenate(sides, axis=2), dtype=np.float32)).to(_device())
@@ -719,10 +697,8 @@ def device_pairs(hparams, filename):
   """The (recorded, synthetic) samples behind the three KL figures, from the
   device statistics: per neuron the firing rates over the trials, per trial the
   upper triangles of the correlation and van Rossum matrices."""
-  real = getattr(hparams, '_recorded_statistics', None)
-  if real is None:  # the validation set is the same for every epoch
-    real = hparams._recorded_statistics = trial_statistics_device(
-        hparams, hparams.validation_cache)
+  real = kept(hparams, '_recorded_statistics', lambda: trial_statistics_device(
+      hparams, hparams.validation_cache))
   fake = trial_statistics_device(hparams, filename)
   n = hparams.num_neurons
   iu = np.triu_indices(n, k=1)
@@ -780,10 +756,9 @@ def device_kl(hparams, filename):
   device report.  The matrices of both files stay on the device (the recorded
   side cached across epochs) and are cut there; the firing rates (one pair per
   neuron of float32 values) are cut on the host."""
-  real = getattr(hparams, '_recorded_statistics_device', None)
-  if real is None:  # the validation set is the same for every epoch
-    real = hparams._recorded_statistics_device = trial_statistics_device(
-        hparams, hparams.validation_cache, matrices_on_device=True)
+  real = kept(hparams, '_recorded_statistics_device',
+              lambda: trial_statistics_device(
+                  hparams, hparams.validation_cache, matrices_on_device=True))
   fake = trial_statistics_device(hparams, filename, matrices_on_device=True)
   hparams._kl_host_fallbacks = getattr(hparams, '_kl_host_fallbacks', 0)
   n = hparams.num_neurons
@@ -796,12 +771,19 @@ def device_kl(hparams, filename):
   return figures
 
 
+def heatmap_minima_device(hparams, filename):
+  """`heatmap_minima_host` from the blocks of one launch; `sort_heatmap` on the
+  host."""
+  blocks = neuron_van_rossum_blocks_device(hparams, filename, hparams.neurons, 45)
+  return [np.nanmin(sort_heatmap(b)[0]) for b in blocks]
+
+
 def temporal_totals_device(hparams, filename):
   """`temporal_totals_host` through cg_spike_ccg and cg_spike_population_hist, a
   batch of trials at a time; the int64 totals summed on the device and brought
   to the host once."""
-  spikes = _trial_spikes(hparams, filename)
-  max_lag = getattr(hparams, 'max_lag', TEMPORAL_MAX_LAG)
+  spikes = _trials(hparams, filename)
+  max_lag = option(hparams, 'max_lag')
   ccg = hist = None
   for batch in _batches(hparams, spikes):
     c, h, _ = spike_metrics.temporal_totals_device(batch, max_lag)
@@ -827,15 +809,13 @@ def novelty_nearest_device(hparams, queries, exclude, exclude_len):
   joined on the device and brought to the host once."""
   import torch
   raw, _, step = novelty_recording(hparams)
-  dev_raw = getattr(hparams, '_novelty_recording_device', None)
-  if dev_raw is None:
-    dev_raw = hparams._novelty_recording_device = torch.from_numpy(raw).to(
-        _device())
-  size = max(int(getattr(hparams, 'batch_trials', 128)), 1)
+  dev_raw = kept(hparams, '_novelty_recording_device',
+                 lambda: torch.from_numpy(raw).to(_device()))
   nearest, index = [], []
-  for i, batch in enumerate(_batches(hparams, queries)):
+  for batch in _batches(hparams, queries):
+    done = sum(len(n) for n in nearest)
     part = None if exclude is None else np.asarray(
-        exclude[i * size:(i + 1) * size], dtype=np.int32)
+        exclude[done:done + len(batch)], dtype=np.int32)
     n, at = signals_metrics.nearest_stretch_totals_device(
         batch, dev_raw, step, part, exclude_len)
     nearest.append(n)
@@ -847,20 +827,27 @@ def state_sets_device(hparams, spikes):
   """`state_sets_host` through cg_population_states, a batch of trials at a
   time; the states stay on the device."""
   return spike_metrics.DeviceStates.cat(
-      spike_metrics.population_states_device(
-          batch, getattr(hparams, 'state_bin', STATE_BIN))
+      spike_metrics.population_states_device(batch, option(hparams, 'state_bin'))
       for batch in _batches(hparams, spikes))
+
+
+def _words_device(hparams, spikes, bin):
+  """cg_binary_words of an NWC host array, a batch of trials at a time."""
+  return spike_metrics.DeviceWords.cat(
+      spike_metrics.binary_words_device(batch, bin)
+      for batch in _batches(hparams, spikes))
+
+
+def _host_integers(tensors):
+  return tuple(x.cpu().numpy().astype(np.int64) for x in tensors)
 
 
 def triplet_sets_device(hparams, spikes):
   """`triplet_sets_host` through cg_binary_words, a batch of trials at a time,
   and one cg_triplet_counts of the side; the integers come to the host."""
-  words = spike_metrics.DeviceWords.cat(
-      spike_metrics.binary_words_device(
-          batch, getattr(hparams, 'triplet_bin', TRIPLET_BIN))
-      for batch in _batches(hparams, spikes))
-  counts, S = spike_metrics.triplet_counts_device(words)
-  return tuple(x.cpu().numpy().astype(np.int64) for x in counts) + (S,)
+  counts, S = spike_metrics.triplet_counts_device(
+      _words_device(hparams, spikes, option(hparams, 'triplet_bin')))
+  return _host_integers(counts) + (S,)
 
 
 def interval_sets_device(hparams, spikes):
@@ -873,63 +860,72 @@ def interval_sets_device(hparams, spikes):
                      'cg_binary_words, which takes 3 .. {} neurons, not {} '
                      '(--device cpu takes any)'.format(
                          spike_metrics.TRIPLET_MAX_NEURONS, C))
-  words = spike_metrics.DeviceWords.cat(
-      spike_metrics.binary_words_device(batch, 1)
-      for batch in _batches(hparams, spikes))
-  return tuple(x.cpu().numpy().astype(np.int64)
-               for x in spike_metrics.interval_counts_device(
-                   words, getattr(hparams, 'max_isi', MAX_ISI)))
+  return _host_integers(spike_metrics.interval_counts_device(
+      _words_device(hparams, spikes, 1), option(hparams, 'max_isi')))
 
 
-def compute_epoch_spike_metrics_device(hparams, filename, epoch):
-  """`compute_epoch_spike_metrics` with the statistics from the device; the
-  histograms behind the KL from cg_pair_histogram (`device_kl`) unless
-  CALCIUMGAN_DEVICE_KL=0, the KL's arithmetic and `sort_heatmap` on the host."""
+# -- the report of one epoch --------------------------------------------------------
+Report = collections.namedtuple('Report', 'key flag report host device')
+# The optional reports in the order of their keys in spike_metrics.json: with
+# hparams.<flag>, out[key] = report(hparams, filename, *back ends of the device).
+# A new family is a row here, its own functions and its parser lines.
+REPORTS = (
+    Report('temporal', 'temporal_metrics', temporal_report,
+           (temporal_totals_host,), (temporal_totals_device,)),
+    Report('spectral', 'spectral_metrics', spectral_report,
+           (spectral_totals_host,), (spectral_totals_device,)),
+    Report('novelty', 'novelty_metrics', novelty_report,
+           (novelty_nearest_host,), (novelty_nearest_device,)),
+    Report('states', 'state_metrics', state_report,
+           (state_sets_host, spike_metrics.state_neighbours),
+           (state_sets_device, spike_metrics.state_neighbours_device)),
+    Report('triplets', 'triplet_metrics', triplet_report,
+           (triplet_sets_host,), (triplet_sets_device,)),
+    Report('intervals', 'interval_metrics', interval_report,
+           (interval_sets_host,), (interval_sets_device,)),
+)
+
+
+def compute_epoch_spike_metrics(hparams, filename, epoch, device=False):
+  """:483-497 without plot_signals / raster_plots: dict of the statistics.
+  device: the statistics from the device; the histograms behind the KL from
+  cg_pair_histogram (`device_kl`) unless CALCIUMGAN_DEVICE_KL=0, the KL's
+  arithmetic and `sort_heatmap` on the host."""
   if not h5_helper.contains(filename, 'spikes'):
-    deconvolve_from_file_device(hparams, filename)
-  if device_kl_enabled():
+    (deconvolve_from_file_device if device else deconvolve_from_file)(
+        hparams, filename)
+  if not device:
+    figures = host_kl(hparams, filename)
+  elif device_kl_enabled():
     figures = device_kl(hparams, filename)
   else:
     pairs = device_pairs(hparams, filename)
     figures = {name: (lambda name=name: pairs_kl_divergence(pairs[name]))
                for name in pairs}
   out = {}
-  kl = figures['firing_rate']()
-  out['firing_rate_kl'] = dict(
-      mean=float(np.mean(kl)),
-      neurons={int(n): float(kl[n]) for n in hparams.neurons})
-  if hparams.verbose:
-    print('\tfiring rate        KL mean: {:.04f}'.format(np.mean(kl)))
-  kl = figures['correlation']()
-  out['correlation_kl'] = dict(mean=float(np.mean(kl)))
-  if hparams.verbose:
-    print('\tcorrelation        KL mean: {:.04f}'.format(np.mean(kl)))
-  blocks = neuron_van_rossum_blocks_device(hparams, filename, hparams.neurons, 45)
-  out['van_rossum_heatmap_min'] = {
-      int(n): float(np.nanmin(sort_heatmap(b)[0]))
-      for n, b in zip(hparams.neurons, blocks)}
-  kl = figures['van_rossum']()
-  out['van_rossum_kl'] = dict(mean=float(np.mean(kl)))
-  if hparams.verbose:
-    print('\tvan Rossum         KL mean: {:.04f}'.format(np.mean(kl)))
-  if 'victor_purpura' in figures:
-    kl = figures['victor_purpura']()
-    out['victor_purpura_kl'] = dict(mean=float(np.mean(kl)))
+
+  def kl_figure(name, label):
+    kl = figures[name]()
+    out[name + '_kl'] = dict(mean=float(np.mean(kl)))
     if hparams.verbose:
-      print('\tVictor-Purpura     KL mean: {:.04f}'.format(np.mean(kl)))
-  if getattr(hparams, 'temporal_metrics', False):
-    out['temporal'] = temporal_report(hparams, filename, temporal_totals_device)
-  if getattr(hparams, 'spectral_metrics', False):
-    out['spectral'] = spectral_report(hparams, filename, spectral_totals_device)
-  if getattr(hparams, 'novelty_metrics', False):
-    out['novelty'] = novelty_report(hparams, filename, novelty_nearest_device)
-  if getattr(hparams, 'state_metrics', False):
-    out['states'] = state_report(hparams, filename, state_sets_device,
-                                 spike_metrics.state_neighbours_device)
-  if getattr(hparams, 'triplet_metrics', False):
-    out['triplets'] = triplet_report(hparams, filename, triplet_sets_device)
-  if getattr(hparams, 'interval_metrics', False):
-    out['intervals'] = interval_report(hparams, filename, interval_sets_device)
+      print('\t{:<18} KL mean: {:.04f}'.format(label, np.mean(kl)))
+    return kl
+
+  kl = kl_figure('firing_rate', 'firing rate')
+  out['firing_rate_kl']['neurons'] = {
+      int(n): float(kl[n]) for n in hparams.neurons}
+  kl_figure('correlation', 'correlation')
+  minima = (heatmap_minima_device if device else heatmap_minima_host)(
+      hparams, filename)
+  out['van_rossum_heatmap_min'] = {
+      int(n): float(m) for n, m in zip(hparams.neurons, minima)}
+  kl_figure('van_rossum', 'van Rossum')
+  if 'victor_purpura' in figures:
+    kl_figure('victor_purpura', 'Victor-Purpura')
+  for row in REPORTS:
+    if getattr(hparams, row.flag, False):
+      out[row.key] = row.report(hparams, filename,
+                                *(row.device if device else row.host))
   return out
 
 
@@ -961,11 +957,9 @@ def main(hparams):
     start = time()
     if hparams.verbose:
       print('\nCompute metrics for {}'.format(info[epoch]['filename']))
-    compute = (compute_epoch_spike_metrics_device
-               if getattr(hparams, 'device', 'cpu') == 'gpu' else
-               compute_epoch_spike_metrics)
-    report[int(epoch)] = compute(hparams, filename=info[epoch]['filename'],
-                                 epoch=epoch)
+    report[int(epoch)] = compute_epoch_spike_metrics(
+        hparams, filename=info[epoch]['filename'], epoch=epoch,
+        device=getattr(hparams, 'device', 'cpu') == 'gpu')
     report[int(epoch)]['elapse'] = time() - start
     with open(os.path.join(hparams.output_dir, 'scalars.jsonl'), 'a') as f:
       f.write(json.dumps({'tag': 'elapse/spike_metrics',
@@ -990,75 +984,61 @@ def build_parser():
   parser.add_argument('--seed', default=12, type=int)
   parser.add_argument('--device', default='cpu', choices=['cpu', 'gpu'],
                       help='gpu: deconvolution and statistics on the device')
-  parser.add_argument('--batch_trials', default=128, type=int,
-                      help='--device gpu: trials per launch')
-  # (absent from the namespace unless given, as main.py --spike_metrics: read
-  # them with getattr(hparams, 'victor_purpura', False) / (..., 'vp_q', 1.0))
-  parser.add_argument('--victor_purpura', action='store_true',
-                      default=argparse.SUPPRESS,
-                      help='also report victor_purpura_kl, the KL of the '
-                      'Victor-Purpura distances between the neurons of a trial')
-  parser.add_argument('--vp_q', type=float, default=argparse.SUPPRESS,
-                      help='--victor_purpura: cost per second of shifting a '
-                      'spike (default 1.0)')
-  # (absent unless given, like --victor_purpura)
-  parser.add_argument('--temporal_metrics', action='store_true',
-                      default=argparse.SUPPRESS,
-                      help='also report `temporal`: autocorrelogram, lagged '
-                      'covariance, cross-correlogram and population-count '
-                      'figures of the generated against the recorded trials')
-  parser.add_argument('--max_lag', type=int, default=argparse.SUPPRESS,
-                      help='--temporal_metrics: largest lag in frames '
-                      '(default 24, at most 256)')
-  # (absent unless given, like --victor_purpura)
-  parser.add_argument('--spectral_metrics', action='store_true',
-                      default=argparse.SUPPRESS,
-                      help='also report `spectral`: power-spectrum figures of '
-                      'the generated against the recorded calcium traces')
-  # (absent unless given, like --victor_purpura)
-  parser.add_argument('--novelty_metrics', action='store_true',
-                      default=argparse.SUPPRESS,
-                      help='also report `novelty`: the distance from every '
-                      'generated trial to the nearest stretch of the recording '
-                      'the run was trained on (a recording directory), against '
-                      'the recording\'s distance to itself')
-  parser.add_argument('--novelty_step', type=int, default=argparse.SUPPRESS,
-                      help='--novelty_metrics: rows between two stretches '
-                      '(default: the stride of the dataset)')
-  # (absent unless given, like --victor_purpura)
-  parser.add_argument('--state_metrics', action='store_true',
-                      default=argparse.SUPPRESS,
-                      help='also report `states`: precision, recall and '
-                      'coverage of the generated population states against the '
-                      'recorded ones, beside the floor two halves of the '
-                      'recorded trials score')
-  parser.add_argument('--state_k', type=int, default=argparse.SUPPRESS,
-                      help='--state_metrics: the ball of a state reaches to its '
-                      'k-th nearest neighbour (default 5, at most 8)')
-  parser.add_argument('--state_bin', type=int, default=argparse.SUPPRESS,
-                      help='--state_metrics: frames per bin of a state '
-                      '(default 12, at most 127)')
-  parser.add_argument('--triplet_metrics', action='store_true',
-                      default=argparse.SUPPRESS,
-                      help='also report `triplets`: the connected third-order '
-                      'correlations of all neuron triplets, generated against '
-                      'recorded, beside the floor two halves of the recorded '
-                      'trials score')
-  parser.add_argument('--triplet_bin', type=int, default=argparse.SUPPRESS,
-                      help='--triplet_metrics: frames per bin of a binary state '
-                      '(default 12)')
-  # (absent unless given, like --victor_purpura)
-  parser.add_argument('--interval_metrics', action='store_true',
-                      default=argparse.SUPPRESS,
-                      help='also report `intervals`: inter-spike-interval '
-                      'histogram, CV and serial correlation, Fano factor and '
-                      'count correlations across trials, generated against '
-                      'recorded, beside the floor two halves of the recorded '
-                      'trials score')
-  parser.add_argument('--max_isi', type=int, default=argparse.SUPPRESS,
-                      help='--interval_metrics: the longest interval with a '
-                      'histogram bin of its own, in frames (default 240, at '
-                      'most 4095)')
+  parser.add_argument('--batch_trials', default=DEFAULTS['batch_trials'],
+                      type=int, help='--device gpu: trials per launch')
+
+  def optional(name, help, **kwargs):
+    """Not a reference flag: absent from the namespace unless given, as main.py
+    --spike_metrics (a flag reads getattr(hparams, 'victor_purpura', False), a
+    value `option(hparams, 'vp_q')`; the help quotes DEFAULTS)."""
+    parser.add_argument(name, default=argparse.SUPPRESS,
+                        help=help.format(**DEFAULTS), **kwargs)
+
+  def flag(name, help):
+    optional(name, help, action='store_true')
+
+  flag('--victor_purpura',
+       'also report victor_purpura_kl, the KL of the Victor-Purpura distances '
+       'between the neurons of a trial')
+  optional('--vp_q', '--victor_purpura: cost per second of shifting a spike '
+           '(default {vp_q})', type=float)
+  flag('--temporal_metrics',
+       'also report `temporal`: autocorrelogram, lagged covariance, '
+       'cross-correlogram and population-count figures of the generated '
+       'against the recorded trials')
+  optional('--max_lag', '--temporal_metrics: largest lag in frames (default '
+           '{max_lag}, at most 256)', type=int)
+  flag('--spectral_metrics',
+       'also report `spectral`: power-spectrum figures of the generated '
+       'against the recorded calcium traces')
+  flag('--novelty_metrics',
+       'also report `novelty`: the distance from every generated trial to the '
+       'nearest stretch of the recording the run was trained on (a recording '
+       'directory), against the recording\'s distance to itself')
+  optional('--novelty_step', '--novelty_metrics: rows between two stretches '
+           '(default: the stride of the dataset)', type=int)
+  flag('--state_metrics',
+       'also report `states`: precision, recall and coverage of the generated '
+       'population states against the recorded ones, beside the floor two '
+       'halves of the recorded trials score')
+  optional('--state_k', '--state_metrics: the ball of a state reaches to its '
+           'k-th nearest neighbour (default {state_k}, at most 8)', type=int)
+  optional('--state_bin', '--state_metrics: frames per bin of a state (default '
+           '{state_bin}, at most 127)', type=int)
+  flag('--triplet_metrics',
+       'also report `triplets`: the connected third-order correlations of all '
+       'neuron triplets, generated against recorded, beside the floor two '
+       'halves of the recorded trials score')
+  optional('--triplet_bin', '--triplet_metrics: frames per bin of a binary '
+           'state (default {triplet_bin})', type=int)
+  flag('--interval_metrics',
+       'also report `intervals`: inter-spike-interval histogram, CV and serial '
+       'correlation, Fano factor and count correlations across trials, '
+       'generated against recorded, beside the floor two halves of the '
+       'recorded trials score')
+  optional('--max_isi', '--interval_metrics: the longest interval with a '
+           'histogram bin of its own, in frames (default {max_isi}, at most '
+           '4095)', type=int)
   return parser
 
 
